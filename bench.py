@@ -2,6 +2,17 @@
 """bench.py — Groth16 proofs/sec on MI355X (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--log-domain 20] [--curve bn128] [--kind dense] [--scheme g16]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps (ONE region),
+writes the last step's proof with --dump-outputs, and prints the line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, the configuration and the key's state).  Everything else the line can carry — the repeated regions,
+lone-proof latencies, the one-stream leg, the unbound region, roofline and clock figures, the CPU baseline and the oracle
+checks, the CLI-shaped legs, the N > 1 sharded / in-library single proofs, the box probes and BASELINE.json's other
+configurations — runs with --full (an option that asks for one of them explicitly runs it in a plain run too).
+--dump-outputs DIR writes the proof of the timed region's last step as DIR/proof_{a,b,c}.npy (float64: the coordinates as
+little-endian 32-bit limbs, [x, y] for A and C, [x, y] x [c0, c1] for B) and DIR/proof_infinity.npy (the three flags): the
+inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 A "step" is one Groth16 proof (sparse mat-vec, 6 NTTs, 5 MSMs, assembly) of the synthetic 2^20-constraint BN254
 circuit of BASELINE.json configs[1].  The proving key, the constraint system and the assignments are
@@ -73,7 +84,7 @@ def config_legs(args, budget_s=None):
         if left < 15:
             res[key] = {"config": what, "skipped": "time budget of the configs block (%.0f s) spent" % budget_s}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(leg_steps), "--warmup", "4", "--witnesses", "2", "--cpu-seconds", "0", "--e2e", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", str(leg_steps), "--warmup", "4", "--witnesses", "2", "--cpu-seconds", "0", "--e2e", "0",
                "--serial-proofs", "0", "--repeats", "2", "--oracle", "trapdoor", "--configs", "0"] + extra
         env = dict(os.environ, ZKHIP_BENCH_CHILD="1", ZKHIP_BENCH_LEG="1", ZKHIP_BENCH_STAGES="")
         env.pop("ZKHIP_BENCH_STAGES")
@@ -464,6 +475,18 @@ def make_witnesses(circ, seeds):
     return out
 
 
+def dump_proof(directory, raw, fq_bytes):
+    """--dump-outputs: one proof as a caller of the batch call receives it (8 coordinates of `fq_bytes` canonical little-endian bytes,
+    A | B | C, then three infinity flags: include/zkhip.h), written as float64 arrays — every 32-bit limb is exact in float64."""
+    os.makedirs(directory, exist_ok=True)
+    raw = np.frombuffer(raw, dtype=np.uint8)
+    limbs = np.frombuffer(raw[:8 * fq_bytes].tobytes(), dtype="<u4").astype(np.float64).reshape(8, fq_bytes // 4)
+    arrays = {"proof_a": limbs[0:2], "proof_b": limbs[2:6].reshape(2, 2, fq_bytes // 4), "proof_c": limbs[6:8],
+              "proof_infinity": raw[8 * fq_bytes:].astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -474,18 +497,18 @@ def main():
     ap.add_argument("--kind", default="dense", choices=["dense", "sha", "sha256", "poseidon"])
     ap.add_argument("--scheme", default="g16", choices=["g16", "gm17"])
     ap.add_argument("--witnesses", type=int, default=0, help="distinct assignments kept resident (0 = one per timed step)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--serial-proofs", type=int, default=3, help="proofs of the one-stream leg after the timed region (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="budget of the cpu_baseline leg (0 = skip; default 12 with --full, else 0)")
+    ap.add_argument("--serial-proofs", type=int, default=None, help="proofs of the one-stream leg after the timed region (0 = skip; default 3 with --full, else 0)")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed regions in all: `value` is the FIRST (the contract's K steps after W warm-up steps); the others repeat it and "
-                         "`repeats` reports every region, the median and the spread")
+                         "`repeats` reports every region, the median and the spread (default 3 with --full, else 1)")
     ap.add_argument("--constraints", type=int, default=0, help="exact constraint count (default 2^log_domain - 2, i.e. a domain of exactly 2^log_domain)")
-    ap.add_argument("--e2e", type=int, default=1,
+    ap.add_argument("--e2e", type=int, default=None,
                     help="after the timed region, time the reference-shaped flow `generate-proof` (program + witness + proving.key files -> "
-                         "proof.json, one fresh process per proof) through zokrates_amd.cli (0 = skip)")
+                         "proof.json, one fresh process per proof) through zokrates_amd.cli (0 = skip; default 1 with --full, else 0)")
     ap.add_argument("--members", type=int, default=0,
                     help="after the timed region, prove ONE proof across this many members inside the library (zkhip_prove_*_multi); "
-                         "members take the visible GPUs in turn, sharing them when there are fewer (0 = skip; N > 1 ranks: rank 0 drives all GPUs)")
+                         "members take the visible GPUs in turn, sharing them when there are fewer (0 = skip; N > 1 ranks with --full: rank 0 drives all GPUs)")
     ap.add_argument("--bind", type=int, default=1,
                     help="Groth16: bind the resident key to the resident constraint system before the timed region (zkhip_pk_bind_r1cs: four "
                          "transforms per proof instead of six, no C mat-vec, same proof bytes — checked here against an unbound proof; the line "
@@ -499,12 +522,21 @@ def main():
     ap.add_argument("--oracle", default="auto", choices=["auto", "algorithmic", "trapdoor", "none"],
                     help="what the device proof is held to: `algorithmic` = the cpu_baseline leg's proof (the C++ restatement of ark's prover, "
                          "needs --cpu-seconds > 0), `trapdoor` = the closed form from the setup's toxic waste (oracle/c, independent of every "
-                         "transform and MSM; seconds at any size), auto = algorithmic when the CPU leg runs (N = 1), trapdoor on rank 0 for N > 1, else none")
-    ap.add_argument("--configs", type=int, default=-1,
+                         "transform and MSM; seconds at any size), auto = algorithmic when the CPU leg runs (N = 1), trapdoor on rank 0 for N > 1 with --full, else none")
+    ap.add_argument("--configs", type=int, default=None,
                     help="after everything else, run BASELINE.json's other configurations as short legs (GM17 2^20, Poseidon chain on BLS12-381, "
                          "stdlib SHA-256 2^20, 2^22 on one GPU and as 8 members), each checked against the oracle's closed form, and append them as "
-                         "the LAST key of the line (`configs`).  -1 = only for the default workload on one GPU; 0 = never; 1 = always")
+                         "the LAST key of the line (`configs`).  -1 = only for the default workload on one GPU; 0 = never; 1 = always "
+                         "(default -1 with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the defaults above marked `with --full`, the lone-proof latencies, the load "
+                         "sampler and clock probe, the roofline figures, the box probes and, for N > 1, the sharded and in-library single proofs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proof of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    for opt, full_default, plain_default in (("cpu_seconds", 12.0, 0.0), ("serial_proofs", 3, 0), ("repeats", 3, 1), ("e2e", 1, 0), ("configs", -1, 0)):
+        if getattr(args, opt) is None:
+            setattr(args, opt, full_default if args.full else plain_default)
     # the host's explicit choice of HIP hardware queues (zkhip_init; the library never touches the environment itself): 16 for a process
     # with ONE resident prover, 8 as soon as it will hold several contexts (--members: every queue reserves scratch for the largest frame)
     # (ranks that SHARE a device — the ZKHIP_BENCH_DEVICE test hook — keep 8 queues each and no stream plan: two provers' 32 queues on one GPU
@@ -601,6 +633,9 @@ def main():
     # reproduce an unbound proof byte for byte, or the run goes on with the key as loaded and says so.
     bound, bound_rnd0 = {"bound": False}, None
     rnd0 = (1000, 3000, 2000) if gm17 else (1000, 2000)      # the randomness of the proof that is held against the oracle
+    # (N > 1 has no cpu_baseline leg: rank 0 holds its proof to the closed form instead — a second of host arithmetic after the timed region)
+    oracle_kind = args.oracle if args.oracle != "auto" else ("algorithmic" if (world == 1 and args.cpu_seconds > 0) else
+                                                             "trapdoor" if (world > 1 and args.full) else "none")
     if args.bind and os.environ.get("ZKHIP_BENCH_BIND") == "0":
         bound["note"] = "second attempt after a measuring process that died: the key is left as loaded"
     elif args.bind:
@@ -613,7 +648,8 @@ def main():
             bound["proof_identical_to_unbound"] = bool(same)
             bound["bound"] = bool(same)
             if same:
-                bound_rnd0 = prove_one(resident[0], rnd0)[0]   # (held against the oracle's proof below)
+                if oracle_kind != "none" or args.cpu_seconds > 0:
+                    bound_rnd0 = prove_one(resident[0], rnd0)[0]   # (held against the oracle's proof below)
             else:
                 pk.unbind()
         except native.ZkhipError as e:
@@ -632,9 +668,10 @@ def main():
     if args.warmup:
         _, tm1 = prove_one(resident[0], rs(0))
         single.append(tm1["total_ms"])
-    sampler = LoadSampler(pci)
-    idle_reading = sampler.read_once()
-    clock = ClockProbe(device)            # a second context's one-wave probe: the shader clock the proving kernels actually run at
+    # (the observers run with --full only: a plain run's timed region has the device to itself)
+    sampler = LoadSampler(pci) if args.full else None
+    idle_reading = sampler.read_once() if sampler else None
+    clock = ClockProbe(device) if args.full else None      # a second context's one-wave probe: the shader clock the proving kernels actually run at
     if args.warmup:
         # The W warm-up steps run the way the timed steps do — through the pipelined batch call — so that the timed region starts
         # on a chip in the state it will be measured in (clocks and power ramp over the first tens of milliseconds of load: with
@@ -645,8 +682,10 @@ def main():
         prove_many([resident[i % nw] for i in range(nwarm)], [rs(100 + i) for i in range(nwarm)])
     steps = [args.warmup + i for i in range(args.steps)]
     mark("warmup_done")
-    sampler.start()
-    clock.start()
+    bound["bound_in_timed_region"] = pk.is_bound(cs)      # the key's state as the timed region finds it (what `value_is` claims)
+    if args.full:
+        sampler.start()
+        clock.start()
     barrier_sync()
     t_begin = time.perf_counter()
     proofs, acc = prove_many([resident[j % nw] for j in steps], [rs(j) for j in steps])
@@ -654,6 +693,8 @@ def main():
     elapsed_local = time.perf_counter() - t_begin
     mark("timed_region_done")
     elapsed = ranks.max_over_ranks(elapsed_local)
+    if rank == 0 and args.dump_outputs:
+        dump_proof(args.dump_outputs, proofs[-1], native.FQ_BYTES[curve_id])
     # the same region again (`value` stays the first one): how far a number taken over K x 10 ms can be trusted
     region_ms = [1000.0 * elapsed / args.steps]
     for rep in range(1, max(1, args.repeats)):
@@ -662,26 +703,27 @@ def main():
         prove_many([resident[j % nw] for j in steps], [rs(j + 1000 * rep) for j in steps])
         barrier_sync()
         region_ms.append(1000.0 * ranks.max_over_ranks(time.perf_counter() - t0) / args.steps)
-    sampler.stop()
-    clock_regions = clock.window(t_begin, time.perf_counter())
     mark("repeats_done")
     per_rank = gather_per_rank(ranks, device, pci, placement, args.steps, elapsed_local)
-    # isolated single-proof latency (not part of the timed region): resident assignment, then from host memory
-    # (a lone proof's latency moves by +-0.4 ms from proof to proof — which streams' kernels meet on a dispatcher — and a minimum of three
-    # moved by 0.6 ms between processes of one build (profiles/r7r_*, r7s_*): sixteen proofs, the minimum as before and the spread beside it)
-    lone = []
-    for i in range(16):
-        _, tm1 = prove_one(resident[i % nw], rs(200 + i))
-        lone.append(tm1["total_ms"])
-    single.extend(lone)
-    single_ms = min(single)
-    lone.sort()
-    single_stats = {"proofs": len(lone), "min": lone[0], "median": lone[len(lone) // 2], "p90": lone[(9 * len(lone)) // 10], "max": lone[-1]}
-    from_host = []
-    for i in range(3):
-        t0 = time.perf_counter()
-        prove_one(zs[i % nw], rs(300 + i))
-        from_host.append(1000.0 * (time.perf_counter() - t0))
+    if args.full:
+        sampler.stop()
+        clock_regions = clock.window(t_begin, time.perf_counter())
+        # isolated single-proof latency (not part of the timed region): resident assignment, then from host memory
+        # (a lone proof's latency moves by +-0.4 ms from proof to proof — which streams' kernels meet on a dispatcher — and a minimum of three
+        # moved by 0.6 ms between processes of one build (profiles/r7r_*, r7s_*): sixteen proofs, the minimum as before and the spread beside it)
+        lone = []
+        for i in range(16):
+            _, tm1 = prove_one(resident[i % nw], rs(200 + i))
+            lone.append(tm1["total_ms"])
+        single.extend(lone)
+        single_ms = min(single)
+        lone.sort()
+        single_stats = {"proofs": len(lone), "min": lone[0], "median": lone[len(lone) // 2], "p90": lone[(9 * len(lone)) // 10], "max": lone[-1]}
+        from_host = []
+        for i in range(3):
+            t0 = time.perf_counter()
+            prove_one(zs[i % nw], rs(300 + i))
+            from_host.append(1000.0 * (time.perf_counter() - t0))
     # one-stream leg: the same proofs with every kernel on ONE stream -> un-overlapped kernel durations
     serial = None
     clock_serial = None
@@ -689,10 +731,11 @@ def main():
         ctx.tune("serial", 1)
         t_s0 = time.perf_counter()
         tms = [prove_one(resident[i % nw], rs(400 + i))[1] for i in range(args.serial_proofs + 1)][1:]
-        clock_serial = clock.window(t_s0, time.perf_counter())
+        clock_serial = clock.window(t_s0, time.perf_counter()) if clock else None
         ctx.tune("serial", 0)
         serial = {k: sum(t[k] for t in tms) / len(tms) for k in tms[0]}
-    clock.stop()
+    if clock:
+        clock.stop()
 
     # the same region once more with the key UNBOUND (six transforms, three mat-vecs): the same-box figure the binding is worth
     if bound["bound"] and args.bind == 1 and args.repeats > 1:          # (--bind 2: bound throughout — a trace of the bound pipeline only)
@@ -717,102 +760,103 @@ def main():
         value_bound, value_unbound = None, value_first
         key_state = "as loaded" + (" — FALLBACK: " + bound["note"] if os.environ.get("ZKHIP_BENCH_BIND") == "0" and args.bind else "")
     avg = {k: v / args.steps for k, v in acc.items()}
-    # ---- roofline of the dominant kernel (HIP events on the library's streams)
     m, N = circ.m, circ.N
     if gm17:   # the MSMs run over the SAP variables and the SAP domain
         m, N = pk.m, pk.hlen - 1
-    fq = native.FQ_BYTES[curve_id]
-    kernels = {
-        # algorithmic bytes per proof: bases read once + the 32-B scalars they pair with (SURVEY.md §8d (iv)+(v)); launches
-        "msm_accumulate<G2> (b_g2_query)": ("kernel_msm_accum_g2_ms", (m + 2) * (4 * fq + 32), 1),
-        # (a, b_g1 and l share the sorted assignment and run as ONE launch, h_query as another; ZKHIP_FUSE_Z=0: four)
-        "msm_accumulate<G1> (a/b_g1/l/h_query)": ("kernel_msm_accum_g1_ms", (3 * (m + 2) + N) * (2 * fq + 32), 4 if os.environ.get("ZKHIP_FUSE_Z") == "0" else 2),
-    }
-    name, (key, bytes_all, launches) = max(kernels.items(), key=lambda kv: avg[kv[1][0]])
-    ms = avg[key]
-    achieved = bytes_all / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    # HBM traffic per launch from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in
-    # separate runs; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950) — measured offline, same workload
-    traffic, traffic_ntt, traffic_cal = None, None, None
     default_workload = args.log_domain == 20 and args.curve == "bn128" and args.kind == "dense" and not gm17
-    evidence = offline_evidence() if default_workload else {"traffic": None, "valu": None, "stale": False}
-    pmc = evidence["traffic"]
-    if pmc:
-        ent = pmc.get("G2" if "G2" in name else "G1", {})
-        traffic = ent.get("traffic_bytes_per_launch")
-        traffic_cal = {"fetch_factor": ent.get("fetch_factor"), "pattern": ent.get("pattern"), "calibration": pmc.get("calibration")}
-        if traffic and "G1" in name:
-            # the file averages over the accumulation launches of its run; re-average if that run cut a proof's G1 work
-            # into a different number of launches than this build (the per-proof total is what was measured)
-            lpp = ent.get("launches_per_proof") or (ent["launches_fetch_pass"] / pmc["NTT"]["proofs"] if pmc.get("NTT", {}).get("proofs") else launches)
-            traffic = int(traffic * lpp / launches)
-        traffic_ntt = pmc.get("NTT", {}).get("traffic_bytes_per_pass")
-    # The honest bound of this kernel is VALU ISSUE (Montgomery products are multiply-adds; one wave64 instruction per 4 cycles and SIMD):
-    #   peak = the kernel's own VALU wave-instructions per launch (rocprofv3 SQ_INSTS_VALU of this build, profiles/pmc_valu.json)
-    #          issued by 1 024 SIMDs at the shader clock MEASURED IN THIS RUN beside the kernels (zkhip_ctx_clock_probe)
-    # expressed as mixed additions per second (one per non-zero signed digit, W digits per scalar).
-    W = msm_windows(synth.FR_BITS[curve_id], m + 2) if args.log_domain >= 15 else None
-    compute = None
-    pv = evidence["valu"]
-    if W and args.curve == "bn128" and args.kind == "dense":   # (sparse / boolean witnesses drop their zero digits: no fixed addition count)
-        madds = (((m + 2) if "G2" in name else (3 * (m + 2) + N)) * W)
-        group = "G2" if "G2" in name else "G1"
-        ghz = clock_regions.get("mean_ghz") or (pv or {}).get(group, {}).get("clock_ghz")
-        ghz_serial = (clock_serial or {}).get("mean_ghz") or ghz
-        ent = (pv or {}).get(group)
-        static = STATIC_VALU_PER_ADDITION.get(group)
-        # wave-instructions of one proof's launches of this kernel: counted (fresh counter file) or, failing that, the static count of the
-        # hot loop (profiles/r5_accum_isa_mix.txt) times the additions
-        instr = ent["valu_wave_instructions_per_launch"] * launches if ent else (madds * static / 64.0 if static else None)
-        compute = {"unit": "mixed additions/s", "achieved": madds / (ms * 1e-3), "windows": W,
-                   "valu_wave_instructions_per_proof": instr,
-                   "instructions_source": ("rocprofv3 SQ_INSTS_VALU of this build (profiles/pmc_valu.json: OFFLINE, fingerprinted)" if ent else
-                                           "static count of the hot loop x additions (no fresh counter file for this build)"),
-                   "shader_clock_ghz": ghz, "shader_clock_ghz_serial_leg": ghz_serial,
-                   "clock_source": "zkhip_ctx_clock_probe: one wavefront beside the kernels, shader cycles / wall clock (LIVE)" if clock_regions.get("mean_ghz") else
-                                   "derived from the counter pass (no live probe)",
-                   "kernel_on_synthetic_lists": {"additions_per_s": 5.57e9 if "G2" in name else 13.4e9, "source": "tools/accum_bench.hip, profiles/r5a_accum_bench.txt (round 5's `peak`: the kernel against itself)"}}
-        if instr and ghz:
-            t_issue_ms = instr / (1024 * ghz * 1e9 / 4) * 1e3                  # per proof, this kernel alone at the issue limit
-            compute["peak"] = madds / (t_issue_ms * 1e-3)
-            compute["peak_source"] = "VALU issue limit: 1024 SIMDs x shader clock / 4 cycles per wave64 instruction / the kernel's instructions per proof"
-            compute["frac"] = compute["achieved"] / compute["peak"]
-            if serial and serial[key] > 0 and ghz_serial:
-                compute["frac_serial"] = (instr / (1024 * ghz_serial * 1e9 / 4) * 1e3) / serial[key]
-        if world == 1 and not gm17 and pv:
-            compute["pipeline_issue_bound"] = pipeline_issue_bound(pv, 1000.0 * elapsed / args.steps, 8 if bound["bound"] else 12, ghz)
-    roofline = {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_ratio": (traffic / (bytes_all / launches)) if traffic else None,
-                "traffic_calibration": traffic_cal,
-                "traffic_source": ("offline rocprofv3 --pmc passes of this workload, " + PMC_TRAFFIC_FILE) if traffic else None,
-                "frac_serial": (bytes_all / (serial[key] * 1e-3) / 1e9 / HBM_PEAK_GBS) if serial and serial[key] > 0 else None,
-                "bytes_per_launch": bytes_all / launches, "ms_per_launch": ms / launches,
-                "ms_per_launch_serial": serial[key] / launches if serial else None, "launches_per_proof": launches,
-                "compute_bound": compute,
-                "offline_evidence": {k: evidence.get(k) for k in ("stale", "why", "csrc_hash", "files") if evidence.get(k) is not None},
-                "note": "bucket accumulation is bound by integer-multiply issue (Montgomery products), not by HBM; `frac` uses HIP-event "
-                        "intervals on the MSM streams inside the timed region (five MSMs and two proofs overlap), `frac_serial` the same "
-                        "kernels alone on one stream after it"}
-    # the NTT passes: 2 * N * 32 B per pass and vector; Groth16 runs 12 pass-vectors per proof (6 transforms: c
-    # needs only its coefficients; the reference runs 7), GM17 8 (4 transforms; the reference 5); the interval also
-    # holds the pointwise quotient kernel
-    passes = 8 if (gm17 or bound["bound"]) else 12
-    if N <= 1 << 10:
-        passes //= 2
-    ntt_bytes = passes * 2 * N * 32
-    roofline_ntt = {"bound": "hbm", "kernel": "ntt_cols / ntt_rows (%d pass-vectors of 2^%d elements per proof)" % (passes, int(np.log2(N))),
-                    "achieved": ntt_bytes / (avg["kernel_ntt_ms"] * 1e-3) / 1e9 if avg.get("kernel_ntt_ms", 0) > 0 else None,
-                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic_ntt, "traffic_ratio": (traffic_ntt / (2.0 * N * 32)) if traffic_ntt else None,
-                    "traffic_source": ("offline rocprofv3 --pmc passes of this workload, " + PMC_TRAFFIC_FILE) if traffic_ntt else None,
-                    "bytes_per_pass": 2 * N * 32}
-    if roofline_ntt["achieved"]:
-        roofline_ntt["frac"] = roofline_ntt["achieved"] / HBM_PEAK_GBS
-        roofline_ntt["us_per_pass"] = 1000.0 * avg["kernel_ntt_ms"] / passes
-    if serial and serial.get("kernel_ntt_ms", 0) > 0:
-        roofline_ntt["frac_serial"] = ntt_bytes / (serial["kernel_ntt_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-        roofline_ntt["us_per_pass_serial"] = 1000.0 * serial["kernel_ntt_ms"] / passes
-    b_alg = gm17_algorithmic_bytes(circ, fq, m, N) if gm17 else proof_algorithmic_bytes(circ, fq)
+    if args.full:
+        # ---- roofline of the dominant kernel (HIP events on the library's streams)
+        fq = native.FQ_BYTES[curve_id]
+        kernels = {
+            # algorithmic bytes per proof: bases read once + the 32-B scalars they pair with (SURVEY.md §8d (iv)+(v)); launches
+            "msm_accumulate<G2> (b_g2_query)": ("kernel_msm_accum_g2_ms", (m + 2) * (4 * fq + 32), 1),
+            # (a, b_g1 and l share the sorted assignment and run as ONE launch, h_query as another; ZKHIP_FUSE_Z=0: four)
+            "msm_accumulate<G1> (a/b_g1/l/h_query)": ("kernel_msm_accum_g1_ms", (3 * (m + 2) + N) * (2 * fq + 32), 4 if os.environ.get("ZKHIP_FUSE_Z") == "0" else 2),
+        }
+        name, (key, bytes_all, launches) = max(kernels.items(), key=lambda kv: avg[kv[1][0]])
+        ms = avg[key]
+        achieved = bytes_all / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+        # HBM traffic per launch from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in
+        # separate runs; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950) — measured offline, same workload
+        traffic, traffic_ntt, traffic_cal = None, None, None
+        evidence = offline_evidence() if default_workload else {"traffic": None, "valu": None, "stale": False}
+        pmc = evidence["traffic"]
+        if pmc:
+            ent = pmc.get("G2" if "G2" in name else "G1", {})
+            traffic = ent.get("traffic_bytes_per_launch")
+            traffic_cal = {"fetch_factor": ent.get("fetch_factor"), "pattern": ent.get("pattern"), "calibration": pmc.get("calibration")}
+            if traffic and "G1" in name:
+                # the file averages over the accumulation launches of its run; re-average if that run cut a proof's G1 work
+                # into a different number of launches than this build (the per-proof total is what was measured)
+                lpp = ent.get("launches_per_proof") or (ent["launches_fetch_pass"] / pmc["NTT"]["proofs"] if pmc.get("NTT", {}).get("proofs") else launches)
+                traffic = int(traffic * lpp / launches)
+            traffic_ntt = pmc.get("NTT", {}).get("traffic_bytes_per_pass")
+        # The honest bound of this kernel is VALU ISSUE (Montgomery products are multiply-adds; one wave64 instruction per 4 cycles and SIMD):
+        #   peak = the kernel's own VALU wave-instructions per launch (rocprofv3 SQ_INSTS_VALU of this build, profiles/pmc_valu.json)
+        #          issued by 1 024 SIMDs at the shader clock MEASURED IN THIS RUN beside the kernels (zkhip_ctx_clock_probe)
+        # expressed as mixed additions per second (one per non-zero signed digit, W digits per scalar).
+        W = msm_windows(synth.FR_BITS[curve_id], m + 2) if args.log_domain >= 15 else None
+        compute = None
+        pv = evidence["valu"]
+        if W and args.curve == "bn128" and args.kind == "dense":   # (sparse / boolean witnesses drop their zero digits: no fixed addition count)
+            madds = (((m + 2) if "G2" in name else (3 * (m + 2) + N)) * W)
+            group = "G2" if "G2" in name else "G1"
+            ghz = clock_regions.get("mean_ghz") or (pv or {}).get(group, {}).get("clock_ghz")
+            ghz_serial = (clock_serial or {}).get("mean_ghz") or ghz
+            ent = (pv or {}).get(group)
+            static = STATIC_VALU_PER_ADDITION.get(group)
+            # wave-instructions of one proof's launches of this kernel: counted (fresh counter file) or, failing that, the static count of the
+            # hot loop (profiles/r5_accum_isa_mix.txt) times the additions
+            instr = ent["valu_wave_instructions_per_launch"] * launches if ent else (madds * static / 64.0 if static else None)
+            compute = {"unit": "mixed additions/s", "achieved": madds / (ms * 1e-3), "windows": W,
+                       "valu_wave_instructions_per_proof": instr,
+                       "instructions_source": ("rocprofv3 SQ_INSTS_VALU of this build (profiles/pmc_valu.json: OFFLINE, fingerprinted)" if ent else
+                                               "static count of the hot loop x additions (no fresh counter file for this build)"),
+                       "shader_clock_ghz": ghz, "shader_clock_ghz_serial_leg": ghz_serial,
+                       "clock_source": "zkhip_ctx_clock_probe: one wavefront beside the kernels, shader cycles / wall clock (LIVE)" if clock_regions.get("mean_ghz") else
+                                       "derived from the counter pass (no live probe)",
+                       "kernel_on_synthetic_lists": {"additions_per_s": 5.57e9 if "G2" in name else 13.4e9, "source": "tools/accum_bench.hip, profiles/r5a_accum_bench.txt (round 5's `peak`: the kernel against itself)"}}
+            if instr and ghz:
+                t_issue_ms = instr / (1024 * ghz * 1e9 / 4) * 1e3                  # per proof, this kernel alone at the issue limit
+                compute["peak"] = madds / (t_issue_ms * 1e-3)
+                compute["peak_source"] = "VALU issue limit: 1024 SIMDs x shader clock / 4 cycles per wave64 instruction / the kernel's instructions per proof"
+                compute["frac"] = compute["achieved"] / compute["peak"]
+                if serial and serial[key] > 0 and ghz_serial:
+                    compute["frac_serial"] = (instr / (1024 * ghz_serial * 1e9 / 4) * 1e3) / serial[key]
+            if world == 1 and not gm17 and pv:
+                compute["pipeline_issue_bound"] = pipeline_issue_bound(pv, 1000.0 * elapsed / args.steps, 8 if bound["bound"] else 12, ghz)
+        roofline = {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_ratio": (traffic / (bytes_all / launches)) if traffic else None,
+                    "traffic_calibration": traffic_cal,
+                    "traffic_source": ("offline rocprofv3 --pmc passes of this workload, " + PMC_TRAFFIC_FILE) if traffic else None,
+                    "frac_serial": (bytes_all / (serial[key] * 1e-3) / 1e9 / HBM_PEAK_GBS) if serial and serial[key] > 0 else None,
+                    "bytes_per_launch": bytes_all / launches, "ms_per_launch": ms / launches,
+                    "ms_per_launch_serial": serial[key] / launches if serial else None, "launches_per_proof": launches,
+                    "compute_bound": compute,
+                    "offline_evidence": {k: evidence.get(k) for k in ("stale", "why", "csrc_hash", "files") if evidence.get(k) is not None},
+                    "note": "bucket accumulation is bound by integer-multiply issue (Montgomery products), not by HBM; `frac` uses HIP-event "
+                            "intervals on the MSM streams inside the timed region (five MSMs and two proofs overlap), `frac_serial` the same "
+                            "kernels alone on one stream after it"}
+        # the NTT passes: 2 * N * 32 B per pass and vector; Groth16 runs 12 pass-vectors per proof (6 transforms: c
+        # needs only its coefficients; the reference runs 7), GM17 8 (4 transforms; the reference 5); the interval also
+        # holds the pointwise quotient kernel
+        passes = 8 if (gm17 or bound["bound"]) else 12
+        if N <= 1 << 10:
+            passes //= 2
+        ntt_bytes = passes * 2 * N * 32
+        roofline_ntt = {"bound": "hbm", "kernel": "ntt_cols / ntt_rows (%d pass-vectors of 2^%d elements per proof)" % (passes, int(np.log2(N))),
+                        "achieved": ntt_bytes / (avg["kernel_ntt_ms"] * 1e-3) / 1e9 if avg.get("kernel_ntt_ms", 0) > 0 else None,
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic_ntt, "traffic_ratio": (traffic_ntt / (2.0 * N * 32)) if traffic_ntt else None,
+                        "traffic_source": ("offline rocprofv3 --pmc passes of this workload, " + PMC_TRAFFIC_FILE) if traffic_ntt else None,
+                        "bytes_per_pass": 2 * N * 32}
+        if roofline_ntt["achieved"]:
+            roofline_ntt["frac"] = roofline_ntt["achieved"] / HBM_PEAK_GBS
+            roofline_ntt["us_per_pass"] = 1000.0 * avg["kernel_ntt_ms"] / passes
+        if serial and serial.get("kernel_ntt_ms", 0) > 0:
+            roofline_ntt["frac_serial"] = ntt_bytes / (serial["kernel_ntt_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            roofline_ntt["us_per_pass_serial"] = 1000.0 * serial["kernel_ntt_ms"] / passes
+        b_alg = gm17_algorithmic_bytes(circ, fq, m, N) if gm17 else proof_algorithmic_bytes(circ, fq)
     workload = (f"synthetic R1CS {args.kind}, n = 2^{args.log_domain} - 2 constraints, {args.curve} GM17 (SAP: {m} variables, domain {N}), "
                 f"4 NTTs + 5 MSMs per proof") if gm17 else (
         (f"Poseidon hash chain depth {circ.depth} (t = 3, 243 constraints per hash), n = {circ.n} constraints (QAP domain 2^{args.log_domain}), "
@@ -837,11 +881,7 @@ def main():
                    "process_group": ranks.describe(),
                    "launcher": ("bench.py --gpus N started the ranks itself" if os.environ.get("ZKHIP_BENCH_LAUNCHED") == "self" else
                                 "external launcher (torch.distributed.run)" if world > 1 else "single process")},
-        "single_proof_ms": single_ms, "single_proof_unbound_ms": bound.get("unbound_single_proof_ms"),
-        "single_proof_ms_stats": single_stats, "single_proof_from_host_ms": min(from_host), "phases_ms": avg, "phases_ms_serial": serial,
-        "whole_proof_hbm": {"algorithmic_bytes": b_alg, "achieved_GBs": b_alg / (elapsed / args.steps) / 1e9,
-                            "frac": b_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS},
-        "roofline": roofline, "roofline_ntt": roofline_ntt,
+        "phases_ms": avg,
         "host_ms": {"setup_gpu": 1000 * t_setup, "pk_load": 1000 * t_pkload, "assignment_h2d": 1000 * t_h2d,
                     "witness_generation_total": 1000 * t_witness},
         "timeline_s": timeline,
@@ -850,9 +890,6 @@ def main():
                     "spread": (max(region_ms) - min(region_ms)) / float(np.median(region_ms)),
                     "value_of_median": world * 1000.0 / float(np.median(region_ms)),
                     "note": "`value` / `ms_per_step` are the FIRST region; every region is K steps over the same K resident witnesses"},
-        "under_load": sampler.summary(idle_reading),
-        "shader_clock": {"timed_regions": clock_regions, "serial_leg": clock_serial,
-                         "source": "zkhip_ctx_clock_probe on a second context of the same device, 2 ms readings back to back (shader cycles / wall clock of one sleeping wavefront)"},
         "per_rank": per_rank,
         "bound_key": bound,
         "stream_plan": {"on": stream_plan, "plan": os.environ.get("ZKHIP_PIPES") or ("M=2,N=3,O=1,n=3,G0=0,Z0=1,H0=0,G1=3,Z1=1,H1=0,G2=3,Z2=2,H2=1" if stream_plan else None),
@@ -861,27 +898,42 @@ def main():
                                 "profiles/r7f_*, r7h_*); against streams made in order of first use (profiles/r7g_*, r7h_*): the dense circuit level in batches and a lone "
                                 "proof 0.25-0.3 ms sooner, stdlib SHA-256 +8-9 %, Poseidon / BLS12-381 +3 %, GM17 level — every leg of this line asks for it"},
     }
+    if serial and not args.full:          # (an explicit --serial-proofs in a plain run; --full reports it below)
+        out["phases_ms_serial"] = serial
+    if args.full:
+        out.update({
+            "single_proof_ms": single_ms, "single_proof_unbound_ms": bound.get("unbound_single_proof_ms"),
+            "single_proof_ms_stats": single_stats, "single_proof_from_host_ms": min(from_host), "phases_ms_serial": serial,
+            "whole_proof_hbm": {"algorithmic_bytes": b_alg, "achieved_GBs": b_alg / (elapsed / args.steps) / 1e9,
+                                "frac": b_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS},
+            "roofline": roofline, "roofline_ntt": roofline_ntt,
+            "under_load": sampler.summary(idle_reading),
+            "shader_clock": {"timed_regions": clock_regions, "serial_leg": clock_serial,
+                             "source": "zkhip_ctx_clock_probe on a second context of the same device, 2 ms readings back to back (shader cycles / wall clock of one sleeping wavefront)"},
+        })
     # ---- optional legs (latency mode): a watchdog guarantees that the throughput line is printed even if one of them hangs
     # (a collective after an asymmetric failure; the in-library path on hardware this container cannot test)
     import threading
-    members = args.members or (world if world > 1 else 0)
+    sharded = world > 1 and args.full
+    members = args.members or (world if sharded else 0)
 
     def give_up():
         if rank == 0:
             note = {"error": "timed out after %d s" % SHARDED_LEG_TIMEOUT_S}
-            if world > 1:
+            if sharded:
                 out.setdefault("sharded_single_proof", note)
             if members >= 1:
                 out.setdefault("multi_single_proof", note)
-            out["cpu_baseline"] = None
+            if args.full or args.cpu_seconds > 0:
+                out["cpu_baseline"] = None
             print(json.dumps(out), flush=True)
         os._exit(0)
 
     watchdog = threading.Timer(SHARDED_LEG_TIMEOUT_S, give_up)
     watchdog.daemon = True
-    if world > 1 or members >= 1:
+    if sharded or members >= 1:
         watchdog.start()
-    if world > 1:
+    if sharded:
         # ONE proof sharded over all ranks (1/world of the bases per GPU, RCCL all-gather of the partial records);
         # reported next to the throughput metric, never instead of it
         try:
@@ -908,8 +960,6 @@ def main():
         ranks.host_barrier()      # the other ranks idle (on the host: no collective kernel parked on their GPUs) while rank 0
                                   # drives every GPU through the library
     watchdog.cancel()
-    # (N > 1 has no cpu_baseline leg: rank 0 holds its proof to the closed form instead — a second of host arithmetic after the timed region)
-    oracle_kind = args.oracle if args.oracle != "auto" else ("algorithmic" if (world == 1 and args.cpu_seconds > 0) else "trapdoor" if world > 1 else "none")
     if rank == 0 and world == 1 and args.cpu_seconds > 0:
         base, cpu_proof = cpu_baseline(circ, pk_bytes, zs[0], args.cpu_seconds, gm17)
         out["cpu_baseline"] = base
@@ -926,7 +976,7 @@ def main():
         if oracle_kind == "algorithmic":
             out["identical_to_oracle"] = bool(out["cpu_baseline"]["gpu_proof_identical"] and (bound_rnd0 is None or bound_rnd0 == cpu_proof))
             out["oracle"] = "algorithmic restatement of ark's prover (oracle/c), the cpu_baseline leg's proof"
-    elif rank == 0:
+    elif rank == 0 and args.full:
         out["cpu_baseline"] = None   # N > 1 or --cpu-seconds 0
     if rank == 0 and oracle_kind == "trapdoor":
         # the closed form from the toxic waste of this run's own setup (oracle/c orc_trapdoor / orc_gm17_trapdoor): no transform, no MSM
@@ -943,7 +993,7 @@ def main():
             out["oracle"] = "trapdoor check failed to run: %r" % (e,)
     if rank == 0 and world == 1 and args.e2e:
         out["cli_end_to_end_ms"] = cli_end_to_end(circ, curve_id, pk_bytes, zs[0], args.scheme, ctx, pk, cs)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         out["box_probe"] = box_probe()
         out["rocm_smi"] = rocm_smi()
     want_configs = args.configs == 1 or (args.configs == -1 and default_workload and world == 1 and not os.environ.get("ZKHIP_BENCH_LEG"))

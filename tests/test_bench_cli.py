@@ -33,7 +33,7 @@ def run_bench(args, extra_env=None, timeout=900, expect_rc=0):
 ])
 def test_single_rank_contract(args, metric):
     with_cli_leg = "--scheme" not in args and "--kind" not in args      # the CLI-shaped leg (seven subprocesses) once is enough
-    lines = run_bench(args + ["--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2"] + ([] if with_cli_leg else ["--e2e", "0"]),
+    lines = run_bench(args + ["--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.2"] + ([] if with_cli_leg else ["--e2e", "0"]),
                       extra_env={"ZKHIP_BENCH_CLI_ALL": "1"})
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -53,6 +53,7 @@ def test_single_rank_contract(args, metric):
     assert "under_load" in d                            # (no sysfs view of a GPU here: the sampler says so instead of inventing numbers)
     b = d["bound_key"]                                  # either scheme runs with the key bound to its system, checked against an unbound proof and the CPU's
     assert b["bound"] is True and b["proof_identical_to_unbound"] is True and b["bind_ms"] > 0 and b["unbound_ms_per_step"] > 0, b
+    assert b["bound_in_timed_region"] is True, b
     assert c["gpu_bound_key_proof_identical"] is True
     if metric == "groth16_proofs_per_sec":
         assert "4 NTTs" in d["config"]["workload"]
@@ -72,6 +73,51 @@ def test_single_rank_contract(args, metric):
     assert chk["verified"] is True and chk["verify_ms"] > 0 and chk["proof_json_identical_to_resident_prover"] is True, chk
 
 
+# what only `--full` adds to the line: a plain run carries the headline figure, the configuration and the key's state
+FULL_ONLY = ["cpu_baseline", "roofline", "roofline_ntt", "whole_proof_hbm", "single_proof_ms", "single_proof_ms_stats", "single_proof_from_host_ms",
+             "under_load", "shader_clock", "identical_to_oracle", "cli_end_to_end_ms", "box_probe", "rocm_smi", "configs", "sharded_single_proof",
+             "multi_single_proof"]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: ONE timed region of exactly K steps and none of the other legs.  --dump-outputs
+    writes the proof of the region's last step; two runs with the same arguments write the same arrays, and they are the proof the
+    oracle's closed form gives for that step's witness and (r, s)."""
+    import numpy as np
+    from oracle import cpu
+    from zokrates_amd import synth
+    steps, warmup = 3, 1
+    docs = []
+    for run in ("a", "b"):
+        lines = run_bench(["--log-domain", "5", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / run)])
+        assert len(lines) == 1
+        docs.append(json.loads(lines[0]))
+    d = docs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "bound_key"):
+        assert k in d, k
+    assert d["metric"] == "groth16_proofs_per_sec" and d["unit"] == "proofs/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["steps"] == steps and d["warmup"] == warmup and d["value"] > 0 and abs(d["ms_per_step"] * d["value"] - 1000.0) < 1e-6 * 1000
+    assert d["repeats"]["regions"] == 1 and d["value_is"] == "value_bound" and d["bound_key"]["bound"] is True
+    # (a bound and an unbound key give the same proof bytes: what the timed region ran with is read from the library itself)
+    assert d["bound_key"]["bound_in_timed_region"] is True, d["bound_key"]
+    assert "unbound_ms_per_step" not in d["bound_key"] and not [k for k in FULL_ONLY if k in d], [k for k in FULL_ONLY if k in d]
+    arrays = {}
+    for name in ("proof_a", "proof_b", "proof_c", "proof_infinity"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+        arrays[name] = a
+    assert arrays["proof_a"].shape == (2, 8) and arrays["proof_b"].shape == (2, 2, 8) and arrays["proof_c"].shape == (2, 8)
+    raw = np.concatenate([arrays[n].ravel() for n in ("proof_a", "proof_b", "proof_c")]).astype("<u4").tobytes()
+    raw += arrays["proof_infinity"].astype(np.uint8).tobytes()
+    # the last timed step is step W + K - 1: witness (W + K - 1) mod K of the K resident ones, (r, s) = rs(W + K - 1) of bench.main
+    j = warmup + steps - 1
+    circ = synth.circuit(0, 5, kind="dense")
+    z = circ.assignment(0x5EED0000 + j % steps)
+    oc = cpu.Circuit.from_csr(0, circ.n, circ.l, circ.w, circ.mats())
+    tb = b"".join(int(v).to_bytes(32, "little") for v in synth.toxic_waste(0, 0xC0FFEE))
+    assert raw == cpu.trapdoor(oc, tb, z, 0x1111111111111111 * (j + 1), 0x2222222222222222 * (j + 3))
+
+
 @pytest.mark.parametrize("scheme,port", [("g16", "29541")])      # (the sharded GM17 proof over two processes: tests/test_multiprocess.py)
 def test_two_ranks_real_bench_script(scheme, port):
     world = 2
@@ -79,7 +125,7 @@ def test_two_ranks_real_bench_script(scheme, port):
     for rank in range(world):
         env = dict(os.environ, ZKHIP_LIBRARY=EMU_LIB, ZKHIP_DIST_BACKEND="gloo", ZKHIP_BENCH_DEVICE="0", RANK=str(rank), LOCAL_RANK=str(rank),
                    WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=port)
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log-domain", "5", "--steps", "2", "--warmup", "1", "--scheme", scheme],
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--log-domain", "5", "--steps", "2", "--warmup", "1", "--scheme", scheme],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=900) for p in procs]
     for p, (out, err) in zip(procs, outs):
@@ -104,7 +150,7 @@ def test_gpus_flag_alone_starts_the_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ZKHIP_LIBRARY=EMU_LIB, ZKHIP_DIST_BACKEND="gloo", ZKHIP_BENCH_DEVICE="0")
     emu_library()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log-domain", "5", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--log-domain", "5", "--steps", "2", "--warmup", "1"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -137,11 +183,12 @@ def test_more_gpus_asked_for_than_visible_fails_loudly():
 def test_stalled_optional_leg_still_prints_the_line():
     """An optional latency leg that never returns (a hung collective, an untested multi-GPU path): the watchdog prints the
     throughput line with the leg marked as timed out and the process exits 0 — the driver's bench run must not lose its line."""
-    lines = run_bench(["--log-domain", "5", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--members", "2"],
+    lines = run_bench(["--full", "--log-domain", "5", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--members", "2"],
                       extra_env={"ZKHIP_BENCH_TEST_STALL": "1", "ZKHIP_BENCH_LEG_TIMEOUT_S": "3"}, timeout=300)
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["value"] > 0 and "timed out" in d["multi_single_proof"]["error"] and d["cpu_baseline"] is None
+    assert d["bound_key"]["bound"] is True and d["bound_key"]["bound_in_timed_region"] is True, d["bound_key"]      # (no oracle leg in this run)
     for k in REQUIRED:
         assert k in d, k
 
@@ -157,6 +204,7 @@ def test_measuring_process_that_dies_is_reported_and_retried():
     assert d["value"] > 0 and len(d["attempts"]) == 2
     assert d["attempts"][0]["signal"] == 6 and d["attempts"][0]["last_stage"] == "context_created" and d["attempts"][1]["exit_status"] == 0
     assert d["bound_key"]["bound"] is False and "second attempt" in d["bound_key"]["note"]      # the retry leaves the key as loaded
+    assert d["bound_key"]["bound_in_timed_region"] is False
     assert "6 NTTs" in d["config"]["workload"]
     assert d["value_is"] == "value_unbound" and d["value_bound"] is None and "FALLBACK" in d["key_state"]      # ... and the line says so at top level
     lines = run_bench(args, extra_env={"ZKHIP_BENCH_TEST_DIE": "*"}, expect_rc=1)
@@ -247,7 +295,7 @@ def test_bench_window_count_mirrors_the_library_rule():
 def test_config_legs_of_the_default_line():
     """The default line carries BASELINE.json's other configurations as its LAST key: short runs of the same script, each bound and
     held to the oracle's closed form.  Here at toy size through the hook that overrides the legs' arguments."""
-    lines = run_bench(["--log-domain", "5", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--e2e", "0", "--configs", "1"],
+    lines = run_bench(["--full", "--log-domain", "5", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--e2e", "0", "--configs", "1"],
                       extra_env={"ZKHIP_BENCH_TEST_LEGS": "1"}, timeout=1500)
     d = json.loads(lines[0])
     assert list(d.keys())[-2:] == ["configs", "attempts"] or list(d.keys())[-1] == "configs", list(d.keys())[-3:]

@@ -7,7 +7,7 @@ out=$root/gpurun_out/$tag
 mkdir -p "$out"
 cd "$root"
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || { echo "SMOKE FAILED: giving the box back"; tail -5 "$out/smoke.log"; exit 0; }
-B="timeout 300 python bench.py --cpu-seconds 0 --steps 32 $*"
+B="timeout 300 python bench.py --full --cpu-seconds 0 --steps 32 $*"
 for rep in 1 2; do
   ZKHIP_LIBRARY=$root/$la $B >> "$out/bench_A.json" 2>> "$out/bench.err"
   ZKHIP_LIBRARY=$root/$lb $B >> "$out/bench_B.json" 2>> "$out/bench.err"

@@ -12,7 +12,7 @@ mkdir -p "$out"
 cd "$root"
 last=${libs[${#libs[@]}-1]}
 ZKHIP_LIBRARY=$root/$last timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q > "$out/parity_last.log" 2>&1; echo "parity($last) rc=$?"; tail -3 "$out/parity_last.log"
-B="timeout 300 python bench.py --cpu-seconds 0 --e2e 0 --steps 32 $*"
+B="timeout 300 python bench.py --full --cpu-seconds 0 --e2e 0 --steps 32 $*"
 for rep in $(seq 1 "$reps"); do
   for l in "${libs[@]}"; do
     n=$(basename "$l" .so)

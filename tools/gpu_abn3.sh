@@ -10,9 +10,9 @@ cd "$root"
 for rep in 1 2; do
   for l in "$@"; do
     n=$(basename "$l" .so)
-    ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --cpu-seconds 0 --e2e 0 --steps 32 >> "$out/dense_$n.json" 2>> "$out/bench.err"
-    ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --cpu-seconds 0 --e2e 0 --scheme gm17 --steps 16 >> "$out/gm17_$n.json" 2>> "$out/bench.err"
-    ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --cpu-seconds 0 --e2e 0 --curve bls12_381 --log-domain 18 --kind poseidon >> "$out/poseidon_$n.json" 2>> "$out/bench.err"
+    ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --full --cpu-seconds 0 --e2e 0 --steps 32 >> "$out/dense_$n.json" 2>> "$out/bench.err"
+    ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --full --cpu-seconds 0 --e2e 0 --scheme gm17 --steps 16 >> "$out/gm17_$n.json" 2>> "$out/bench.err"
+    ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --full --cpu-seconds 0 --e2e 0 --curve bls12_381 --log-domain 18 --kind poseidon >> "$out/poseidon_$n.json" 2>> "$out/bench.err"
   done
 done
 for w in dense gm17 poseidon; do for l in "$@"; do n=$(basename "$l" .so); python - "$out/${w}_$n.json" <<'PY'

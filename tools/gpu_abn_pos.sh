@@ -6,8 +6,8 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag
 mkdir -p "$out"; cd "$root"
 for rep in 1 2; do for l in "$@"; do n=$(basename "$l" .so)
-  ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --cpu-seconds 0 --e2e 0 --curve bls12_381 --log-domain 18 --kind poseidon >> "$out/poseidon_$n.json" 2>> "$out/bench.err"
-  ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --cpu-seconds 0 --e2e 0 --kind poseidon --log-domain 20 --steps 16 >> "$out/poseidon_bn_2e20_$n.json" 2>> "$out/bench.err"
+  ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --full --cpu-seconds 0 --e2e 0 --curve bls12_381 --log-domain 18 --kind poseidon >> "$out/poseidon_$n.json" 2>> "$out/bench.err"
+  ZKHIP_LIBRARY=$root/$l timeout 300 python bench.py --full --cpu-seconds 0 --e2e 0 --kind poseidon --log-domain 20 --steps 16 >> "$out/poseidon_bn_2e20_$n.json" 2>> "$out/bench.err"
 done; done
 for w in poseidon poseidon_bn_2e20; do for l in "$@"; do n=$(basename "$l" .so); python - "$out/${w}_$n.json" <<'PY'
 import json,sys

@@ -10,8 +10,8 @@ cd "$root"
 timeout 1200 python -m pytest tests/ -x -q -m gpu > "$out/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$out/pytest_gpu.log"
 tail -4 "$out/pytest_gpu.log"
 timeout 240 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1; tail -1 "$out/smoke.log"
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench_driver_command.json" 2> "$out/bench_driver_command.err"; echo "bench rc=$?"
-timeout 400 python bench.py --kind sha256 --cpu-seconds 0 --steps 16 > "$out/bench_sha256_with_cli_legs.json" 2> "$out/bench_sha256.err"; echo "sha256 rc=$?"
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$out/bench_driver_command.json" 2> "$out/bench_driver_command.err"; echo "bench rc=$?"
+timeout 400 python bench.py --full --kind sha256 --cpu-seconds 0 --steps 16 > "$out/bench_sha256_with_cli_legs.json" 2> "$out/bench_sha256.err"; echo "sha256 rc=$?"
 python - "$out" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]+"/bench_driver_command.json").readline())

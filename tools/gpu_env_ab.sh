@@ -14,8 +14,8 @@ timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log
 for rep in 1 2; do
   for s in "${settings[@]}"; do
     name=$(echo "$s" | tr -c 'A-Za-z0-9_=\n' '_')
-    if [ "$s" = "-" ]; then timeout 300 python bench.py --cpu-seconds 0 --steps 32 "$@" >> "$out/bench_$name.json" 2>> "$out/bench.err"
-    else env $s timeout 300 python bench.py --cpu-seconds 0 --steps 32 "$@" >> "$out/bench_$name.json" 2>> "$out/bench.err"; fi
+    if [ "$s" = "-" ]; then timeout 300 python bench.py --full --cpu-seconds 0 --steps 32 "$@" >> "$out/bench_$name.json" 2>> "$out/bench.err"
+    else env $s timeout 300 python bench.py --full --cpu-seconds 0 --steps 32 "$@" >> "$out/bench_$name.json" 2>> "$out/bench.err"; fi
   done
 done
 for f in "$out"/bench_*.json; do python - "$f" <<'PY'

@@ -9,7 +9,7 @@ mkdir -p "$out"
 cd "$root"
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || { echo "SMOKE FAILED: giving the box back"; tail -5 "$out/smoke.log"; exit 0; }
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace -d "$out/prof" -o t -- python "$root/bench.py" --cpu-seconds 0 --steps 8 --warmup 2 --serial-proofs 0 "$@" > "$out/prof.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace -d "$out/prof" -o t -- python "$root/bench.py" --full --cpu-seconds 0 --steps 8 --warmup 2 --serial-proofs 0 "$@" > "$out/prof.log" 2>&1
 db=$(find "$out/prof" -name "*.db" | head -1)
 grep -h '^{"metric"' "$out/prof.log" > "$out/bench_under_rocprof.json"
 for w in -6 -5 -4; do python "$root/tools/gantt.py" "$db" $w > "$out/single_proof_gantt_$w.txt" 2>&1; done

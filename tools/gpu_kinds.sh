@@ -7,7 +7,7 @@ out=$root/gpurun_out/$tag
 mkdir -p "$out"
 cd "$root"
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || { echo "SMOKE FAILED"; tail -5 "$out/smoke.log"; exit 0; }
-run() { name=$1; shift; timeout 400 python bench.py --cpu-seconds 0 --e2e 0 --steps 32 "$@" > "$out/bench_$name.json" 2>> "$out/bench.err"; }
+run() { name=$1; shift; timeout 400 python bench.py --full --cpu-seconds 0 --e2e 0 --steps 32 "$@" > "$out/bench_$name.json" 2>> "$out/bench.err"; }
 run dense
 run sha256 --kind sha256
 run sha256_2e18 --kind sha256 --log-domain 18

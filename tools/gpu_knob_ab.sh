@@ -9,7 +9,7 @@ cd "$root"
 i=0
 for kv in "$@"; do
   i=$((i+1))
-  env $kv timeout ${RUN_TIMEOUT:-40} python3 bench.py --steps ${STEPS:-24} --warmup 4 --cpu-seconds 0 --serial-proofs 0 --e2e 0 > "$out/run$i.json" 2> "$out/run$i.err"
+  env $kv timeout ${RUN_TIMEOUT:-40} python3 bench.py --full --steps ${STEPS:-24} --warmup 4 --cpu-seconds 0 --serial-proofs 0 --e2e 0 > "$out/run$i.json" 2> "$out/run$i.err"
   python3 - "$out/run$i.json" "$kv" <<'PY'
 import json,sys
 try:

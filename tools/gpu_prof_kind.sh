@@ -10,7 +10,7 @@ export ZKHIP_BENCH_CHILD=1
 for mode in serial pipelined; do
   [ $mode = serial ] && export ZKHIP_SERIAL=1 || unset ZKHIP_SERIAL
   rm -rf "$out/prof_$mode"
-  timeout 420 rocprofv3 --kernel-trace --stats -d "$out/prof_$mode" -o $mode -- python "$root/bench.py" --cpu-seconds 0 --steps 10 --warmup 2 --serial-proofs 0 --e2e 0 "$@" > "$out/prof_$mode.log" 2>&1
+  timeout 420 rocprofv3 --kernel-trace --stats -d "$out/prof_$mode" -o $mode -- python "$root/bench.py" --full --cpu-seconds 0 --steps 10 --warmup 2 --serial-proofs 0 --e2e 0 "$@" > "$out/prof_$mode.log" 2>&1
   db=$(find "$out/prof_$mode" -name "*.db" | head -1)
   [ -n "$db" ] && python "$root/tools/rocpd_stats.py" "$db" "$out/${tag}_${mode}_kernel_stats.md" > /dev/null
   grep -h '^{"metric"' "$out/prof_$mode.log" > "$out/${tag}_${mode}_bench_under_rocprof.json"

@@ -22,7 +22,7 @@ def plan_string(p):
 
 def run(plan, name):
     env = dict(os.environ, ZKHIP_BENCH_CHILD="1", ZKHIP_PIPES=plan_string(plan))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "6", "--witnesses", "2", "--cpu-seconds", "0", "--e2e", "0", "--serial-proofs", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "24", "--warmup", "6", "--witnesses", "2", "--cpu-seconds", "0", "--e2e", "0", "--serial-proofs", "0",
            "--repeats", "2", "--oracle", "none", "--configs", "0", "--bind", "2", "--pipe-plan", "1"] + WORKLOADS[name]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=150).stdout
