@@ -13,7 +13,7 @@
  *    failure — zokrates_ark/src/groth16.rs:41-44 `.unwrap()` — so the Rust shim turns non-zero
  *    into `panic!`.)
  *  - Field elements cross the boundary as canonical little-endian bytes (32 B for Fr; sz(Fq) =
- *    32 B for bn128, 48 B for bls12_381): the bytes of ark `ToBytes` / `Field::write`
+ *    32 B for bn128, 48 B for bls12_381 and bls12_377): the bytes of ark `ToBytes` / `Field::write`
  *    (/root/reference/zokrates_field/src/lib.rs:215-226).  Neither side needs the other's
  *    Montgomery constant.
  *  - Caller owns every input buffer for the duration of the call; the library copies what it
@@ -44,6 +44,7 @@ extern "C" {
 /* curve ids; names are zokrates_common::constants (/root/reference/zokrates_common/src/constants.rs:5-9) */
 #define ZKHIP_CURVE_BN128 0
 #define ZKHIP_CURVE_BLS12_381 1
+#define ZKHIP_CURVE_BLS12_377 2
 
 typedef struct zkhip_ctx zkhip_ctx;
 typedef struct zkhip_pk zkhip_pk;
@@ -255,7 +256,12 @@ int32_t zkhip_witness_map(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t*
 int32_t zkhip_msm_g1(zkhip_ctx* ctx, int32_t curve, uint64_t n, const uint8_t* bases, const uint8_t* scalars, uint8_t* out);
 int32_t zkhip_msm_g2(zkhip_ctx* ctx, int32_t curve, uint64_t n, const uint8_t* bases, const uint8_t* scalars, uint8_t* out);
 /* Element-wise Montgomery field ops on the device (parity tests): op 0 add, 1 sub, 2 mul;
- * field 0 = Fr, 1 = Fq; a, b, out: count x sz(field) canonical LE. */
+ * field 0 = Fr, 1 = Fq; a, b, out: count x sz(field) canonical LE.
+ * field 2 = Fq2 = Fq[u]/(u^2 + BETA) (BETA = 1 for bn128 and bls12_381, 5 for bls12_377), elements c0 then c1, 2 x sz(Fq), with
+ * the further ops 3 sqr and 4 inv (of a; 0 -> 0; b is read but not used); field 3 = the same field computed in the MSM kernels'
+ * unsaturated limbs, ops 2 and 3 in the accumulation kernel's inlined form, with the further ops 5 mul and 6 sqr (the
+ * out-of-line forms of the other kernels), 7 = a * b - a * a with one reduction per component (the fused Y3), and 8, 9, 10 =
+ * (3a)(4b), (3a)^2, (3a)(4b) - (3a)(4a) on un-reduced multiples (values up to 6p and 8p: the top of the forms' operand range). */
 int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op, uint64_t count,
                        const uint8_t* a, const uint8_t* b, uint8_t* out);
 

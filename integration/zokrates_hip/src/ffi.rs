@@ -12,6 +12,7 @@ use std::os::raw::c_char;
 
 pub const ZKHIP_CURVE_BN128: i32 = 0;
 pub const ZKHIP_CURVE_BLS12_381: i32 = 1;
+pub const ZKHIP_CURVE_BLS12_377: i32 = 2;
 
 pub const ZKHIP_TUNE_PIPE_PLAN: i32 = 28;
 

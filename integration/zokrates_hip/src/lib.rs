@@ -101,6 +101,7 @@ fn curve_id<T: Field>() -> (i32, usize) {
     match T::name() {
         "bn128" => (ffi::ZKHIP_CURVE_BN128, 32),
         "bls12_381" => (ffi::ZKHIP_CURVE_BLS12_381, 48),
+        "bls12_377" => (ffi::ZKHIP_CURVE_BLS12_377, 48),
         other => panic!("hip backend: unsupported curve {}", other),
     }
 }

@@ -3,7 +3,7 @@
     python -m zokrates_amd.build            # incremental
     python -m zokrates_amd.build --force
 
-The three translation units (two curves + the C ABI) compile in parallel; hipcc cross-compiles for
+The translation units (the G1 and G2 kernels and the prover of each of three curves, the C ABI, the file readers) compile in parallel; hipcc cross-compiles for
 gfx950 without a GPU.  The result `zokrates_amd/libzkhip.so` is git-ignored but travels to the GPU
 box with the repository snapshot.
 """
@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libzkhip.so")
-UNITS = ["bls381_g2", "bls381_g1", "bn254_g2", "bn254_g1", "curve_bn254", "curve_bls381", "zkhip_api", "ingest"]   # slowest first
+UNITS = ["bls381_g1", "bls377_g1", "bn254_g2", "bls377_g2", "bls381_g2", "bn254_g1", "curve_bn254", "curve_bls381", "curve_bls377", "zkhip_api", "ingest"]   # slowest first
 HEADERS = ["core.cuh", "devrt.h", "ec.cuh", "field.cuh", "fieldu.cuh", "kernels_msm.cuh", "kernels_ntt.cuh", "setup.cuh", "gm17.cuh", "group.cuh", "bind.cuh", "ingest.h"]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

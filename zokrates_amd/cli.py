@@ -78,7 +78,7 @@ def _curve_of(path):
     with open(path, "rb") as f:
         head = f.read(4096)
     if head[:4] == b"ZOK\0":
-        cid = {bytes.fromhex("b4f7b5bd"): 0, bytes.fromhex("40d8c1f9"): 1}.get(head[8:12])
+        cid = {bytes.fromhex("b4f7b5bd"): 0, bytes.fromhex("40d8c1f9"): 1, bytes.fromhex("c2955ab5"): 2}.get(head[8:12])
         if cid is None:
             sys.exit("unknown curve identifier in the program file")
         return cid

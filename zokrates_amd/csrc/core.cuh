@@ -1,6 +1,6 @@
 // core.cuh — host side of libzkhip.so: contexts, key/constraint-system residency and the Groth16 prover
-// schedule, templated on the curve.  Instantiated once per curve in curve_bn254.hip / curve_bls381.hip
-// (separate translation units so the two curves compile in parallel); the C ABI lives in zkhip_api.hip.
+// schedule, templated on the curve.  Instantiated once per curve in curve_bn254.hip / curve_bls381.hip / curve_bls377.hip
+// (separate translation units so the curves compile in parallel); the C ABI lives in zkhip_api.hip.
 //
 // Replaces `<Ark as Backend<T, G16>>::generate_proof` (/root/reference/zokrates_ark/src/groth16.rs:20-53)
 // from the point where the reference hands over to ark: `ProvingKey::deserialize_unchecked` (:40-42) and
@@ -50,6 +50,20 @@ struct CurveBls381 {
     // /root/reference/zokrates_proof_systems/src/solidity.rs:430-441
     static const u32* g1_gen() { static const u32 t[] = {0xdb22c6bbu, 0xfb3af00au, 0xf97a1aefu, 0x6c55e83fu, 0x171bac58u, 0xa14e3a3fu, 0x9774b905u, 0xc3688c4fu, 0x4fa9ac0fu, 0x2695638cu, 0x3197d794u, 0x17f1d3a7u, 0x46c5e7e1u, 0x0caa2329u, 0xa2888ae4u, 0xd03cc744u, 0x2c04b3edu, 0x00db18cbu, 0xd5d00af6u, 0xfcf5e095u, 0x741d8ae4u, 0xa09e30edu, 0xe3aaa0f1u, 0x08b3f481u}; return t; }
     static const u32* g2_gen() { static const u32 t[] = {0xc121bdb8u, 0xd48056c8u, 0xa805bbefu, 0x0bac0326u, 0x7ae3d177u, 0xb4510b64u, 0xfa403b02u, 0xc6e47ad4u, 0x2dc51051u, 0x26080527u, 0xf08f0a91u, 0x024aa2b2u, 0x5d042b7eu, 0xe5ac7d05u, 0x13945d57u, 0x334cf112u, 0xdc7f5049u, 0xb5da61bbu, 0x9920b61au, 0x596bd0d0u, 0x88274f65u, 0x7dacd3a0u, 0x52719f60u, 0x13e02b60u, 0x08b82801u, 0xe1935486u, 0x3baca289u, 0x923ac9ccu, 0x5160d12cu, 0x6d429a69u, 0x8cbdd3a7u, 0xadfd9baau, 0xda2e351au, 0x8cc9cdc6u, 0x727d6e11u, 0x0ce5d527u, 0xf05f79beu, 0xaaa9075fu, 0x5cec1da1u, 0x3f370d27u, 0x572e99abu, 0x267492abu, 0x85a763afu, 0xcb3e287eu, 0x2bc28b99u, 0x32acd2b0u, 0x2ea734ccu, 0x0606c4a0u}; return t; }
+};
+struct CurveBls377 {
+    static constexpr int ID = ZKHIP_CURVE_BLS12_377;
+    typedef Fe<Bls377Fr> Fr;
+    typedef Fe<Bls377Fq> Fq;
+    typedef Fe2<Bls377Fq> Fq2;       // u^2 = -5 (Bls377Fq::BETA)
+    static constexpr u64 GENERATOR = 22;
+    static constexpr int TWO_ADICITY = 47;
+    // generators of order r on y^2 = x^3 + 1 and on the twist y^2 = x^3 + 1/u, canonical limbs as above.  Written down as
+    // [UPSTREAM] ark-bls12-377 0.3.0's G1 / G2 generators; that ark uses exactly these points is NOT checked against its source
+    // (they are on their curves and of order r: tests/test_bls12_377.py).  Only a setup called without explicit generators reads
+    // them; proving never does, and ark's own setup draws random generators.
+    static const u32* g1_gen() { static const u32 t[] = {0xb21be9efu, 0xeab9b16eu, 0xffcd394eu, 0xd5481512u, 0xbd37cb5cu, 0x188282c8u, 0xaa9d41bbu, 0x85951e2cu, 0xbf87ff54u, 0xc8fc6225u, 0xfe740a67u, 0x008848deu, 0x559c8ea6u, 0xfd82de55u, 0x34a9591au, 0xc2fe3d36u, 0x4fb82305u, 0x6d182ad4u, 0xca3e52d9u, 0xbd7fb348u, 0x30afeec4u, 0x1f674f5du, 0xc5102effu, 0x01914a69u}; return t; }
+    static const u32* g2_gen() { static const u32 t[] = {0x7c005196u, 0x74e3e48fu, 0xbb535402u, 0x71889f52u, 0x57db6b9bu, 0x7ea501f5u, 0x203e5031u, 0xc565f071u, 0xa3841d01u, 0xc89630a2u, 0x71c785feu, 0x018480beu, 0x6ea16afeu, 0xb26bfefau, 0xbff76fe6u, 0x5cf89984u, 0x0799c9deu, 0xe7223eceu, 0x6651cecbu, 0x532777eeu, 0xb1b140d5u, 0x70dc5a51u, 0xe7004031u, 0x00ea6040u, 0x09fd4ddfu, 0xf0940944u, 0x6d8c7c2eu, 0xf2cf8888u, 0xf832d204u, 0xe458c282u, 0x74b49a58u, 0xde03ed72u, 0xcbb2efb4u, 0xd960736bu, 0x5d446f7bu, 0x00690d66u, 0x85eb8f93u, 0xd9a1cdd1u, 0x5e52270bu, 0x4279b83fu, 0xcee304c2u, 0x2463b01au, 0x3d591bf1u, 0x61ef11acu, 0x151a70aau, 0x9e549da3u, 0xd2835518u, 0x00f8169fu}; return t; }
 };
 
 struct ApiError {
@@ -424,7 +438,7 @@ static NttPlan<C>* get_plan(zkhip_ctx* ctx, int logN) {
         if (p->curve == C::ID && p->logN == logN) return (NttPlan<C>*)p.get();
     const int sub = ctx->ntt_max_sublog;
     require(logN >= 0 && logN <= 3 * sub && logN <= C::TWO_ADICITY, ZKHIP_ERR_BAD_ARG,
-            "domain size unsupported (log2 N must not exceed the field's two-adicity: 28 for bn128, 32 for bls12_381)");
+            "domain size unsupported (log2 N must not exceed the field's two-adicity: 28 for bn128, 32 for bls12_381, 47 for bls12_377)");
     auto* pl = new NttPlan<C>();
     ctx->plans.emplace_back(pl);
     pl->curve = C::ID;
@@ -2284,6 +2298,24 @@ struct Prover {
         stream_sync(s);
     }
 
+    // fields 2 and 3 of zkhip_field_op: Fq2 in the saturated form and in the MSM kernels' unsaturated one (k_field_op_fq2)
+    template <bool UNSAT>
+    static void field_op_fq2_api(zkhip_ctx* ctx, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+        typedef typename C::Fq2 F;
+        Stream s = ctx->stream;
+        const size_t bytes = count * sizeof(F);
+        ctx->cur->va.ensure(bytes); ctx->cur->vb.ensure(bytes);
+        dev_h2d(ctx->cur->va.p, a, bytes, s);
+        dev_h2d(ctx->cur->vb.p, b, bytes, s);
+        const unsigned T = 64, B = blocks_for(count, T);
+        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
+        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->vb), count);
+        ZK_LAUNCH((k_field_op_fq2<typename F::Params, UNSAT>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->va), count, op);
+        ZK_LAUNCH((k_from_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
+        dev_d2h(out, ctx->cur->va.p, bytes, s);
+        stream_sync(s);
+    }
+
     static void r1cs_load(zkhip_ctx* ctx, zkhip_r1cs* cs, const u64* const rp[3], const u32* const col[3], const uint8_t* const val[3]) {
         Stream s = ctx->stream;
         std::vector<u64> long_rows, huge_rows;
@@ -2382,7 +2414,9 @@ struct CurveOps {
 template <class C>
 static void field_op_dispatch(zkhip_ctx* ctx, int field, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
     if (field == 0) Prover<C>::template field_op_api<typename C::Fr>(ctx, op, count, a, b, out);
-    else Prover<C>::template field_op_api<typename C::Fq>(ctx, op, count, a, b, out);
+    else if (field == 1) Prover<C>::template field_op_api<typename C::Fq>(ctx, op, count, a, b, out);
+    else if (field == 2) Prover<C>::template field_op_fq2_api<false>(ctx, op, count, a, b, out);
+    else Prover<C>::template field_op_fq2_api<true>(ctx, op, count, a, b, out);
 }
 template <class C>
 static int ntt_log1_of(zkhip_ctx* ctx, int logN) { return get_plan<C>(ctx, logN)->split(); }
@@ -2442,4 +2476,5 @@ static CurveOps make_curve_ops() {
 }
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();
+const CurveOps* curve_ops_bls377();
 }  // namespace zk

@@ -55,6 +55,7 @@ struct Bn254Fq {
     static constexpr int N = 8;
     static constexpr int BITS = 254;
     static constexpr u32 INV = 0xe4866389u;
+    static constexpr u32 BETA = 1;   // Fq2 = Fq[u]/(u^2 + BETA)
     ZK_TABLE(mod, 8, 0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u)
     ZK_TABLE(r1, 8, 0xc58f0d9du, 0xd35d438du, 0xf5c70b3du, 0x0a78eb28u, 0x7879462cu, 0x666ea36fu, 0x9a07df2fu, 0x0e0a77c1u)
     ZK_TABLE(r2, 8, 0x538afa89u, 0xf32cfc5bu, 0xd44501fbu, 0xb5e71911u, 0x0a417ff6u, 0x47ab1effu, 0xcab8351fu, 0x06d89f71u)
@@ -71,12 +72,35 @@ struct Bls381Fq {
     static constexpr int N = 12;
     static constexpr int BITS = 381;
     static constexpr u32 INV = 0xfffcfffdu;
+    static constexpr u32 BETA = 1;
     ZK_TABLE(mod, 12, 0xffffaaabu, 0xb9feffffu, 0xb153ffffu, 0x1eabfffeu, 0xf6b0f624u, 0x6730d2a0u, 0xf38512bfu, 0x64774b84u,
              0x434bacd7u, 0x4b1ba7b6u, 0x397fe69au, 0x1a0111eau)
     ZK_TABLE(r1, 12, 0x0002fffdu, 0x76090000u, 0xc40c0002u, 0xebf4000bu, 0x53c758bau, 0x5f489857u, 0x70525745u, 0x77ce5853u,
              0xa256ec6du, 0x5c071a97u, 0xfa80e493u, 0x15f65ec3u)
     ZK_TABLE(r2, 12, 0x1c341746u, 0xf4df1f34u, 0x09d104f1u, 0x0a76e6a6u, 0x4c95b6d5u, 0x8de5476cu, 0x939d83c0u, 0x67eb88a9u,
              0xb519952du, 0x9a793e85u, 0x92cae3aau, 0x11988fe5u)
+};
+// BLS12-377 ([UPSTREAM] ark-bls12-377 0.3.0; /root/reference/zokrates_field/src/bls12_377.rs): r has 253 bits and two-adicity 47,
+// q has 377 bits (12 words, R = 2^384), and Fq2 = Fq[u]/(u^2 + 5): the one field here whose quadratic non-residue is not -1.
+struct Bls377Fr {
+    static constexpr int N = 8;
+    static constexpr int BITS = 253;
+    static constexpr u32 INV = 0xffffffffu;
+    ZK_TABLE(mod, 8, 0x00000001u, 0x0a118000u, 0xd0000001u, 0x59aa76feu, 0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu)
+    ZK_TABLE(r1, 8, 0xfffffff3u, 0x7d1c7fffu, 0x6ffffff2u, 0x7257f50fu, 0x512c0feeu, 0x16d81575u, 0x2bbb9a9du, 0x0d4bda32u)
+    ZK_TABLE(r2, 8, 0xb861857bu, 0x25d577bau, 0x8860591fu, 0xcc2c27b5u, 0xe5dc8593u, 0xa7cc008fu, 0xeff1c939u, 0x011fdae7u)
+};
+struct Bls377Fq {
+    static constexpr int N = 12;
+    static constexpr int BITS = 377;
+    static constexpr u32 INV = 0xffffffffu;
+    static constexpr u32 BETA = 5;
+    ZK_TABLE(mod, 12, 0x00000001u, 0x8508c000u, 0x30000000u, 0x170b5d44u, 0xba094800u, 0x1ef3622fu, 0x00f5138fu, 0x1a22d9f3u, 0x6ca1493bu,
+             0xc63b05c0u, 0x17c510eau, 0x01ae3a46u)
+    ZK_TABLE(r1, 12, 0xffffff68u, 0x02cdffffu, 0x7fffffb1u, 0x51409f83u, 0x8a7d3ff2u, 0x9f7db3a9u, 0x6e7c6305u, 0x7b4e97b7u, 0x803c84e8u,
+             0x4cf495bfu, 0xe2fdf49au, 0x008d6661u)
+    ZK_TABLE(r2, 12, 0x9400cd22u, 0xb786686cu, 0xb00431b1u, 0x0329fcaau, 0x62d6b46du, 0x22a5f111u, 0x827dc3acu, 0xbfdf7d03u, 0x41790bf9u,
+             0x837e92f0u, 0x1e914b88u, 0x006dfccbu)
 };
 
 // ---- element type ----
@@ -303,7 +327,7 @@ ZK_HD Fe<P> fe_from_u64(u64 x) {
 template <class P> ZK_HD Fe<P> ec_mul(const Fe<P>& a, const Fe<P>& b) { return fe_mul_nc(a, b); }
 template <class P> ZK_HD Fe<P> ec_sqr(const Fe<P>& a) { return fe_mul_nc(a, a); }
 
-// ---- quadratic extension Fq2 = Fq[u]/(u^2+1) (both supported curves) ----
+// ---- quadratic extension Fq2 = Fq[u]/(u^2 + BETA): BETA = 1 for BN254 and BLS12-381, 5 for BLS12-377 (P::BETA) ----
 template <class P>
 struct Fe2 {
     typedef P Params;
@@ -318,22 +342,41 @@ template <class P> ZK_HD Fe2<P> fe_add(const Fe2<P>& a, const Fe2<P>& b) { retur
 template <class P> ZK_HD Fe2<P> fe_sub(const Fe2<P>& a, const Fe2<P>& b) { return {fe_sub(a.c0, b.c0), fe_sub(a.c1, b.c1)}; }
 template <class P> ZK_HD Fe2<P> fe_neg(const Fe2<P>& a) { return {fe_neg(a.c0), fe_neg(a.c1)}; }
 template <class P> ZK_HD Fe2<P> fe_dbl(const Fe2<P>& a) { return {fe_dbl(a.c0), fe_dbl(a.c1)}; }
+// BETA * x by doubling and adding (canonical in, canonical out); the identity for BETA = 1
+template <class P>
+ZK_HD Fe<P> fe_times_beta(const Fe<P>& x) {
+    if constexpr (P::BETA == 1) {
+        return x;
+    } else {
+        static_assert(P::BETA == 5, "fe_times_beta: BETA in {1, 5}");
+        return fe_add(fe_dbl(fe_dbl(x)), x);
+    }
+}
 // Fq2 products are out-of-line calls as well (operands by value), built from fe_mul_nc
 template <class P>
-ZK_HD_CALL Fe2<P> fe_mul(const Fe2<P> a, const Fe2<P> b) {  // Karatsuba: 3 base-field products
+ZK_HD_CALL Fe2<P> fe_mul(const Fe2<P> a, const Fe2<P> b) {  // Karatsuba: 3 base-field products; c0 = a0 b0 - BETA a1 b1
     Fe<P> v0 = fe_mul_nc(a.c0, b.c0), v1 = fe_mul_nc(a.c1, b.c1);
     Fe<P> s = fe_mul_nc(fe_add(a.c0, a.c1), fe_add(b.c0, b.c1));
-    return {fe_sub(v0, v1), fe_sub(fe_sub(s, v0), v1)};
+    return {fe_sub(v0, fe_times_beta(v1)), fe_sub(fe_sub(s, v0), v1)};
 }
 template <class P>
 ZK_HD_CALL Fe2<P> fe_sqr(const Fe2<P> a) {  // complex squaring: 2 base-field products
-    Fe<P> t = fe_mul_nc(fe_add(a.c0, a.c1), fe_sub(a.c0, a.c1));
-    Fe<P> u = fe_mul_nc(a.c0, a.c1);
-    return {t, fe_dbl(u)};
+    if constexpr (P::BETA == 1) {
+        Fe<P> t = fe_mul_nc(fe_add(a.c0, a.c1), fe_sub(a.c0, a.c1));
+        Fe<P> u = fe_mul_nc(a.c0, a.c1);
+        return {t, fe_dbl(u)};
+    } else {
+        // (a0 + a1)(a0 - BETA a1) = a0^2 - BETA a1^2 - (BETA - 1) a0 a1: for BETA = 5 the square's c0 is that plus 4 a0 a1
+        static_assert(P::BETA == 5, "fe_sqr: BETA in {1, 5}");
+        Fe<P> t = fe_mul_nc(fe_add(a.c0, a.c1), fe_sub(a.c0, fe_times_beta(a.c1)));
+        Fe<P> u = fe_mul_nc(a.c0, a.c1);
+        Fe<P> u2 = fe_dbl(u);
+        return {fe_add(t, fe_dbl(u2)), u2};
+    }
 }
 template <class P>
-ZK_HD_CALL Fe2<P> fe_inv(const Fe2<P>& a) {
-    Fe<P> n = fe_inv(fe_add(fe_sqr(a.c0), fe_sqr(a.c1)));
+ZK_HD_CALL Fe2<P> fe_inv(const Fe2<P>& a) {  // (a0 - a1 u) / (a0^2 + BETA a1^2)
+    Fe<P> n = fe_inv(fe_add(fe_sqr(a.c0), fe_times_beta(fe_sqr(a.c1))));
     return {fe_mul(a.c0, n), fe_neg(fe_mul(a.c1, n))};
 }
 template <class P> ZK_HD Fe2<P> ec_mul(const Fe2<P>& a, const Fe2<P>& b) { return fe_mul(a, b); }

@@ -6,6 +6,7 @@
 // headroom to take every partial product of a column with NO carry at all:
 //     BN254 Fq:      9 limbs x 29 bits (R' = 2^261)  -> 166 G mul/s measured (tools/femul_bench.hip), 1.9x
 //     BLS12-381 Fq: 14 limbs x 28 bits (R' = 2^392)
+//     BLS12-377 Fq: 14 limbs x 28 bits (R' = 2^392; q has 377 bits, so values have 15 spare bits where BLS12-381 has 11)
 // Elements stay in Montgomery form w.r.t. R' and in a REDUNDANT representation: limbs may slightly exceed 2^B and
 // the integer value may be a small multiple of p above the canonical one.  Invariants (checked by the bounds notes in
 // ec.cuh and by the parity tests):
@@ -34,9 +35,11 @@ template <class P> struct UCfg;
 #endif
 template <> struct UCfg<Bn254Fq> { static constexpr int B = 29, N = 9, MUL_NQ = ZK_MUL_NQ; static constexpr bool FQ2_INLINE = true, MUL_CHAIN = ZK_MUL_CHAIN != 0; };
 template <> struct UCfg<Bls381Fq> { static constexpr int B = 28, N = 14, MUL_NQ = 1; static constexpr bool FQ2_INLINE = false, MUL_CHAIN = false; };
-// the scalar fields (NTT passes, kernels_ntt.cuh): both moduli are <= 255 bits
+template <> struct UCfg<Bls377Fq> { static constexpr int B = 28, N = 14, MUL_NQ = 1; static constexpr bool FQ2_INLINE = false, MUL_CHAIN = false; };
+// the scalar fields (NTT passes, kernels_ntt.cuh): all three moduli are <= 255 bits
 template <> struct UCfg<Bn254Fr> { static constexpr int B = 29, N = 9, MUL_NQ = ZK_MUL_NQ; static constexpr bool FQ2_INLINE = false, MUL_CHAIN = ZK_MUL_CHAIN != 0; };
 template <> struct UCfg<Bls381Fr> { static constexpr int B = 29, N = 9, MUL_NQ = ZK_MUL_NQ; static constexpr bool FQ2_INLINE = false, MUL_CHAIN = ZK_MUL_CHAIN != 0; };
+template <> struct UCfg<Bls377Fr> { static constexpr int B = 29, N = 9, MUL_NQ = ZK_MUL_NQ; static constexpr bool FQ2_INLINE = false, MUL_CHAIN = ZK_MUL_CHAIN != 0; };
 
 // ---- compile-time constants: p, -p^-1, powers of two mod p and bias multiples of p, all in B-bit limbs ----
 template <class P>
@@ -162,6 +165,11 @@ struct UConst {
     static constexpr u32 P_TOP = split(modulus()).v[N - 1];
     static constexpr u32 Q_MAGIC = (u32)(((u64)1 << 32) / ((u64)P_TOP + 1));   // floor(2^32 / (p_top + 1))
 };
+
+// BLS12-377: the base field has the room the loose quotient digits need (2^63.03 by LOOSE_OK's sum; its scalar field, like the other
+// two curves', has not, and the transforms' products keep their masks), and both top limbs serve fe_relax's quotient estimate
+static_assert(UConst<Bls377Fq>::LOOSE_OK && UConst<Bls381Fq>::LOOSE_OK && UConst<Bn254Fq>::LOOSE_OK, "base fields: columns with 32-bit quotient digits fit 64 bits");
+static_assert(UConst<Bls377Fq>::Q_MAGIC > 0 && UConst<Bls377Fr>::Q_MAGIC > 0 && UConst<Bls377Fq>::P_TOP > 0 && UConst<Bls377Fr>::P_TOP > 0, "BLS12-377: fe_relax's quotient estimate");
 
 template <class P>
 struct Fu {
@@ -503,7 +511,7 @@ template <int K, class P> ZK_HD Fe2<P> fe_sub_k(const Fe2<P>& a, const Fe2<P>& b
 template <class P> ZK_HD Fe2<P> fe_relax(const Fe2<P>& x) { return x; }
 template <class P> ZK_HD bool fe_is_zero_modp(const Fe2<P>& x) { return x.is_zero(); }
 
-// ---- Fq2 = Fq[u]/(u^2+1) over unsaturated limbs ----
+// ---- Fq2 = Fq[u]/(u^2 + BETA) over unsaturated limbs (P::BETA: 1 for BN254 and BLS12-381, 5 for BLS12-377) ----
 template <class P>
 struct Fu2 {
     typedef P Params;
@@ -535,7 +543,33 @@ template <class P> ZK_HD Fe<P> fe_cneg_for_mul(const Fe<P>& y, bool neg) { retur
 template <class P> ZK_HD Fe2<P> fe_cneg_for_mul(const Fe2<P>& y, bool neg) { return neg ? fe_neg(y) : y; }
 template <class P> ZK_HD Fe<P> fu_x3_numerator(const Fe<P>& rr, const Fe<P>& ppp, const Fe<P>& q) { return fe_sub(fe_sub(rr, ppp), fe_dbl(q)); }
 template <class P> ZK_HD Fe2<P> fu_x3_numerator(const Fe2<P>& rr, const Fe2<P>& ppp, const Fe2<P>& q) { return fe_sub(fe_sub(rr, ppp), fe_dbl(q)); }
-// (a0 + a1 u)(b0 + b1 u) = (a0 b0 - a1 b1) + (a0 b1 + a1 b0) u: two sums of two products, each reduced once
+// The non-residue BETA != 1 goes on a CARRIED OPERAND, never on the product columns: the operand that stands for -a1 b1 (or for
+// + c1 d1 in the fused Y3) is scaled limb by limb and given one parallel carry round, so what the products see is again TIGHT and
+// every column bound written for BETA = 1 holds unchanged — also the LOOSE one.  (Scaling the un-normalised 8p - b1 and multiplying
+// it at once would put a column at 14 * (2^28 + 8) * 15 * 2^28 + the other product's and the reduction's 2 * 14 * 2^56 = 2^63.8: inside
+// 64 bits with nothing to spare, and outside for 32-bit quotient digits.)  What is paid is the carry round: ~40 of the ~1 300
+// instructions of an Fq2 product.  Bounds, B = 28, N = 14, BETA = 5:
+//   limbs: nbias8_i - b1_i < 2^(B+1) + 2^B, times 5 < 15 * 2^28 < 2^32 (the static_assert below); a TIGHT d1_i <= 2^B + 8, times 5 < 2^31.
+//          After the carry round every limb but the top one is <= 2^B - 1 + 14 (the carry of 15 * 2^B - 1): TIGHT up to six units, which no bound notices.
+//   top limb: 5 * (top(8p) - 2 - b1_top) < 5 * 2^16; it wraps only where 8p - b1 does (ZK_LAZY_TOP_CHECK, as for BETA = 1).
+//   values: 5 (8p - b1) < 40p and 5 d1 < 40p against operands < 8p: a component is (64 + 320) p^2 / R' + p, the fused Y3's
+//          (64 + 320 + 64 + 320) p^2 / R' + p, and R' = 2^392 > 2^15 q: both stay below p + p / 42 < 2p.
+template <class P>
+ZK_HD Fu<P> fu_beta_neg8(const Fu<P>& b) {   // BETA * (8p - b), TIGHT, value < 8 BETA p; needs value(b) < 8p
+    static_assert(P::BETA * 3 <= (1u << (32 - Fu<P>::B)), "BETA * (spread bias - limb) fits 32 bits");
+    u32 t[Fu<P>::N];
+    ZK_LAZY_TOP_CHECK(P, UConst<P>::nbias8(Fu<P>::N - 1), b.v[Fu<P>::N - 1], "fu_beta_neg8");
+    ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) t[i] = P::BETA * (UConst<P>::nbias8(i) - b.v[i]);
+    return fu_norm<P>(t);
+}
+template <class P>
+ZK_HD Fu<P> fu_beta_times(const Fu<P>& a) {   // BETA * a, TIGHT in, TIGHT out
+    static_assert(P::BETA * 2 <= (1u << (32 - Fu<P>::B)), "BETA * limb fits 32 bits");
+    u32 t[Fu<P>::N];
+    ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) t[i] = P::BETA * a.v[i];
+    return fu_norm<P>(t);
+}
+// (a0 + a1 u)(b0 + b1 u) = (a0 b0 - BETA a1 b1) + (a0 b1 + a1 b0) u: two sums of two products, each reduced once
 // (the same 4 x N^2 + 2 x N^2 multiply-adds as Karatsuba's three full products, but one negation instead of five
 // additions, and results that stay below 2p whatever the operands)
 template <class P, bool LOOSE = false>
@@ -543,8 +577,12 @@ ZK_HD Fu2<P> fu2_mul_inl(const Fu2<P>& a, const Fu2<P>& b) {
     // 8p - b1 without its carry round (limbs < 2^(B+1) + 2^B): it is multiplied at once, in a column of two products whose other
     // operands are TIGHT — N (2^(2B) + 2^(2B+1.6)) + N 2^(2B) stays below 2^64 for both limb widths (ZK_CHECK_OVERFLOW builds check)
     Fu<P> nb1;
-    ZK_LAZY_TOP_CHECK(P, UConst<P>::nbias8(Fu<P>::N - 1), b.c1.v[Fu<P>::N - 1], "fu2_mul_inl");
-    ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) nb1.v[i] = UConst<P>::nbias8(i) - b.c1.v[i];
+    if constexpr (P::BETA == 1) {
+        ZK_LAZY_TOP_CHECK(P, UConst<P>::nbias8(Fu<P>::N - 1), b.c1.v[Fu<P>::N - 1], "fu2_mul_inl");
+        ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) nb1.v[i] = UConst<P>::nbias8(i) - b.c1.v[i];
+    } else {
+        nb1 = fu_beta_neg8(b.c1);   // BETA (8p - b1), carried: TIGHT (see above)
+    }
     return {fu_mul2_inl<P, LOOSE>(a.c0, b.c0, a.c1, nb1), fu_mul2_inl<P, LOOSE>(a.c0, b.c1, a.c1, b.c0)};
 }
 // (a0 + a1 u)^2 = (a0 + a1)(a0 - a1) + 2 a0 a1 u: two single products.  Operands < 6p keep (a0 + a1) < 12p and
@@ -554,6 +592,12 @@ ZK_HD Fu2<P> fu2_sqr_inl(const Fu2<P>& a) {
     // (the sum and the doubled limb are multiplied at once by a TIGHT operand: no carry round for them)
     Fu<P> d0;
     ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) d0.v[i] = a.c0.v[i] << 1;
+    if constexpr (P::BETA != 1) {
+        // c0 = a0^2 - BETA a1^2 as ONE two-product sum, a0 a0 + a1 (BETA (8p - a1)): three limb products for the square instead of
+        // two.  The complex form (a0 + a1)(a0 - BETA a1) + (BETA - 1) a0 a1 keeps two, but its c0 is a sum of two reduced values
+        // (< 10p), and every caller in ec.cuh counts on a square below 2p; here all operands are TIGHT and c0 < 2p as for BETA = 1.
+        return {fu_mul2_inl<P, LOOSE>(a.c0, a.c0, a.c1, fu_beta_neg8(a.c1)), LOOSE ? fu_mul_loose(d0, a.c1) : fu_mul_inl(d0, a.c1)};
+    }
     if (LOOSE) return {fu_mul_loose(fe_add_lazy(a.c0, a.c1), fe_sub_k<8>(a.c0, a.c1)), fu_mul_loose(d0, a.c1)};
     return {fu_mul_inl(fe_add_lazy(a.c0, a.c1), fe_sub_k<8>(a.c0, a.c1)), fu_mul_inl(d0, a.c1)};
 }
@@ -564,6 +608,8 @@ ZK_HD Fu2<P> fu2_sqr_inl(const Fu2<P>& a) {
 // Operands: TIGHT, a < 4p per component, b < 2p per component.
 template <class P>
 ZK_HD Fu2<P> fu2_mul_kara(const Fu2<P>& a, const Fu2<P>& b) {
+    // (BETA != 1: c0 wants BETA a1 (8p - b1) and c1 the unscaled a1 (8p - b1) — a fourth limb product, so the plain form serves)
+    if constexpr (P::BETA != 1) return fu2_mul_inl<P>(a, b);
     typedef UConst<P> C;
     constexpr int N = Fu<P>::N, B = Fu<P>::B;
     constexpr u32 M = Fu<P>::M;
@@ -612,7 +658,13 @@ ZK_HD Fu2<P> fu2_mul_kara(const Fu2<P>& a, const Fu2<P>& b) {
 template <class P, bool LOOSE = false>
 ZK_HD Fu2<P> fu2_mulsub_inl(const Fu2<P>& a, const Fu2<P>& b, const Fu2<P>& c, const Fu2<P>& d) {
     // c0 = a0 b0 - a1 b1 - c0 d0 + c1 d1;  c1 = a0 b1 + a1 b0 - c0 d1 - c1 d0      (negations as 8p - x)
-    const Fu<P> nb1 = fe_sub_k<8>(Fu<P>::zero(), b.c1), nd0 = fe_sub_k<8>(Fu<P>::zero(), d.c0), nd1 = fe_sub_k<8>(Fu<P>::zero(), d.c1);
+    const Fu<P> nd0 = fe_sub_k<8>(Fu<P>::zero(), d.c0), nd1 = fe_sub_k<8>(Fu<P>::zero(), d.c1);
+    if constexpr (P::BETA != 1) {
+        // c0 = a0 b0 - BETA a1 b1 - c0 d0 + BETA c1 d1: the two scaled operands carried (TIGHT, < 40p: bounds above fu_beta_neg8)
+        return {fu_mul4_inl<P, LOOSE>(a.c0, b.c0, a.c1, fu_beta_neg8(b.c1), c.c0, nd0, c.c1, fu_beta_times(d.c1)),
+                fu_mul4_inl<P, LOOSE>(a.c0, b.c1, a.c1, b.c0, c.c0, nd1, c.c1, nd0)};
+    }
+    const Fu<P> nb1 = fe_sub_k<8>(Fu<P>::zero(), b.c1);
     return {fu_mul4_inl<P, LOOSE>(a.c0, b.c0, a.c1, nb1, c.c0, nd0, c.c1, d.c1), fu_mul4_inl<P, LOOSE>(a.c0, b.c1, a.c1, b.c0, c.c0, nd1, c.c1, nd0)};
 }
 template <class P> ZK_HD_CALL Fu2<P> fu2_mul_call(const Fu2<P> a, const Fu2<P> b) { return fu2_mul_inl<P>(a, b); }
@@ -730,10 +782,12 @@ template <class P> struct FuUnpack<Fu2<P>> { ZK_HD static Fu2<P> get(const u32* 
 
 template <class P> ZK_HD Fu2<P> fu_from_fe(const Fe2<P>& a) { return {fu_from_fe(a.c0), fu_from_fe(a.c1)}; }
 template <class P> ZK_HD Fe2<P> fu_to_fe(const Fu2<P>& a) { return {fu_to_fe(a.c0), fu_to_fe(a.c1)}; }
-// 1 / (a0 + a1 u) = (a0 - a1 u) / (a0^2 + a1^2)
+// 1 / (a0 + a1 u) = (a0 - a1 u) / (a0^2 + BETA a1^2)
 template <class P>
 ZK_HD Fu2<P> ec_inv(const Fu2<P>& a) {
-    const Fu<P> n = fu_inv(fe_add(fu_sqr_inl(a.c0), fu_sqr_inl(a.c1)));
+    Fu<P> n;
+    if constexpr (P::BETA == 1) n = fu_inv(fe_add(fu_sqr_inl(a.c0), fu_sqr_inl(a.c1)));
+    else n = fu_inv(fu_mul2_inl<P>(a.c0, a.c0, a.c1, fu_beta_times(a.c1)));   // one two-product sum: < 2p
     return {fu_mul_inl(a.c0, n), fu_mul_inl(fe_sub_k<8>(Fu<P>::zero(), a.c1), n)};
 }
 

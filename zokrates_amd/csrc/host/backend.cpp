@@ -128,6 +128,14 @@ struct FrParams {
 };
 const FrParams FR_BN128 = {{0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}, 2};
 const FrParams FR_BLS12_381 = {{0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull}, 1};
+const FrParams FR_BLS12_377 = {{0x0a11800000000001ull, 0x59aa76fed0000001ull, 0x60b44d1e5c37b001ull, 0x12ab655e9a2ca556ull}, 3};
+const char* curve_name(int32_t curve) {
+    if (curve == ZKHIP_CURVE_BN128) return "bn128";
+    if (curve == ZKHIP_CURVE_BLS12_381) return "bls12_381";
+    if (curve == ZKHIP_CURVE_BLS12_377) return "bls12_377";
+    throw Error(ZKHIP_ERR_BAD_ARG, "unknown curve id");
+}
+bool known_curve(int32_t curve) { return curve == ZKHIP_CURVE_BN128 || curve == ZKHIP_CURVE_BLS12_381 || curve == ZKHIP_CURVE_BLS12_377; }
 bool lt(const uint64_t a[4], const uint64_t b[4]) {
     for (int i = 3; i >= 0; --i)
         if (a[i] != b[i]) return a[i] < b[i];
@@ -165,8 +173,8 @@ void from_mont(const uint64_t x[4], const FrParams& f, uint64_t out[4]) {
 }  // namespace
 
 std::array<uint8_t, 32> fr_rand(StdRng& rng, int32_t curve) {
-    if (curve != ZKHIP_CURVE_BN128 && curve != ZKHIP_CURVE_BLS12_381) throw Error(ZKHIP_ERR_BAD_ARG, "unknown curve id");
-    const FrParams& f = curve == ZKHIP_CURVE_BN128 ? FR_BN128 : FR_BLS12_381;
+    if (!known_curve(curve)) throw Error(ZKHIP_ERR_BAD_ARG, "unknown curve id");
+    const FrParams& f = curve == ZKHIP_CURVE_BN128 ? FR_BN128 : curve == ZKHIP_CURVE_BLS12_381 ? FR_BLS12_381 : FR_BLS12_377;   // (known_curve: one of the three)
     for (;;) {
         uint64_t limbs[4];
         for (int i = 0; i < 4; ++i) limbs[i] = rng.next_u64();
@@ -330,7 +338,7 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     if (raw[8 * fq + 2]) memcpy(&raw[7 * fq], one.data(), fq);
     Proof p;
     p.scheme = scheme == Scheme::GM17 ? "gm17" : "g16";
-    p.curve = curve == ZKHIP_CURVE_BN128 ? "bn128" : "bls12_381";
+    p.curve = curve_name(curve);
     p.proof.a = {hex_be(&raw[0], fq), hex_be(&raw[fq], fq)};
     p.proof.b.x = {hex_be(&raw[2 * fq], fq), hex_be(&raw[3 * fq], fq)};
     p.proof.b.y = {hex_be(&raw[4 * fq], fq), hex_be(&raw[5 * fq], fq)};
@@ -400,14 +408,14 @@ SetupKeypair Hip::setup(Scheme scheme, const Program& program, StdRng& rng) {
 // The verification key sits at the head of ark's proving key (ProvingKey { vk, .. }: serialize_unchecked writes it first):
 // g16: alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1[]; gm17: h_g2, g_alpha_g1, h_beta_g2, g_gamma_g1, h_gamma_g2, query[].
 std::string verification_key_json(Scheme scheme, int32_t curve, const uint8_t* pk, size_t len) {
-    if (curve != ZKHIP_CURVE_BN128 && curve != ZKHIP_CURVE_BLS12_381) throw Error(ZKHIP_ERR_BAD_ARG, "verification_key_json: unsupported curve");
+    if (!known_curve(curve)) throw Error(ZKHIP_ERR_BAD_ARG, "verification_key_json: unsupported curve");
     const size_t fq = curve == ZKHIP_CURVE_BN128 ? 32 : 48, g1 = 2 * fq, g2 = 4 * fq;
     const size_t fixed = scheme == Scheme::GM17 ? 2 * g1 + 3 * g2 : g1 + 3 * g2;
     if (!pk || len < fixed + 8) throw Error(ZKHIP_ERR_PARSE, "proving key too short for its verification key");
     uint64_t count;
     memcpy(&count, pk + fixed, 8);
     if (count > (len - fixed - 8) / g1) throw Error(ZKHIP_ERR_PARSE, "proving key too short for its verification key");
-    const std::string cname = curve == ZKHIP_CURVE_BN128 ? "bn128" : "bls12_381";
+    const std::string cname = curve_name(curve);
     std::string s = "{\n";
     if (scheme == Scheme::GM17) {      // (scheme/gm17.rs:19-27)
         size_t pos = 0;

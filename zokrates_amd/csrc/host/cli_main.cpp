@@ -246,9 +246,9 @@ int main(int argc, char** argv) {
             uint8_t head[12] = {0};
             if (!f || fread(head, 1, 12, f) != 12) { if (f) fclose(f); throw Error(ZKHIP_ERR_PARSE, "Invalid header"); }
             fclose(f);
-            static const uint8_t BN[4] = {0xb4, 0xf7, 0xb5, 0xbd}, BLS[4] = {0x40, 0xd8, 0xc1, 0xf9};
-            curve = !memcmp(head + 8, BN, 4) ? ZKHIP_CURVE_BN128 : !memcmp(head + 8, BLS, 4) ? ZKHIP_CURVE_BLS12_381 : -1;
-            if (memcmp(head, "ZOK\0", 4) != 0 || curve < 0) throw Error(ZKHIP_ERR_PARSE, "not a ZoKrates program for bn128 / bls12_381");
+            static const uint8_t BN[4] = {0xb4, 0xf7, 0xb5, 0xbd}, BLS[4] = {0x40, 0xd8, 0xc1, 0xf9}, BLS377[4] = {0xc2, 0x95, 0x5a, 0xb5};
+            curve = !memcmp(head + 8, BN, 4) ? ZKHIP_CURVE_BN128 : !memcmp(head + 8, BLS, 4) ? ZKHIP_CURVE_BLS12_381 : !memcmp(head + 8, BLS377, 4) ? ZKHIP_CURVE_BLS12_377 : -1;
+            if (memcmp(head, "ZOK\0", 4) != 0 || curve < 0) throw Error(ZKHIP_ERR_PARSE, "not a ZoKrates program for bn128 / bls12_381 / bls12_377");
         }
         // which bytes hold the key (the image of an earlier run, if --key-cache has one): mapped on a second thread while the
         // HIP runtime starts

@@ -29,32 +29,14 @@
 #include "../../../include/zkhip_backend.hpp"
 
 namespace zk {
-// BLS12-377 is not a curve libzkhip proves over; the verifier knows it so that it can be held against the reference's own GM17
-// artefacts, all of which are over this curve (zokrates_stdlib/tests/tests/snark/gm17.json and zokrates_core_test/tests/tests/
-// snark/snark_verify_bls12_377_{1,2,5}.json: proofs made by `zokrates generate-proof -b ark -s gm17`).  [UPSTREAM] ark-bls12-377
-// 0.3.0: q (377 bits), r (253 bits), y^2 = x^3 + 1, Fq2 = Fq[u]/(u^2 + 5), Fq6 = Fq2[v]/(v^3 - u), twist y^2 = x^3 + 1/u (type D),
-// x = 0x8508c00000000001.  Montgomery constants as field.cuh defines them (R = 2^384).
-struct Bls377Fr {
-    static constexpr int N = 8;
-    static constexpr int BITS = 253;
-    ZK_TABLE(mod, 8, 0x00000001u, 0x0a118000u, 0xd0000001u, 0x59aa76feu, 0x5c37b001u, 0x60b44d1eu, 0x9a2ca556u, 0x12ab655eu)
-};
-struct Bls377Fq {
-    static constexpr int N = 12;
-    static constexpr int BITS = 377;
-    static constexpr u32 INV = 0xffffffffu;
-    ZK_TABLE(mod, 12, 0x00000001u, 0x8508c000u, 0x30000000u, 0x170b5d44u, 0xba094800u, 0x1ef3622fu, 0x00f5138fu, 0x1a22d9f3u, 0x6ca1493bu,
-             0xc63b05c0u, 0x17c510eau, 0x01ae3a46u)
-    ZK_TABLE(r1, 12, 0xffffff68u, 0x02cdffffu, 0x7fffffb1u, 0x51409f83u, 0x8a7d3ff2u, 0x9f7db3a9u, 0x6e7c6305u, 0x7b4e97b7u, 0x803c84e8u,
-             0x4cf495bfu, 0xe2fdf49au, 0x008d6661u)
-    ZK_TABLE(r2, 12, 0x9400cd22u, 0xb786686cu, 0xb00431b1u, 0x0329fcaau, 0x62d6b46du, 0x22a5f111u, 0x827dc3acu, 0xbfdf7d03u, 0x41790bf9u,
-             0x837e92f0u, 0x1e914b88u, 0x006dfccbu)
-};
+// BLS12-377's parameter packs (Bls377Fr, Bls377Fq) live in field.cuh with the other curves'.  The reference's own GM17 artefacts are
+// all over this curve (zokrates_stdlib/tests/tests/snark/gm17.json and zokrates_core_test/tests/tests/snark/
+// snark_verify_bls12_377_{1,2,5}.json: proofs made by `zokrates generate-proof -b ark -s gm17`).  [UPSTREAM] ark-bls12-377 0.3.0:
+// y^2 = x^3 + 1, Fq2 = Fq[u]/(u^2 + 5), Fq6 = Fq2[v]/(v^3 - u), twist y^2 = x^3 + 1/u (type D), x = 0x8508c00000000001.
 
 // Fq2 = Fq[u] / (u^2 + BETA) for the verifier: BETA = 1 for BN254 and BLS12-381 (field.cuh's Fe2), 5 for BLS12-377.  With the
 // overloads below the group law of ec.cuh (Xyzz<F>) works over it unchanged.
-template <class P> struct QBeta { static constexpr u32 value = 1; };
-template <> struct QBeta<Bls377Fq> { static constexpr u32 value = 5; };
+template <class P> struct QBeta { static constexpr u32 value = P::BETA; };
 template <class P>
 struct Q2 {
     typedef P Params;

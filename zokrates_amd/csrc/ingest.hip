@@ -533,9 +533,16 @@ bool canonical32(const uint8_t* b) {
 }  // namespace
 
 // curve id = first 4 bytes of sha256(modulus, little-endian bytes) (/root/reference/zokrates_field/src/lib.rs:283-293);
-// bn128's value is pinned by /root/reference/zokrates_book/src/toolbox/ir.md:15 (b4f7b5bd), bls12_381's recomputed (40d8c1f9)
+// bn128's value is pinned by /root/reference/zokrates_book/src/toolbox/ir.md:15 (b4f7b5bd), bls12_381's (40d8c1f9) and bls12_377's (c2955ab5) recomputed
 static const uint8_t ID_BN128[4] = {0xb4, 0xf7, 0xb5, 0xbd};
 static const uint8_t ID_BLS12_381[4] = {0x40, 0xd8, 0xc1, 0xf9};
+static const uint8_t ID_BLS12_377[4] = {0xc2, 0x95, 0x5a, 0xb5};
+static const uint8_t* curve_file_id(int curve) {
+    if (curve == ZKHIP_CURVE_BN128) return ID_BN128;
+    if (curve == ZKHIP_CURVE_BLS12_381) return ID_BLS12_381;
+    if (curve == ZKHIP_CURVE_BLS12_377) return ID_BLS12_377;
+    fail(ZKHIP_ERR_BAD_ARG, "unknown curve id");
+}
 
 void prog_parse(const uint8_t* bytes, size_t len, zkhip_prog* out) {
     // ProgHeader::read (serialize.rs:150-199): magic, version, curve id, constraint count, return count, 4 x (type u32, offset u64, length u64)
@@ -546,7 +553,8 @@ void prog_parse(const uint8_t* bytes, size_t len, zkhip_prog* out) {
     if (memcmp(bytes + 4, VERSION, 4)) fail(ZKHIP_ERR_PARSE, "Invalid file version");
     if (!memcmp(bytes + 8, ID_BN128, 4)) out->curve = ZKHIP_CURVE_BN128;
     else if (!memcmp(bytes + 8, ID_BLS12_381, 4)) out->curve = ZKHIP_CURVE_BLS12_381;
-    else fail(ZKHIP_ERR_BAD_ARG, "Unknown curve identifier (this backend proves over bn128 and bls12_381)");
+    else if (!memcmp(bytes + 8, ID_BLS12_377, 4)) out->curve = ZKHIP_CURVE_BLS12_377;
+    else fail(ZKHIP_ERR_BAD_ARG, "Unknown curve identifier (this backend proves over bn128, bls12_381 and bls12_377)");
     const uint32_t constraint_count = rd32(bytes + 12);
     out->return_count = rd32(bytes + 16);
     uint64_t off[4], ln[4];
@@ -561,8 +569,11 @@ void prog_parse(const uint8_t* bytes, size_t len, zkhip_prog* out) {
     if (out->curve == ZKHIP_CURVE_BN128) {
         Builder<Bn254Fr> b;
         b.run(bytes, off[0], ln[0], off[1], ln[1], out);
-    } else {
+    } else if (out->curve == ZKHIP_CURVE_BLS12_381) {
         Builder<Bls381Fr> b;
+        b.run(bytes, off[0], ln[0], off[1], ln[1], out);
+    } else {
+        Builder<Bls377Fr> b;
         b.run(bytes, off[0], ln[0], off[1], ln[1], out);
     }
     if (out->n != constraint_count) fail(ZKHIP_ERR_PARSE, "constraint count in the header does not match the statements");
@@ -603,7 +614,7 @@ uint64_t prog_write(int curve, uint64_t n, uint64_t m, const uint64_t* const rp[
                     const int64_t* ids, const int64_t* arg_ids, const uint8_t* arg_private, uint64_t n_args, uint32_t return_count, uint8_t* out,
                     uint64_t cap) {
     constexpr uint64_t HEADER_REGION = 120;   // size_of::<ProgHeader>() on x86-64; the 100 bytes the header occupies lead it
-    if (curve != ZKHIP_CURVE_BN128 && curve != ZKHIP_CURVE_BLS12_381) fail(ZKHIP_ERR_BAD_ARG, "unknown curve id");
+    if (curve != ZKHIP_CURVE_BN128 && curve != ZKHIP_CURVE_BLS12_381 && curve != ZKHIP_CURVE_BLS12_377) fail(ZKHIP_ERR_BAD_ARG, "unknown curve id");
     if (n >= ((uint64_t)1 << 32)) fail(ZKHIP_ERR_BAD_ARG, "constraint count does not fit the header");
     if (cap < HEADER_REGION) fail(ZKHIP_ERR_BAD_ARG, "output buffer too small (see zkhip_prog_write_bound)");
     memset(out, 0, HEADER_REGION);
@@ -660,7 +671,7 @@ uint64_t prog_write(int curve, uint64_t n, uint64_t m, const uint64_t* const rp[
     uint8_t* h = out;
     static const uint8_t MAGIC_VERSION[8] = {0x5a, 0x4f, 0x4b, 0, 3, 0, 0, 0};
     memcpy(h, MAGIC_VERSION, 8);
-    memcpy(h + 8, curve == ZKHIP_CURVE_BN128 ? ID_BN128 : ID_BLS12_381, 4);
+    memcpy(h + 8, curve_file_id(curve), 4);
     const uint32_t cnt = (uint32_t)n;
     memcpy(h + 12, &cnt, 4);
     memcpy(h + 16, &return_count, 4);
@@ -684,7 +695,7 @@ void prog_assignment(const zkhip_prog* prog, const uint8_t* wit, size_t len, uin
         const uint8_t* ent = wit + 8 + 40 * i;
         int64_t id;
         memcpy(&id, ent, 8);
-        const bool ok = prog->curve == ZKHIP_CURVE_BN128 ? canonical32<Bn254Fr>(ent + 8) : canonical32<Bls381Fr>(ent + 8);
+        const bool ok = prog->curve == ZKHIP_CURVE_BN128 ? canonical32<Bn254Fr>(ent + 8) : prog->curve == ZKHIP_CURVE_BLS12_381 ? canonical32<Bls381Fr>(ent + 8) : canonical32<Bls377Fr>(ent + 8);
         if (!ok) fail(ZKHIP_ERR_PARSE, "non-canonical field element in the witness");
         std::vector<uint32_t>& v = id >= 0 ? pos : neg;
         const uint64_t k = id >= 0 ? (uint64_t)id : (uint64_t)(-(id + 1));

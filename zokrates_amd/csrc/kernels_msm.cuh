@@ -93,7 +93,10 @@ template <class P_> struct MsmTuning<Fu2<P_>> { static constexpr int ACCUM_WPE =
 #define ZK_BLS_G2_ZZ_LDS 0
 #endif
 template <> struct MsmTuning<Fu<Bls381Fq>> { static constexpr int ACCUM_WPE = ZK_BLS_G1_ACCUM_WPE, COLD_WPE = 3, FUSED_WPE = ZK_BLS_G1_FUSED_WPE, SLICE_WPE = ZK_BLS_G1_SLICE_WPE; static constexpr bool IS_EXT = false, PREFETCH_REGS = true, ZZ_IN_LDS = false, XY_IN_LDS = false; };
+// BLS12-377: the same limb plan (14 x 28 bits), so the BLS12-381 values are the starting point
+template <> struct MsmTuning<Fu<Bls377Fq>> : MsmTuning<Fu<Bls381Fq>> {};
 template <> struct MsmTuning<Fu2<Bls381Fq>> { static constexpr int ACCUM_WPE = ZK_BLS_G2_ACCUM_WPE, COLD_WPE = 1, FUSED_WPE = ZK_BLS_G2_SLICE_WPE, SLICE_WPE = ZK_BLS_G2_SLICE_WPE; static constexpr bool IS_EXT = true, PREFETCH_REGS = true, ZZ_IN_LDS = ZK_BLS_G2_ZZ_LDS != 0, XY_IN_LDS = false; };
+template <> struct MsmTuning<Fu2<Bls377Fq>> : MsmTuning<Fu2<Bls381Fq>> {};
 // dynamic LDS of one accumulation workgroup (256 work-items): the coordinates of the running sum that live there, word-major
 template <class F> constexpr size_t msm_accum_lds_bytes() { return (size_t)((MsmTuning<F>::ZZ_IN_LDS ? 2 : 0) + (MsmTuning<F>::XY_IN_LDS ? 2 : 0)) * (sizeof(F) / 4) * 256 * 4; }
 // the base tables of the MSMs one launch serves (A, B1 and L of a proof share the sort of the assignment)

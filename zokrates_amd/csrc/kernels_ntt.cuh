@@ -118,6 +118,39 @@ __global__ void k_field_op(const F* __restrict__ a, const F* __restrict__ b, F* 
     F x = a[i], y = b[i];
     out[i] = op == 0 ? fe_add(x, y) : op == 1 ? fe_sub(x, y) : fe_mul(x, y);
 }
+// The same over Fq2 (parity tests of the extension's arithmetic, whose non-residue differs between the curves).  UNSAT = false: the
+// saturated Fe2 of field.cuh; UNSAT = true: the unsaturated Fu2 of the MSM kernels, entered and left through fu_from_fe / fu_to_fe.
+// op: 0 add, 1 sub, 2 mul, 3 sqr, 4 inv (0 -> 0); UNSAT only: 5 mul and 6 sqr in their out-of-line forms (2 and 3 are the
+// accumulation kernel's inlined ones with loose quotient digits), 7 the fused x * y - x * x of the mixed addition's Y3; 8, 9, 10
+// the hot forms again at the upper end of the value range they are written for, on X = 3 x (< 6p, as Pp and R of a mixed addition)
+// and Y = 4 y (< 8p, the bound of the negated and the scaled operand): X * Y, X * X, X * Y - X * (4 x).
+template <class P, bool UNSAT>
+__global__ void k_field_op_fq2(const Fe2<P>* __restrict__ a, const Fe2<P>* __restrict__ b, Fe2<P>* __restrict__ out, u64 n, int op) {
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fe2<P> x = a[i], y = b[i];
+    if (!UNSAT) {
+        out[i] = op == 0 ? fe_add(x, y) : op == 1 ? fe_sub(x, y) : op == 2 ? fe_mul(x, y) : op == 3 ? fe_sqr(x) : fe_inv(x);
+        return;
+    }
+    const Fu2<P> ux = fu_from_fe(x), uy = fu_from_fe(y);
+    Fu2<P> r;
+    switch (op) {
+    case 0: r = fe_add(ux, uy); break;
+    case 1: r = fe_sub_k<2>(ux, uy); break;
+    case 2: r = fu2_mul_inl<P, true>(ux, uy); break;
+    case 3: r = fu2_sqr_inl<P, true>(ux); break;
+    case 4: r = ec_inv(ux); break;
+    case 5: r = fu2_mul_call(ux, uy); break;
+    case 6: r = fu2_sqr_call(ux); break;
+    case 7: r = fu2_mulsub_inl<P, true>(ux, uy, ux, ux); break;
+    default: {
+        const Fu2<P> X = fe_add(fe_dbl(ux), ux), Y = fe_dbl(fe_dbl(uy));      // TIGHT (a carry round each), < 6p and < 8p
+        r = op == 8 ? fu2_mul_inl<P, true>(X, Y) : op == 9 ? fu2_sqr_inl<P, true>(X) : fu2_mulsub_inl<P, true>(X, Y, X, fe_dbl(fe_dbl(ux)));
+    } break;
+    }
+    out[i] = fu_to_fe(r);
+}
 // out[i] = in[i] * tbl[i]
 template <class F>
 __global__ void k_mul_table(const F* __restrict__ in, const F* __restrict__ tbl, F* __restrict__ out, u64 n) {

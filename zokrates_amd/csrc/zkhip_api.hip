@@ -11,6 +11,7 @@
 static const CurveOps* ops_for(int curve) {
     if (curve == ZKHIP_CURVE_BN128) return curve_ops_bn254();
     if (curve == ZKHIP_CURVE_BLS12_381) return curve_ops_bls381();
+    if (curve == ZKHIP_CURVE_BLS12_377) return curve_ops_bls377();
     throw ApiError{ZKHIP_ERR_BAD_ARG, "unknown curve id"};
 }
 // errors of calls that have no context (zkhip_ctx_create, zkhip_prog_*): one message per calling thread
@@ -559,7 +560,7 @@ int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op,
                        uint8_t* out) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
     return guarded(ctx, [&] {
-        require(a && b && out && op >= 0 && op <= 2 && (field == 0 || field == 1), ZKHIP_ERR_BAD_ARG, "bad argument");
+        require(a && b && out && op >= 0 && field >= 0 && field <= 3 && op <= (field < 2 ? 2 : field == 2 ? 4 : 10), ZKHIP_ERR_BAD_ARG, "bad argument");
         ops_for(curve)->field_op(ctx, field, op, count, a, b, out);
     });
 }

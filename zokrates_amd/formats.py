@@ -14,12 +14,13 @@ import struct
 
 import numpy as np
 
-CURVE_NAMES = {0: "bn128", 1: "bls12_381"}
+CURVE_NAMES = {0: "bn128", 1: "bls12_381", 2: "bls12_377"}
 FR_MODULUS = {
     0: 21888242871839275222246405745257275088548364400416034343698204186575808495617,
     1: 52435875175126190479447740508185965837690552500527637822603658699938581184513,
+    2: 8444461749428370424248824938781546531375899335154063827935233455917409239041,
 }
-FQ_BYTES = {0: 32, 1: 48}
+FQ_BYTES = {0: 32, 1: 48, 2: 48}
 
 
 class FormatError(ValueError):

@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # emulator build to run its multi-rank plumbing on CPU); unset, the in-tree HIP library is the only candidate
 DEFAULT_LIB = os.environ.get("ZKHIP_LIBRARY") or os.path.join(HERE, "libzkhip.so")
 
-CURVE_IDS = {"bn128": 0, "bls12_381": 1}
-FQ_BYTES = {0: 32, 1: 48}
+CURVE_IDS = {"bn128": 0, "bls12_381": 1, "bls12_377": 2}
+FQ_BYTES = {0: 32, 1: 48, 2: 48}
 
 ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "PARSE", -3: "NOMEM", -4: "DEVICE", -5: "UNSATISFIED"}
 
@@ -249,10 +249,10 @@ class Context:
         return out.tobytes()
 
     def field_op(self, curve_id, field, op, a, b):
-        nb = 32 if field == 0 else FQ_BYTES[curve_id]
+        nb = 32 if field == 0 else FQ_BYTES[curve_id] * (2 if field >= 2 else 1)     # (fields 2, 3: Fq2 — include/zkhip.h)
         a = _u8(a); b = _u8(b, a.size)
         out = np.zeros(a.size, dtype=np.uint8)
-        code = {"add": 0, "sub": 1, "mul": 2}[op]
+        code = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "mul_call": 5, "sqr_call": 6, "mulsub": 7, "mul_wide": 8, "sqr_wide": 9, "mulsub_wide": 10}[op]
         self._check(self.lib.L.zkhip_field_op(self.h, curve_id, field, code, a.size // nb, _ptr(a), _ptr(b), _ptr(out)))
         return out
 

@@ -20,6 +20,7 @@ MASK32 = 0xFFFFFFFF
 FR = {
     0: (21888242871839275222246405745257275088548364400416034343698204186575808495617, 2),   # bn128: modulus, REPR_SHAVE_BITS
     1: (52435875175126190479447740508185965837690552500527637822603658699938581184513, 1),   # bls12_381
+    2: (8444461749428370424248824938781546531375899335154063827935233455917409239041, 3),    # bls12_377
 }
 
 

@@ -16,12 +16,13 @@ No oracle code is used here: tests feed these matrices to the oracle through its
 """
 import numpy as np
 
-CURVE_IDS = {"bn128": 0, "bls12_381": 1}
+CURVE_IDS = {"bn128": 0, "bls12_381": 1, "bls12_377": 2}
 FR_MODULUS = {
     0: 21888242871839275222246405745257275088548364400416034343698204186575808495617,
     1: 52435875175126190479447740508185965837690552500527637822603658699938581184513,
+    2: 8444461749428370424248824938781546531375899335154063827935233455917409239041,
 }
-FR_BITS = {0: 254, 1: 255}
+FR_BITS = {0: 254, 1: 255, 2: 253}
 
 _GAMMA = np.uint64(0x9E3779B97F4A7C15)
 _M1 = np.uint64(0xBF58476D1CE4E5B9)
