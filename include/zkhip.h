@@ -39,7 +39,9 @@ extern "C" {
 #define ZKHIP_ERR_PARSE (-2)        /* malformed proving key / non-canonical field element         */
 #define ZKHIP_ERR_NOMEM (-3)        /* host or device allocation failed                            */
 #define ZKHIP_ERR_DEVICE (-4)       /* no GPU, HIP runtime error, kernel launch failure            */
-#define ZKHIP_ERR_UNSATISFIED (-5)  /* assignment does not satisfy the R1CS (only when checked)    */
+#define ZKHIP_ERR_UNSATISFIED (-5)  /* the assignment does not satisfy the R1CS: zkhip_r1cs_check, and the single-GPU prove calls of a
+                                     * context in checked mode (zkhip_ctx_set_checked); also zkhip_prog_assignment for a variable
+                                     * the witness file gives no value                                                            */
 
 /* curve ids; names are zokrates_common::constants (/root/reference/zokrates_common/src/constants.rs:5-9) */
 #define ZKHIP_CURVE_BN128 0
@@ -224,6 +226,32 @@ int32_t zkhip_prove_g16_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1
 int32_t zkhip_prove_g16_resident_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, uint32_t count,
                                        zkhip_assignment* const* zs, const uint8_t* rs, uint8_t* proofs_out,
                                        zkhip_timings* timings);
+
+/* ---- checked proving ----
+ * A prove call turns ANY assignment into proof bytes: one that does not satisfy the system gives a proof that does not verify, and
+ * finding that out with the verifier costs a host pairing per proof.  The device holds Az, Bz and Cz before the first transform
+ * (over a key bound to the system: Az and Bz, and C's mat-vec is a third of the witness map's), so it can say so itself, and name
+ * the constraint — for a program read by zkhip_prog_parse the row is the statement number of the `out` file. */
+/* Az o Bz == Cz on the device.  z: host assignment (m x 32 B) or NULL to use z_resident.  ZKHIP_OK and
+ * *first_row = UINT64_MAX, *n_bad = 0 when every constraint holds; otherwise ZKHIP_ERR_UNSATISFIED, the lowest
+ * failing row and the number of failing rows (either pointer may be NULL).  Works for any key state and scheme:
+ * it needs no key. */
+int32_t zkhip_r1cs_check(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* z, zkhip_assignment* z_resident,
+                         uint64_t* first_row, uint64_t* n_bad);
+/* Checked mode of a context (default 0).  Returns the previous setting; on = -1 only reports.
+ * In checked mode zkhip_prove_g16, _resident, _batch, _resident_batch and zkhip_prove_gm17, _resident, _resident_batch test
+ * every proof's assignment on the device (one pointwise pass over the three row-product vectors; over a bound key C's mat-vec
+ * as well) with no further synchronisation.  If any fails, the call returns ZKHIP_ERR_UNSATISFIED, zkhip_last_error names the
+ * first failing proof and its constraint, the output slot of every failing proof is zero-filled, the slot of every other proof
+ * of the call holds the bytes the unchecked call writes, and the context stays usable.  With checked mode off nothing changes:
+ * the same launches, bytes and return codes as without this section.
+ * The multi-GPU entry points — zkhip_prove_*_partial, zkhip_prove_g16_split_*, zkhip_prove_*_multi* — IGNORE checked mode (the
+ * members of a zkhip_multi are created with it off): their callers use zkhip_r1cs_check. */
+int32_t zkhip_ctx_set_checked(zkhip_ctx* ctx, int32_t on);
+/* After a prove call that returned ZKHIP_ERR_UNSATISFIED: up to cap (proof index within the call, first failing
+ * row, failing rows) triples, in proof order; *count = how many proofs of the call failed. */
+int32_t zkhip_ctx_unsatisfied(const zkhip_ctx* ctx, uint32_t cap, uint32_t* proof_idx, uint64_t* first_row,
+                              uint64_t* n_bad, uint32_t* count);
 
 /* ---- one proof across several GPUs ----
  * Every MSM is a sum over independent (scalar, base) pairs, so rank k of `world` loads only its index range of

@@ -122,6 +122,9 @@ class Program {
     uint64_t constraints() const { return n_; }
     uint64_t variables() const { return l_ + w_; }
     zkhip_prog* get() const { return prog_; }
+    // the ZoKrates names ("~one", "_7", "~out_0": zkhip_prog_variable_order) of the variables in row `row` of A (0), B (1) or C (2),
+    // joined by " + " — what a failing constraint index (Hip::check) is worth to the author of the program
+    std::string row_variables(int32_t which, uint64_t row) const;
 
   private:
     zkhip_prog* prog_ = nullptr;
@@ -206,6 +209,13 @@ class Hip {
     // gamma, delta, tau; GM17: gamma = 1 as in ark-gm17), standard group generators (ark samples random ones from the RNG: a
     // key made here is valid, not byte-equal to `zokrates setup --entropy`'s), key generation on the GPU (zkhip_setup_*)
     SetupKeypair setup(Scheme scheme, const Program& program, StdRng& rng);
+    // Checked proving (zkhip.h "checked proving").  check: does the witness satisfy the system?  On the device, without a key
+    // (zkhip_r1cs_check); false fills *first_row (the statement number of the `out` file) and *n_bad where given.  set_checked:
+    // every prove of this object tests its assignment on the device and throws Error(ZKHIP_ERR_UNSATISFIED, "... constraint k ...")
+    // instead of returning a proof that cannot verify; off by default, returns the previous setting.
+    bool check(const System& system, const uint8_t* witness, size_t witness_len, uint64_t* first_row = nullptr, uint64_t* n_bad = nullptr);
+    bool set_checked(bool on);
+    bool checked() const;
     std::string describe() const;
 
   private:

@@ -7,6 +7,7 @@ use std::os::raw::c_char;
 #[repr(C)] pub struct zkhip_r1cs { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_multi { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_prog { _p: [u8; 0] }
+#[repr(C)] pub struct zkhip_assignment { _p: [u8; 0] }
 /// 16 floats: h2d, matvec, ntt, msm_h, msm_z, finish, total, accum_g1, accum_g2, kernel_ntt, 6 reserved (milliseconds)
 #[repr(C)] #[derive(Default, Clone, Copy)] pub struct zkhip_timings { pub ms: [f32; 16] }
 
@@ -51,6 +52,12 @@ extern "C" {
     pub fn zkhip_pk_bind_r1cs(ctx: *mut zkhip_ctx, pk: *mut zkhip_pk, r1cs: *const zkhip_r1cs) -> i32;
     pub fn zkhip_pk_unbind(pk: *mut zkhip_pk) -> i32;
     pub fn zkhip_pk_is_bound(pk: *const zkhip_pk, r1cs: *const zkhip_r1cs) -> i32;
+    // checked proving: Az o Bz == Cz on the device (needs no key), and the context's checked mode for the single-GPU prove calls
+    pub fn zkhip_r1cs_check(ctx: *mut zkhip_ctx, r1cs: *const zkhip_r1cs, z: *const u8, z_resident: *mut zkhip_assignment,
+        first_row: *mut u64, n_bad: *mut u64) -> i32;
+    pub fn zkhip_ctx_set_checked(ctx: *mut zkhip_ctx, on: i32) -> i32;
+    pub fn zkhip_ctx_unsatisfied(ctx: *const zkhip_ctx, cap: u32, proof_idx: *mut u32, first_row: *mut u64, n_bad: *mut u64,
+        count: *mut u32) -> i32;
     /// a shard of a multi-GPU key (or a whole key, Groth16 or GM17) bound from the key FILE: the transforms need every base once
     pub fn zkhip_pk_bind_r1cs_shard(ctx: *mut zkhip_ctx, pk: *mut zkhip_pk, r1cs: *const zkhip_r1cs, key_bytes: *const u8, len: usize) -> i32;
     // one proof across several GPUs of this process

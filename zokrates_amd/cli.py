@@ -177,6 +177,20 @@ def cmd_generate_proof(args):
             sys.exit("witness does not match the constraint system")
         inputs = [int.from_bytes(z[32 * i:32 * i + 32].tobytes(), "little") for i in range(1, cs.l)]
     lap("r1cs_upload_ms", t0)
+    if args.check:
+        # Az o Bz == Cz on the device before proving (zkhip_r1cs_check): a failing witness is refused with its first failing constraint
+        t0 = time.perf_counter()
+        row, bad = cs.check(z)
+        if bad:
+            msg = f"the witness does not satisfy the program: constraint {row} of {cs.n} is not satisfied ({bad} in all)"
+            if "prog" in host:       # the ZoKrates names of the variables of that statement's right-hand side
+                rp, col, _ = host["prog"].mats()[2]
+                ids = host["prog"].variable_order()
+                names = ["~one" if i == 0 else f"_{i - 1}" if i > 0 else f"~out_{-i - 1}" for i in (int(ids[c]) for c in col[int(rp[row]):int(rp[row + 1])])]
+                msg += "; its right-hand side is over " + (" + ".join(names) or "0")
+            sys.exit(msg)
+        lap("check_ms", t0)
+        print(f"checked: the witness satisfies all {cs.n} constraints")
     # the blinding scalars are drawn as the reference draws them: StdRng seeded from --entropy (rng.rs:5-20) or from the OS,
     # then `Fr::rand` twice (Groth16: r, s) or three times (GM17: d1, d2, r) — zokrates_amd/rng.py
     t0 = time.perf_counter()
@@ -235,6 +249,7 @@ def main(argv=None):
     g.add_argument("--timings", action="store_true", help="print the split of the wall clock as one JSON object")
     g.add_argument("--entropy")
     g.add_argument("--device", type=int, default=0)
+    g.add_argument("--check", action="store_true", help="test the witness against the constraints on the GPU first; refuse one that fails, naming the constraint")
     g.set_defaults(fn=cmd_generate_proof)
     args = ap.parse_args(argv)
     args.fn(args)

@@ -137,6 +137,8 @@ static constexpr int ZK_NSLOTS = 4;   // most proofs in flight (zkhip_prove_g16*
 // everything one proof in flight owns: its scalars, NTT vectors, sort results, MSM workspaces, window sums and events
 struct ProofSlot {
     DBuf scalars, zmont, va, vb, vc, ws1, ws2, zflag;   // zflag: one word, set by k_check_canonical when a host assignment is staged
+    DBuf verdict;             // checked mode: u64 lowest failing row (~0: none), u64 failing rows (k_r1cs_check)
+    int check_idx = -1;       // >= 0: the proof in flight is checked, and this is its index within the call (zkhip_ctx_set_checked)
     MsmSort sorts[3];         // over z (every table), over h, over z without the variables a family of tables holds at infinity (zkhip_pk::thin_mask)
     MsmLane lanes[ZK_NLANES];
     void* h_ws = nullptr;      // pinned host copy of the window sums
@@ -228,6 +230,9 @@ struct zkhip_ctx {
                               // histogram leaves LDS to the kernels beside it and reads the digits once more per halving)
     int tenants = 1;          // contexts of one zkhip_multi that share this context's device (their keys are sized for a share of its memory)
     int nslots = 3;           // proofs in flight in the batch calls (<= ZK_NSLOTS; measured 2 / 3 / 4: 72.0 / 76.0 / 74.8 proofs/s)
+    bool checked = false;     // zkhip_ctx_set_checked: the single-GPU prove calls test Az o Bz == Cz on the device and refuse a proof that fails
+    struct Unsatisfied { u32 proof; u64 first_row, n_bad; };
+    std::vector<Unsatisfied> unsat;   // the failing proofs of the last such call, in proof order (zkhip_ctx_unsatisfied)
     std::string err;
     std::string desc;
     ProofSlot slots[ZK_NSLOTS];
@@ -1546,7 +1551,9 @@ struct Prover {
     // `bound`: the key is bound to this system (PkLoader::bind) — the transforms that lead from the quotient's evaluations to h's
     // coefficients, and everything c needs, were applied to the key's bases once: what is left per proof is a and b to their
     // coefficients and on to the coset (FOUR transforms), and U_j = a_j b_j / Z(g) as canonical integers in NATURAL order in va.
-    static void witness_map(zkhip_ctx* ctx, const zkhip_r1cs* cs, NttPlan<C>* pl, bool bound = false, int half = -1) {
+    // `check` (checked mode): a b == c over the R1CS rows is tested where all three vectors exist and BEFORE the first transform,
+    // which works in place, is enqueued behind it on the same stream; over a bound key that means C's mat-vec as well.
+    static void witness_map(zkhip_ctx* ctx, const zkhip_r1cs* cs, NttPlan<C>* pl, bool bound = false, int half = -1, bool check = false) {
         Stream s = ctx->ws;
         const u64 N = pl->N;
         ctx->cur->va.ensure(3 * N * sizeof(Fr));
@@ -1562,7 +1569,8 @@ struct Prover {
             event_record(ctx->cur->ntt_e, s);
             return;
         }
-        matvec(ctx, cs, ptr<Fr>(ctx->cur->zmont), a, b, c, cs->n, cs->l, N, bound ? 2 : 3);
+        matvec(ctx, cs, ptr<Fr>(ctx->cur->zmont), a, b, c, cs->n, cs->l, N, (bound && !check) ? 2 : 3);
+        if (check) enqueue_check(*ctx->cur, a, b, c, cs->n, s);
         event_record(ctx->cur->ntt_b, s);
         if (bound) {
             ntt_kind_a<C>(ctx, pl, a, true, ptr<Fr>(pl->s_coset), 2, N);    // a, b: ifft, then * g^i
@@ -1582,6 +1590,67 @@ struct Prover {
         ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, s, a, b, pl->zinv_rp, a, N);
         ntt_kind_a<C>(ctx, pl, a, true, ptr<Fr>(pl->s_cosetinv_canon), 1, 0, 1, c);   // coset_ifft, canonical, minus c's share
         event_record(ctx->cur->ntt_e, s);
+    }
+
+    // ---- checked mode (zkhip_ctx_set_checked).  The slot's verdict is reset where its zflag word is, tested by k_r1cs_check on the
+    // stream that owns the three row-product vectors, travels in the slot's pinned record behind the zflag word (copy_out) and is
+    // read where that word is read (unsatisfied): no synchronisation of its own.
+    static void verdict_reset(ProofSlot& sl, Stream st) {
+        sl.verdict.ensure(16);
+        dev_memset(sl.verdict.p, 0xff, 8, st);
+        dev_memset((uint8_t*)sl.verdict.p + 8, 0, 8, st);
+    }
+    static void enqueue_check(ProofSlot& sl, const Fr* a, const Fr* b, const Fr* c, u64 n, Stream s) {
+        ZK_LAUNCH((k_r1cs_check<typename Fr::Params>), dim3(blocks_for(n, 256)), dim3(256), 0, s, a, b, c, n, ptr<unsigned long long>(sl.verdict));
+    }
+    // the slot's finished proof failed its check: noted in the context (`record`: the pinned record at its zflag word)
+    static bool unsatisfied(zkhip_ctx* ctx, const ProofSlot& sl, const uint8_t* record) {
+        if (sl.check_idx < 0) return false;
+        u64 v[2];
+        memcpy(v, record + 8, 16);
+        if (!v[1]) return false;
+        ctx->unsat.push_back({(u32)sl.check_idx, v[0], v[1]});
+        return true;
+    }
+    // the end of a checked prove call of `count` proofs over `cs`: ZKHIP_ERR_UNSATISFIED naming the first proof that failed
+    static void raise_unsatisfied(const zkhip_ctx* ctx, u32 count, const zkhip_r1cs* cs) {
+        if (ctx->unsat.empty()) return;
+        const auto& u = ctx->unsat.front();
+        char msg[200];
+        snprintf(msg, sizeof(msg), "proof %u of %u: constraint %llu of %llu is not satisfied (%llu in all)", u.proof, count, (unsigned long long)u.first_row,
+                 (unsigned long long)cs->n, (unsigned long long)u.n_bad);
+        throw ApiError{ZKHIP_ERR_UNSATISFIED, msg};
+    }
+    // canonical integer -> R'-form factor (NttPlan::k_to_rp) without a plan: the stand-alone check transforms nothing
+    static Fr k_to_rp() {
+        Fr rp = Fr::one();
+        for (int i = 32 * Fr::N; i < Fu<typename Fr::Params>::B * Fu<typename Fr::Params>::N; ++i) rp = fe_add(rp, rp);
+        return fe_to_mont(rp);
+    }
+    // zkhip_r1cs_check: the three mat-vecs over rows [0, n) and the test, nothing else; out = {lowest failing row or ~0, failing rows}
+    static void r1cs_check(zkhip_ctx* ctx, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, u64 out[2]) {
+        ProofSlot& sl = *ctx->cur;
+        Stream s = ctx->stream;
+        ctx->ws = s;
+        const u64 m = cs->l + cs->w, n = cs->n;
+        if (z_host) {
+            upload_z(ctx, sl.scalars, m, z_host, sl.zflag);
+        } else {
+            sl.zflag.ensure(4);
+            dev_memset(sl.zflag.p, 0, 4, s);      // a resident assignment was checked when it was uploaded
+        }
+        sl.zmont.ensure(m * 32);
+        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, s, (const Fr*)(z_host ? sl.scalars.p : z_dev), ptr<Fr>(sl.zmont), m, k_to_rp());
+        sl.vc.ensure(3 * std::max<u64>(n, 1) * sizeof(Fr));
+        Fr *ra = ptr<Fr>(sl.vc), *rb = ra + n, *rc = rb + n;
+        verdict_reset(sl, s);
+        if (n) matvec(ctx, cs, ptr<Fr>(sl.zmont), ra, rb, rc, n, 0, n);
+        enqueue_check(sl, ra, rb, rc, n, s);
+        u32 flag = 0;
+        dev_d2h(&flag, sl.zflag.p, 4, s);
+        dev_d2h(out, sl.verdict.p, 16, s);
+        stream_sync(s);
+        require_canonical(flag);
     }
 
     // z -> HBM (canonical integers; slots m, m+1 are reserved for r, s)
@@ -1613,8 +1682,8 @@ struct Prover {
     // src_dev != nullptr: the assignment is already in HBM (copied device-to-device into the slot); else z is a host buffer
     // `lone`: nothing else of this context is in flight beside this proof (the single-proof entry points; a batch pipelines)
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* src_dev,
-                        const uint8_t* r, const uint8_t* s_, bool lone = false) {
-        enqueue_head(ctx, sl, pk, cs, z_host, src_dev, r, s_, lone, -1);
+                        const uint8_t* r, const uint8_t* s_, bool lone = false, int check_idx = -1) {
+        enqueue_head(ctx, sl, pk, cs, z_host, src_dev, r, s_, lone, -1, check_idx);
         enqueue_tail(ctx, sl, pk, cs);
     }
     // whether a proof over (pk, cs) may be split between members: a bound key (its proof needs a and b on the coset and nothing else
@@ -1626,7 +1695,7 @@ struct Prover {
     // (0: a, 1: b) of a bound key's, after which sl.half_ready is recorded and the caller brings the other vector into
     // sl.va + (1 - half) * N before enqueue_tail
     static void enqueue_head(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* src_dev,
-                             const uint8_t* r, const uint8_t* s_, bool lone, int half) {
+                             const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1) {
         require(pk->curve == C::ID && cs->curve == C::ID, ZKHIP_ERR_BAD_ARG, "curve mismatch between key and constraint system");
         require(pk->scheme == 0, ZKHIP_ERR_BAD_ARG, "this is a GM17 proving key: use zkhip_prove_gm17");
         require(pk->m == cs->l + cs->w && pk->w == cs->w && pk->N == cs->N, ZKHIP_ERR_BAD_ARG,
@@ -1639,6 +1708,7 @@ struct Prover {
         require(half < 0 || (bound && half <= 1), ZKHIP_ERR_BAD_ARG, "internal: only a proof over a bound key splits its witness map");
         sl.half = half;
         sl.lone = lone;
+        sl.check_idx = half < 0 ? check_idx : -1;
         Fr rr = fe_from_bytes_canon<Fr>(r), ss = fe_from_bytes_canon<Fr>(s_);
         require(canon_lt_mod(rr) && canon_lt_mod(ss), ZKHIP_ERR_BAD_ARG, "r or s not a canonical field element");
         NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
@@ -1657,6 +1727,7 @@ struct Prover {
             sl.zflag.ensure(4);
             dev_memset(sl.zflag.p, 0, 4, st);      // a resident assignment was checked when it was uploaded
         }
+        if (sl.check_idx >= 0) verdict_reset(sl, st);
         void* d_scalars = sl.scalars.p;
         stage_scalars(ctx, pl, d_scalars, m, r, s_);
         event_record(sl.ev[0], st);
@@ -1703,7 +1774,7 @@ struct Prover {
         if ((lone_sched & 4) && pk->z_n) stream_wait_event(wn, sl.sorts[0].ready);
         event_record(sl.ev[1], wn);
         ctx->ws = wn;
-        witness_map(ctx, cs, pl, bound, half);
+        witness_map(ctx, cs, pl, bound, half, sl.check_idx >= 0);
         ctx->ws = ctx->stream;
         if (half >= 0) event_record(sl.half_ready, wn);
     }
@@ -1815,15 +1886,23 @@ struct Prover {
         }
     }
 
-    // the slot's pinned host copy of the window sums (4 G1 MSMs, the G2 MSM, the verdict word of the canonical check)
+    // the slot's pinned host copy of the window sums (4 G1 MSMs, the G2 MSM, the verdict word of the canonical check and, 8 bytes
+    // on, the 16-byte verdict of checked mode)
     static void host_sums(ProofSlot& sl, int Wmax) {
         const size_t b1 = (size_t)4 * Wmax * sizeof(Xyzz<Fq>), b2 = (size_t)Wmax * sizeof(Xyzz<Fq2>);
-        if (sl.h_ws_cap < b1 + b2 + 4) {
+        if (sl.h_ws_cap < b1 + b2 + 24) {
             host_free_pinned(sl.h_ws);
             sl.h_ws = nullptr; sl.h_ws_cap = 0;
-            sl.h_ws = host_alloc_pinned(b1 + b2 + 4);
-            sl.h_ws_cap = b1 + b2 + 4;
+            sl.h_ws = host_alloc_pinned(b1 + b2 + 24);
+            sl.h_ws_cap = b1 + b2 + 24;
         }
+    }
+    // where that record's zflag word is
+    static const uint8_t* host_record(const zkhip_ctx* ctx, const ProofSlot& sl, const zkhip_pk* pk) {
+        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
+        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
+        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
+        return (const uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>) + (size_t)Wmax * sizeof(Xyzz<Fq2>);
     }
     // ---- the end of a proof's device work: every lane has copied its window sums out behind its fold (msm_run_tables) and recorded
     // `done`; a stream of its own — the main stream is free for the next proof — waits for all of them, fetches the verdict of the
@@ -1835,6 +1914,10 @@ struct Prover {
         const size_t b1 = (size_t)4 * Wmax * sizeof(Xyzz<Fq>), b2 = (size_t)Wmax * sizeof(Xyzz<Fq2>);
         sl.zflag.ensure(4);
         dev_d2h_pinned((uint8_t*)sl.h_ws + b1 + b2, sl.zflag.p, 4, so);   // written on the main stream before ev[0], which every lane waits for
+        if (sl.check_idx >= 0) {
+            stream_wait_event(so, sl.ev[2]);      // "h ready": recorded behind the check on the stream of the witness map
+            dev_d2h_pinned((uint8_t*)sl.h_ws + b1 + b2 + 8, sl.verdict.p, 16, so);
+        }
         event_record(sl.ev[3], so);
         sl.busy = true;
     }
@@ -1980,7 +2063,8 @@ struct Prover {
         u32 zflag;
         memcpy(&zflag, (const uint8_t*)(h_ws2 + Wmax), 4);
         require_canonical(zflag);
-        assemble_tail(g, sA, rB1, rsD, out);
+        if (unsatisfied(ctx, sl, (const uint8_t*)(h_ws2 + Wmax))) memset(out, 0, 8 * FQB + 3);      // a refused proof: all zero
+        else assemble_tail(g, sA, rB1, rsD, out);
         fill_timings(sl, tm, t_fin);
     }
     static Xyzz<Fq> rs_delta(const zkhip_pk* pk, const Fr& rr, const Fr& ss) {
@@ -2136,13 +2220,17 @@ struct Prover {
     // one proof from a host assignment / from an assignment resident in HBM
     static void prove_host(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z, const uint8_t* r, const uint8_t* s_,
                            uint8_t* out, zkhip_timings* tm) {
-        enqueue(ctx, ctx->slots[0], pk, cs, z, nullptr, r, s_, true);
+        ctx->unsat.clear();
+        enqueue(ctx, ctx->slots[0], pk, cs, z, nullptr, r, s_, true, ctx->checked ? 0 : -1);
         finish(ctx, ctx->slots[0], pk, out, tm);
+        raise_unsatisfied(ctx, 1, cs);
     }
     static void prove_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, void* d_scalars, const uint8_t* r, const uint8_t* s_,
                                uint8_t* out, zkhip_timings* tm) {
-        enqueue(ctx, ctx->slots[0], pk, cs, nullptr, d_scalars, r, s_, true);
+        ctx->unsat.clear();
+        enqueue(ctx, ctx->slots[0], pk, cs, nullptr, d_scalars, r, s_, true, ctx->checked ? 0 : -1);
         finish(ctx, ctx->slots[0], pk, out, tm);
+        raise_unsatisfied(ctx, 1, cs);
     }
     // `count` proofs, two in flight: while the GPU works on proof i the host finishes proof i-1 and enqueues proof i+1,
     // so the latency-bound tail of one proof (the H fold) overlaps the MSMs of the next.
@@ -2153,12 +2241,13 @@ struct Prover {
         zkhip_timings acc, one;
         memset(&acc, 0, sizeof(acc));
         const auto t0 = std::chrono::steady_clock::now();
+        ctx->unsat.clear();
         try {
             const u32 NS = (u32)ctx->nslots;   // proofs in flight
             for (u32 i = 0; i < count + NS - 1; ++i) {
                 if (i < count)
                     enqueue(ctx, ctx->slots[i % NS], pk, cs, z_host ? z_host + (size_t)i * pk->m * 32 : nullptr, z_host ? nullptr : z_dev[i],
-                            rs + (size_t)i * 64, rs + (size_t)i * 64 + 32);
+                            rs + (size_t)i * 64, rs + (size_t)i * 64 + 32, false, ctx->checked ? (int)i : -1);
                 if (i >= NS - 1 && i - (NS - 1) < count) {
                     const u32 j = i - (NS - 1);
                     finish(ctx, ctx->slots[j % NS], pk, proofs_out + (size_t)j * proof_bytes, &one);
@@ -2175,6 +2264,7 @@ struct Prover {
             *tm = acc;
             tm->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
+        raise_unsatisfied(ctx, count, cs);
     }
     static void assignment_upload(zkhip_ctx* ctx, zkhip_assignment* a, const uint8_t* z) {
         DBuf flag;
@@ -2391,6 +2481,7 @@ struct CurveOps {
                                    size_t*, zkhip_timings*);
     void (*record_from_sums)(zkhip_ctx*, const zkhip_pk*, const uint8_t*, const uint8_t*, uint8_t*);
     void (*assignment_upload)(zkhip_ctx*, zkhip_assignment*, const uint8_t*);
+    void (*r1cs_check)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const void*, u64 out[2]);
     void (*ntt)(zkhip_ctx*, u32, int, uint8_t*);
     void (*witness_map)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, uint8_t*);
     void (*msm_g1)(zkhip_ctx*, u64, const uint8_t*, const uint8_t*, uint8_t*);
@@ -2457,6 +2548,7 @@ static CurveOps make_curve_ops() {
     o.gm17_prove_device_sums = &Gm17<C>::prove_device_sums;
     o.record_from_sums = &Prover<C>::record_from_sums;
     o.assignment_upload = &Prover<C>::assignment_upload;
+    o.r1cs_check = &Prover<C>::r1cs_check;
     o.ntt = &Prover<C>::ntt_api;
     o.witness_map = &Prover<C>::witness_map_api;
     o.msm_g1 = &Prover<C>::template msm_api<typename C::Fq, 2>;

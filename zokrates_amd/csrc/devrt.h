@@ -489,6 +489,8 @@ inline bool grid_nonempty(const dim3& g) { return g.x != 0 && g.y != 0 && g.z !=
 // true if the predicate holds in ANY active lane of the wavefront: a wave-uniform condition (a scalar branch, no exec masking —
 // both sides of an `if` on it are ordinary control flow whose results meet without per-lane copies)
 #define ZK_WAVE_ANY(pred) (__builtin_amdgcn_ballot_w64(pred) != 0)
+// the 64-bit mask of the lanes of the wavefront in which the predicate holds (every lane of the wave must reach it)
+#define ZK_WAVE_BALLOT(pred) ((unsigned long long)__builtin_amdgcn_ballot_w64(pred))
 // -DZK_CHECKED: a debugging build whose kernels check every index they compute from data another kernel produced (sorted
 // entries, bucket offsets, partial slots, matrix columns) and trap instead of touching memory outside their buffers; with
 // ZKHIP_TRACE=1 (synchronise after every launch) the launch that trapped is the last one named on stderr.
@@ -547,6 +549,7 @@ inline JitterState& jitter_state() { static JitterState st; return st; }
 #define ZK_DYN_SMEM(name) unsigned char* name = emu::dyn_smem()
 #define ZK_PRIO_HIGH() ((void)0)
 #define ZK_WAVE_ANY(pred) (pred)      /* (the fibres of the emulator decide one by one: both sides compute the same result) */
+#define ZK_WAVE_BALLOT(pred) emu::wave_ballot(pred)
 #ifdef ZK_CHECKED
 #define ZK_ASSERT_IDX(cond) do { if (!(cond)) { fprintf(stderr, "ZK_ASSERT_IDX failed: %s (%s:%d)\n", #cond, __FILE__, __LINE__); abort(); } } while (0)
 #else

@@ -181,11 +181,12 @@ struct Gm17 {
     }
     // every kernel and copy of one proof, no host synchronisation (the slot discipline of Prover<C>::enqueue)
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* src_dev,
-                        const uint8_t* d1, const uint8_t* r) {
+                        const uint8_t* d1, const uint8_t* r, int check_idx = -1) {
         check_match(pk, cs);
         require(!sl.busy, ZKHIP_ERR_DEVICE, "internal: proof slot still in flight");
         make_pipe_streams(ctx);
         slot_init(ctx, sl);
+        sl.check_idx = check_idx;      // (checked mode, Prover<C>::enqueue_check: the test is on the R1CS rows, not on the SAP's)
         const u64 m = cs->l + cs->w, n = cs->n, l = cs->l, M = pk->m, D = pk->N;
         Fr dd = fe_from_bytes_canon<Fr>(d1), rr = fe_from_bytes_canon<Fr>(r);
         require(canon_lt_mod(dd) && canon_lt_mod(rr), ZKHIP_ERR_BAD_ARG, "d1 or r not a canonical field element");
@@ -213,6 +214,7 @@ struct Gm17 {
             sl.zflag.ensure(4);
             dev_memset(sl.zflag.p, 0, 4, st);
         }
+        if (check_idx >= 0) P::verdict_reset(sl, st);
         uint8_t* d_scalars = (uint8_t*)sl.scalars.p;
         sl.zmont.ensure(m * 32);
         dev_h2d(d_scalars + M * 32, sl.r, 32, st);
@@ -230,7 +232,9 @@ struct Gm17 {
         }
         sl.vc.ensure(3 * std::max<u64>(n, 1) * sizeof(Fr));      // the three row-product vectors
         Fr *ra = ptr<Fr>(sl.vc), *rb = ra + n, *rc = rb + n;
-        if (n) P::matvec(ctx, cs, ptr<Fr>(sl.zmont), ra, rb, rc, n, 0, n, bound ? 2 : 3);
+        // (checked mode over a bound key: C's rows as well, for the check alone — the SAP rows below still leave W to the bases)
+        if (n) P::matvec(ctx, cs, ptr<Fr>(sl.zmont), ra, rb, rc, n, 0, n, (bound && check_idx < 0) ? 2 : 3);
+        if (check_idx >= 0) P::enqueue_check(sl, ra, rb, rc, n, st);
         ZK_LAUNCH((k_sap_rows<typename Fr::Params>), dim3(blocks_for(n + l, 256)), dim3(256), 0, st, ra, rb, rc, ptr<Fr>(sl.zmont), sa, bound ? (Fr*)nullptr : sc,
                   (Fr*)d_scalars, n, l, m);
         event_record(sl.ev[1], st);
@@ -311,7 +315,8 @@ struct Gm17 {
         const auto t_fin = std::chrono::steady_clock::now();
         Fr rho;
         memcpy(rho.v, sl.r, 32);
-        assemble(pk, g, rho, out);
+        if (P::unsatisfied(ctx, sl, P::host_record(ctx, sl, pk))) memset(out, 0, 8 * FQB + 3);      // a refused proof: all zero
+        else assemble(pk, g, rho, out);
         P::fill_timings(sl, tm, t_fin);
     }
     static void assemble(const zkhip_pk* pk, const typename P::Sums& g, const Fr& rho, uint8_t* out) {
@@ -383,8 +388,10 @@ struct Gm17 {
     static void prove(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const uint8_t* rnd,
                       uint8_t* out, zkhip_timings* tm) {
         check_d2(rnd);
-        enqueue(ctx, ctx->slots[0], pk, cs, z_host, z_dev, rnd, rnd + 64);
+        ctx->unsat.clear();
+        enqueue(ctx, ctx->slots[0], pk, cs, z_host, z_dev, rnd, rnd + 64, ctx->checked ? 0 : -1);
         finish(ctx, ctx->slots[0], pk, out, tm);
+        P::raise_unsatisfied(ctx, 1, cs);
     }
     // `count` proofs, ZK_NSLOTS in flight (see Prover<C>::prove_batch); rnd: count x 96 B
     static void prove_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 count, const uint8_t* z_host, void* const* z_dev,
@@ -394,13 +401,14 @@ struct Gm17 {
         zkhip_timings acc, one;
         memset(&acc, 0, sizeof(acc));
         const auto t0 = std::chrono::steady_clock::now();
+        ctx->unsat.clear();
         try {
             const u32 NS = (u32)ctx->nslots;   // proofs in flight
             for (u32 i = 0; i < count + NS - 1; ++i) {
                 if (i < count) {
                     check_d2(rnd + (size_t)i * 96);
                     enqueue(ctx, ctx->slots[i % NS], pk, cs, z_host ? z_host + (size_t)i * m * 32 : nullptr, z_host ? nullptr : z_dev[i],
-                            rnd + (size_t)i * 96, rnd + (size_t)i * 96 + 64);
+                            rnd + (size_t)i * 96, rnd + (size_t)i * 96 + 64, ctx->checked ? (int)i : -1);
                 }
                 if (i >= NS - 1 && i - (NS - 1) < count) {
                     const u32 j = i - (NS - 1);
@@ -418,6 +426,7 @@ struct Gm17 {
             *tm = acc;
             tm->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
+        P::raise_unsatisfied(ctx, count, cs);
     }
 
     // ------------------------------------------------------------ setup

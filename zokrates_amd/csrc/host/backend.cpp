@@ -206,6 +206,20 @@ Program::Program(const uint8_t* bytes, size_t len) {
     curve_ = (int32_t)d[0]; n_ = d[1]; l_ = d[2]; w_ = d[3];
 }
 Program::~Program() { if (prog_) zkhip_prog_free(prog_); }
+std::string Program::row_variables(int32_t which, uint64_t row) const {
+    const uint64_t* rp = nullptr;
+    const uint32_t* col = nullptr;
+    const uint8_t* val = nullptr;
+    const int64_t* ids = nullptr;
+    if (row >= n_ || zkhip_prog_matrix(prog_, which, &rp, &col, &val) != ZKHIP_OK || zkhip_prog_variable_order(prog_, &ids) != ZKHIP_OK) return "";
+    std::string s;
+    for (uint64_t q = rp[row]; q < rp[row + 1]; ++q) {
+        const int64_t id = ids[col[q]];
+        if (!s.empty()) s += " + ";
+        s += id == 0 ? std::string("~one") : id > 0 ? "_" + std::to_string(id - 1) : "~out_" + std::to_string(-id - 1);
+    }
+    return s.empty() ? "0" : s;
+}
 
 Hip::Hip(int32_t device) {
     const int32_t rc = zkhip_ctx_create(device, &ctx_);
@@ -290,6 +304,17 @@ bool Hip::bind(Key& key, const System& system) {
     return true;
 }
 bool Hip::is_bound(const Key& key, const System& system) const { return zkhip_pk_is_bound(key.get(), system.get()) == 1; }
+bool Hip::set_checked(bool on) { return zkhip_ctx_set_checked(ctx_, on ? 1 : 0) == 1; }
+bool Hip::checked() const { return zkhip_ctx_set_checked(ctx_, -1) == 1; }
+bool Hip::check(const System& system, const uint8_t* witness, size_t witness_len, uint64_t* first_row, uint64_t* n_bad) {
+    const Program& program = system.program();
+    std::vector<uint8_t> z(program.variables() * 32);
+    int32_t rc = zkhip_prog_assignment(program.get(), witness, witness_len, z.data(), nullptr, 0, nullptr);
+    if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
+    rc = zkhip_r1cs_check(ctx_, system.get(), z.data(), nullptr, first_row, n_bad);
+    if (rc != ZKHIP_ERR_UNSATISFIED) check(rc);
+    return rc == ZKHIP_OK;
+}
 
 Proof Hip::prove(Scheme scheme, const Program& program, const uint8_t* witness, size_t witness_len, const Key& key, StdRng& rng, Timings* tm) {
     // the constraint system on the device, for this one proof

@@ -1,7 +1,7 @@
 // zkhip-cli — `zokrates generate-proof` for the hip backend, as a native executable over zkhip_backend.hpp.
 //
 //   zkhip-cli generate-proof -i out -w witness -p proving.key -j proof.json [-s g16|gm17] [--entropy TEXT]
-//                            [--key-cache DIR] [--device N] [--timings] [--verify]
+//                            [--key-cache DIR] [--device N] [--timings] [--verify] [--check]
 //
 // Mirrors /root/reference/zokrates_cli/src/ops/generate_proof.rs:95-202: the compiled program (`out`), the witness and the
 // proving key are read from files, the proof is written as JSON, one proof per process; `--entropy` seeds the RNG as
@@ -70,7 +70,7 @@ std::pair<int, int> cpu_and_node() {
 }
 int usage() {
     fprintf(stderr, "usage: zkhip-cli generate-proof -i <out> -w <witness> -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] "
-                    "[--key-cache DIR] [--device N] [--timings] [--verify] [--full-tables]\n"
+                    "[--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--full-tables]\n"
                     "       zkhip-cli setup -i <out> -p <proving.key> -v <verification.key> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
                     "       zkhip-cli verify [-v <verification.key>] [-j <proof.json>]\n"
                     "       zkhip-cli print-proof [-j <proof.json>] [-f remix|json]\n");
@@ -192,13 +192,14 @@ int main(int argc, char** argv) {
     if (argc >= 2 && strcmp(argv[1], "pairing-check") == 0) return cmd_pairing_check(argc, argv);
     if (argc < 2 || strcmp(argv[1], "generate-proof") != 0) return usage();
     std::string input = "out", witness_path = "witness", pk_path = "proving.key", proof_path = "proof.json", scheme_s = "g16", entropy, cache_dir;
-    bool have_entropy = false, timings = false, self_check = false, resident_tables = false;
+    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false;
     int device = 0;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(2); } return argv[++i]; };
         if (a == "-i" || a == "--input") input = val();
         else if (a == "--verify") self_check = true;
+        else if (a == "--check") check_first = true;                 // the witness against the constraints, on the device, before proving
         else if (a == "--full-tables") resident_tables = true;      // (measurement: build the window-multiple tables a resident prover uses)
         else if (a == "-w" || a == "--witness") witness_path = val();
         else if (a == "-p" || a == "--proving-key-path") pk_path = val();
@@ -314,7 +315,27 @@ int main(int argc, char** argv) {
         if (!program) throw Error(host_code ? host_code : ZKHIP_ERR_PARSE, host_error);
         StdRng rng = have_entropy ? get_rng_from_entropy(entropy) : StdRng::from_os_entropy();
         Timings tm;
-        const Proof proof = hip.prove(scheme, *program, witness.data, witness.size, key, rng, &tm);
+        // --check: Az o Bz == Cz on the device first (zkhip_r1cs_check: the three mat-vecs and one pointwise pass) — a witness that
+        // fails is refused with the number of its first failing constraint, the statement number of the `out` file
+        System system;
+        double ms_check = 0;
+        if (check_first) {
+            t0 = std::chrono::steady_clock::now();
+            system = hip.load_system(*program);
+            tm.r1cs_upload = ms_since(t0);
+            t0 = std::chrono::steady_clock::now();
+            uint64_t first_row = 0, n_bad = 0;
+            if (!hip.check(system, witness.data, witness.size, &first_row, &n_bad))
+                throw Error(ZKHIP_ERR_UNSATISFIED, "the witness does not satisfy the program: constraint " + std::to_string(first_row) + " of " +
+                                                       std::to_string(program->constraints()) + " is not satisfied (" + std::to_string(n_bad) +
+                                                       " in all); its right-hand side is over " + program->row_variables(2, first_row));
+            ms_check = ms_since(t0);
+            printf("checked: the witness satisfies all %llu constraints (%.3f ms)\n", (unsigned long long)program->constraints(), ms_check);
+        }
+        const double upload_ms = tm.r1cs_upload;
+        const Proof proof = check_first ? hip.prove(scheme, system, witness.data, witness.size, key, rng, &tm)
+                                        : hip.prove(scheme, *program, witness.data, witness.size, key, rng, &tm);
+        if (check_first) tm.r1cs_upload = upload_ms;
         t0 = std::chrono::steady_clock::now();
         {
             std::ofstream o(proof_path);
@@ -342,7 +363,9 @@ int main(int argc, char** argv) {
             const VerificationKey vk = VerificationKey::from_json(verification_key_json(scheme, curve, head.data(), head.size()));
             if (!verify(vk, proof)) {
                 remove(proof_path.c_str());
-                throw Error(ZKHIP_ERR_UNSATISFIED, "the proof does not verify against the key of " + pk_path + " (witness not satisfying the program, or a key for another program)");
+                throw Error(ZKHIP_ERR_UNSATISFIED, "the proof does not verify against the key of " + pk_path +
+                                                       (check_first ? " (a key for another program: the witness satisfies this one)"
+                                                                    : " (witness not satisfying the program, or a key for another program)"));
             }
             ms_verify = ms_since(t0);
             printf("verified against the verification key of %s\n", pk_path.c_str());

@@ -312,6 +312,29 @@ __global__ void __launch_bounds__(MATVEC_HUGE_THREADS) k_matvec_huge(CsrDev A, C
     }
     if (threadIdx.x == 0) (which == 0 ? oa : which == 1 ? ob : oc)[i] = acc;
 }
+// Checked proving: is a_i * b_i == c_i for every R1CS row i < n?  a, b, c are the vectors the mat-vec kernels above leave
+// (rows n .. N-1 — the input-consistency rows of a and the zero fill — have b = c = 0 and are not looked at).
+// verdict[0] = lowest failing row (the caller sets it to ~0), verdict[1] = number of failing rows (set to 0).
+// Representation: the mat-vec's sums are fe_mul / fe_add results of operands < p, i.e. CANONICAL packed integers of <M_i, z> * R'
+// (R'-form: the assignment enters as z * R', the matrix values in the saturated Montgomery form cancel their R); rp_mul is the
+// R' Montgomery product followed by rp_canon, so a_i b_i / R' is the canonical integer of <A_i, z> <B_i, z> * R' — equal values
+// have equal words for every curve's Fr here and nothing is left to reduce before the comparison.
+// Memory-bound (3 x 32 B per row, one product), no LDS; a wavefront that saw no failure issues no atomic — a satisfied system
+// is a pure streaming read.  Otherwise its first lane adds the population count of the wave's ballot and offers the wave's lowest
+// failing row (rows rise with the lane number: the lowest set bit of the ballot) with one 64-bit atomic each.
+template <class P>
+__global__ void __launch_bounds__(256) k_r1cs_check(const Fe<P>* __restrict__ a, const Fe<P>* __restrict__ b, const Fe<P>* __restrict__ c, u64 n,
+                                                    unsigned long long* __restrict__ verdict) {
+    ZK_PRIO_HIGH();
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (i < n) bad = !rp_mul(a[i], b[i]).equals(c[i]);
+    const unsigned long long failing = ZK_WAVE_BALLOT(bad);      // (every lane arrives here: no early return above)
+    if (failing != 0 && (threadIdx.x & 63u) == 0) {
+        atomicMin(&verdict[0], (unsigned long long)(i + (u64)__builtin_ctzll(failing)));
+        atomicAdd(&verdict[1], (unsigned long long)__builtin_popcountll(failing));
+    }
+}
 // lanes per row for a matrix with `nnz` entries in `n` rows: the largest power of two <= half the average row length
 static inline int matvec_group(u64 nnz, u64 n) {
     const u64 avg = n ? nnz / n : 0;

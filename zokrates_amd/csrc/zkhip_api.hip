@@ -528,6 +528,43 @@ int32_t zkhip_prove_g16_resident_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const
     });
 }
 
+// ---- checked proving
+int32_t zkhip_r1cs_check(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* z, zkhip_assignment* z_resident, uint64_t* first_row, uint64_t* n_bad) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {
+        require(r1cs && (z || z_resident), ZKHIP_ERR_BAD_ARG, "null argument");
+        require(r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "constraint system belongs to another context");
+        if (!z) require(z_resident->ctx == ctx && z_resident->curve == r1cs->curve && z_resident->m == r1cs->l + r1cs->w, ZKHIP_ERR_BAD_ARG,
+                        "assignment does not match the constraint system");
+        u64 v[2] = {~(u64)0, 0};
+        ops_for(r1cs->curve)->r1cs_check(ctx, r1cs, z, z ? nullptr : z_resident->scalars.p, v);
+        if (first_row) *first_row = v[0];
+        if (n_bad) *n_bad = v[1];
+        if (v[1]) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "constraint %llu of %llu is not satisfied (%llu in all)", (unsigned long long)v[0], (unsigned long long)r1cs->n,
+                     (unsigned long long)v[1]);
+            throw ApiError{ZKHIP_ERR_UNSATISFIED, msg};
+        }
+    });
+}
+int32_t zkhip_ctx_set_checked(zkhip_ctx* ctx, int32_t on) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    const int32_t was = ctx->checked ? 1 : 0;
+    if (on >= 0) ctx->checked = on != 0;
+    return was;
+}
+int32_t zkhip_ctx_unsatisfied(const zkhip_ctx* ctx, uint32_t cap, uint32_t* proof_idx, uint64_t* first_row, uint64_t* n_bad, uint32_t* count) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    for (size_t k = 0; k < ctx->unsat.size() && k < cap; ++k) {
+        if (proof_idx) proof_idx[k] = ctx->unsat[k].proof;
+        if (first_row) first_row[k] = ctx->unsat[k].first_row;
+        if (n_bad) n_bad[k] = ctx->unsat[k].n_bad;
+    }
+    if (count) *count = (uint32_t)ctx->unsat.size();
+    return ZKHIP_OK;
+}
+
 int32_t zkhip_ntt(zkhip_ctx* ctx, int32_t curve, uint32_t log_n, int32_t dir, uint8_t* data) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
     return guarded(ctx, [&] {

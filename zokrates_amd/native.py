@@ -20,9 +20,15 @@ ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "PARSE", -3: "NOMEM", -4: "DEVICE", -5:
 
 
 class ZkhipError(RuntimeError):
+    """`unsatisfied`: after ZKHIP_ERR_UNSATISFIED from a prove call of a context in checked mode, the (proof index within the call,
+    first failing row, failing rows) triples of `zkhip_ctx_unsatisfied`; from `ConstraintSystem.check`, the one triple (0, row, rows).
+    `proofs`: what a batch call wrote all the same — the failing proofs' slots zero-filled, the others as without the check."""
+
     def __init__(self, code, msg):
         super().__init__(f"zkhip error {code} ({ERR_NAMES.get(code, '?')}): {msg}")
         self.code = code
+        self.unsatisfied = []
+        self.proofs = None
 
 
 class Timings(C.Structure):
@@ -65,6 +71,7 @@ class Library:
         "zkhip_ctx_create_multi", "zkhip_multi_free", "zkhip_multi_size", "zkhip_multi_ctx", "zkhip_multi_last_error", "zkhip_multi_r1cs_load",
         "zkhip_multi_pk_load_g16", "zkhip_multi_pk_load_gm17", "zkhip_prove_g16_multi", "zkhip_prove_gm17_multi",
         "zkhip_multi_pk_load_g16_replicas", "zkhip_prove_g16_multi_batch", "zkhip_multi_use_rccl", "zkhip_multi_exchange",
+        "zkhip_r1cs_check", "zkhip_ctx_set_checked", "zkhip_ctx_unsatisfied",
     ]
 
     def __init__(self, path=None):
@@ -152,6 +159,9 @@ class Library:
         L.zkhip_prog_write_bound.restype = i32; L.zkhip_prog_write_bound.argtypes = [u64, u64, u64, vp]
         L.zkhip_prog_write.restype = i32; L.zkhip_prog_write.argtypes = [i32, u64, u64] + [vp] * 9 + [vp, vp, vp, u64, u32, vp, u64, vp]
         L.zkhip_prog_assignment.restype = i32; L.zkhip_prog_assignment.argtypes = [vp, vp, sz, vp, vp, u64, vp]
+        L.zkhip_r1cs_check.restype = i32; L.zkhip_r1cs_check.argtypes = [vp] * 6
+        L.zkhip_ctx_set_checked.restype = i32; L.zkhip_ctx_set_checked.argtypes = [vp, i32]
+        L.zkhip_ctx_unsatisfied.restype = i32; L.zkhip_ctx_unsatisfied.argtypes = [vp, u32, vp, vp, vp, vp]
         self.L = L
 
     def init(self, hw_queues):
@@ -192,9 +202,27 @@ class Context:
         if rc != 0:
             raise ZkhipError(rc, self.lib.L.zkhip_last_error(None).decode())
 
-    def _check(self, rc):
+    def _check(self, rc, proofs=None):
         if rc != 0:
-            raise ZkhipError(rc, self.lib.L.zkhip_last_error(self.h).decode())
+            e = ZkhipError(rc, self.lib.L.zkhip_last_error(self.h).decode())
+            if rc == -5:
+                e.unsatisfied = self.unsatisfied()
+                e.proofs = proofs() if proofs else None
+            raise e
+
+    def set_checked(self, on=True):
+        """`zkhip_ctx_set_checked`: the single-GPU prove calls of this context test Az o Bz == Cz on the device and refuse (ZkhipError
+        code -5, `unsatisfied`) an assignment that fails.  None only reports.  Returns the previous setting."""
+        return bool(self.lib.L.zkhip_ctx_set_checked(self.h, -1 if on is None else int(bool(on))))
+
+    def unsatisfied(self):
+        """`zkhip_ctx_unsatisfied`: [(proof index, first failing row, failing rows)] of the last checked prove call that failed."""
+        count = C.c_uint32()
+        self.lib.L.zkhip_ctx_unsatisfied(self.h, 0, None, None, None, C.byref(count))
+        k = count.value
+        idx, row, bad = np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint64), np.zeros(max(k, 1), dtype=np.uint64)
+        self.lib.L.zkhip_ctx_unsatisfied(self.h, k, _ptr(idx), _ptr(row), _ptr(bad), C.byref(count))
+        return [(int(idx[i]), int(row[i]), int(bad[i])) for i in range(k)]
 
     def describe(self):
         buf = C.create_string_buffer(256)
@@ -359,6 +387,20 @@ class ConstraintSystem:
         self.ctx._check(self.ctx.lib.L.zkhip_r1cs_fingerprint(self.ctx.h, self.h, _ptr(out)))
         return int(out[0]), int(out[1])
 
+    def check(self, z):
+        """`zkhip_r1cs_check`: Az o Bz == Cz on the device for a host assignment (uint8[m*32]) or a resident `Assignment`.
+        Returns (first failing row or None, failing rows); never raises for an unsatisfied system."""
+        first, bad = C.c_uint64(), C.c_uint64()
+        if isinstance(z, Assignment):
+            zp, za = None, z.h
+        else:
+            z = _u8(z, self.m * 32)
+            zp, za = _ptr(z), None
+        rc = self.ctx.lib.L.zkhip_r1cs_check(self.ctx.h, self.h, zp, za, C.byref(first), C.byref(bad))
+        if rc not in (0, -5):
+            self.ctx._check(rc)
+        return (None if rc == 0 else int(first.value)), int(bad.value)
+
     def witness_map(self, z):
         N = 1
         while N < self.n + self.l:
@@ -491,6 +533,10 @@ def prove_g16(ctx, pk, cs, z, r, s, want_timings=False):
     return (out.tobytes(), tm.as_dict()) if want_timings else out.tobytes()
 
 
+def _split_proofs(out, count, step):
+    return [out[i * step:(i + 1) * step].tobytes() for i in range(count)]
+
+
 def prove_g16_resident_batch(ctx, pk, cs, assignments, rs):
     """Pipelined proofs over resident assignments (may repeat); rs: list of (r, s) ints.  Returns (proofs, timings)."""
     nb = FQ_BYTES[pk.curve_id]
@@ -500,9 +546,8 @@ def prove_g16_resident_batch(ctx, pk, cs, assignments, rs):
     rsb = np.frombuffer(b"".join(int(r).to_bytes(32, "little") + int(s).to_bytes(32, "little") for r, s in rs), dtype=np.uint8)
     out = np.zeros(count * (8 * nb + 3), dtype=np.uint8)
     tm = Timings()
-    ctx._check(ctx.lib.L.zkhip_prove_g16_resident_batch(ctx.h, pk.h, cs.h, count, handles, _ptr(rsb), _ptr(out), C.byref(tm)))
-    step = 8 * nb + 3
-    return [out[i * step:(i + 1) * step].tobytes() for i in range(count)], tm.as_dict()
+    ctx._check(ctx.lib.L.zkhip_prove_g16_resident_batch(ctx.h, pk.h, cs.h, count, handles, _ptr(rsb), _ptr(out), C.byref(tm)), lambda: _split_proofs(out, count, 8 * nb + 3))
+    return _split_proofs(out, count, 8 * nb + 3), tm.as_dict()
 
 
 def prove_g16_batch(ctx, pk, cs, zs, rs):
@@ -513,9 +558,8 @@ def prove_g16_batch(ctx, pk, cs, zs, rs):
     rsb = np.frombuffer(b"".join(int(r).to_bytes(32, "little") + int(s).to_bytes(32, "little") for r, s in rs), dtype=np.uint8)
     out = np.zeros(count * (8 * nb + 3), dtype=np.uint8)
     tm = Timings()
-    ctx._check(ctx.lib.L.zkhip_prove_g16_batch(ctx.h, pk.h, cs.h, count, _ptr(zs), _ptr(rsb), _ptr(out), C.byref(tm)))
-    step = 8 * nb + 3
-    return [out[i * step:(i + 1) * step].tobytes() for i in range(count)], tm.as_dict()
+    ctx._check(ctx.lib.L.zkhip_prove_g16_batch(ctx.h, pk.h, cs.h, count, _ptr(zs), _ptr(rsb), _ptr(out), C.byref(tm)), lambda: _split_proofs(out, count, 8 * nb + 3))
+    return _split_proofs(out, count, 8 * nb + 3), tm.as_dict()
 
 
 # ---- GM17 (BASELINE.json config 5) ----
@@ -581,9 +625,8 @@ def prove_gm17_resident_batch(ctx, pk, cs, assignments, rnds):
     rb = np.ascontiguousarray(np.concatenate([_rnd96(*t) for t in rnds])) if count else np.zeros(1, dtype=np.uint8)
     out = np.zeros(max(count, 1) * (8 * nb + 3), dtype=np.uint8)
     tm = Timings()
-    ctx._check(ctx.lib.L.zkhip_prove_gm17_resident_batch(ctx.h, pk.h, cs.h, count, handles, _ptr(rb), _ptr(out), C.byref(tm)))
-    step = 8 * nb + 3
-    return [out[i * step:(i + 1) * step].tobytes() for i in range(count)], tm.as_dict()
+    ctx._check(ctx.lib.L.zkhip_prove_gm17_resident_batch(ctx.h, pk.h, cs.h, count, handles, _ptr(rb), _ptr(out), C.byref(tm)), lambda: _split_proofs(out, count, 8 * nb + 3))
+    return _split_proofs(out, count, 8 * nb + 3), tm.as_dict()
 
 
 # ---- ZoKrates' own files (N1): host only ----
