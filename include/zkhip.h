@@ -289,7 +289,13 @@ int32_t zkhip_msm_g2(zkhip_ctx* ctx, int32_t curve, uint64_t n, const uint8_t* b
  * the further ops 3 sqr and 4 inv (of a; 0 -> 0; b is read but not used); field 3 = the same field computed in the MSM kernels'
  * unsaturated limbs, ops 2 and 3 in the accumulation kernel's inlined form, with the further ops 5 mul and 6 sqr (the
  * out-of-line forms of the other kernels), 7 = a * b - a * a with one reduction per component (the fused Y3), and 8, 9, 10 =
- * (3a)(4b), (3a)^2, (3a)(4b) - (3a)(4a) on un-reduced multiples (values up to 6p and 8p: the top of the forms' operand range). */
+ * (3a)(4b), (3a)^2, (3a)(4b) - (3a)(4a) on un-reduced multiples (values up to 6p and 8p: the top of the forms' operand range).
+ * fields 4 and 5 (tests only) = Fr and Fq, count x sz(field), computed in the single-field unsaturated limbs of the transform
+ * passes and the G1 kernels: op 0 add, 1 sub (bias 2p), 2 mul, 3 sqr, 4 sub (bias 4p), 5 mul and 6 sqr with loose quotient digits
+ * (where the field has the room; the plain forms otherwise), 7 = 8a through three doublings and the weak reduction, 8, 9, 10 as
+ * field 3's on (3a)(4b), (3a)^2, (3a)(4b) - (3a)(4a), 11 = a - 3b by the one-carry-round numerator of X3, and the butterfly
+ * shapes of the transforms, each difference or sum multiplied at once without its carry round: 12 = (a - b) b, 13 = (3a - 7b) a,
+ * 14 = (a + b) a, 15 = -a b (lazy negation).  Fields above 5 are refused. */
 int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op, uint64_t count,
                        const uint8_t* a, const uint8_t* b, uint8_t* out);
 

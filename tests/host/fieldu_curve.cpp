@@ -3,11 +3,15 @@
 #include <cstring>
 #include "ec.cuh"
 using namespace zk;
-template <class P> Fe<P> rnd_fe() {
+template <class P> Fe<P> rnd_fe() {   // uniform below p: BITS random bits, drawn again while they are not below the modulus
     Fe<P> r;
-    for (int i = 0; i < P::N; ++i) r.v[i] = (u32)rand() * 2654435761u + (u32)rand();
-    r.v[P::N - 1] &= (1u << ((P::BITS - 1) % 32)) - 1;
-    return r;
+    for (;;) {
+        for (int i = 0; i < P::N; ++i) r.v[i] = (u32)rand() * 2654435761u + (u32)rand();
+        if (P::BITS % 32) r.v[P::N - 1] &= (1u << (P::BITS % 32)) - 1;
+        bool lt = false;
+        for (int i = P::N - 1; i >= 0; --i) if (r.v[i] != P::mod(i)) { lt = r.v[i] < P::mod(i); break; }
+        if (lt) return r;
+    }
 }
 template <class P> Fe<P> sat(const Fu<P>& a) { return fu_to_fe(a); }
 template <class P> Fe2<P> sat(const Fu2<P>& a) { return fu_to_fe(a); }
@@ -80,5 +84,7 @@ int main() {
     b += test<Fe2<Bn254Fq>, Fu2<Bn254Fq>>("bn254 G2");
     b += test<Fe<Bls381Fq>, Fu<Bls381Fq>>("bls381 G1");
     b += test<Fe2<Bls381Fq>, Fu2<Bls381Fq>>("bls381 G2");
+    b += test<Fe<Bls377Fq>, Fu<Bls377Fq>>("bls377 G1");
+    b += test<Fe2<Bls377Fq>, Fu2<Bls377Fq>>("bls377 G2");
     return b;
 }

@@ -1,6 +1,6 @@
 // TEST ONLY: the fused products of the hot mixed addition (fu2_mul_kara: Karatsuba Fq2 product with two side-by-side
 // reductions; fu_mul4_inl / fu2_mulsub_inl / ec_mulsub: a*b - c*d with one reduction) against the plain products of
-// fieldu.cuh, random and edge operands (zero components, values up to 3p), both base fields.
+// fieldu.cuh, random and edge operands (zero components, values up to 3p), all three base fields.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -64,7 +64,7 @@ template <class P> int run(const char* name) {
     return bad;
 }
 int main() {
-    const int bad = run<Bn254Fq>("bn254") + run<Bls381Fq>("bls12_381");
+    const int bad = run<Bn254Fq>("bn254") + run<Bls381Fq>("bls12_381") + run<Bls377Fq>("bls12_377");
     printf("%d failures\n", bad);
     return bad != 0;
 }

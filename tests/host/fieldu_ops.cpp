@@ -3,14 +3,18 @@
 #include <cstring>
 #include "ec.cuh"
 using namespace zk;
-template <class P> Fe<P> rnd_fe() {
+template <class P> Fe<P> rnd_fe() {   // uniform below p: BITS random bits, drawn again while they are not below the modulus
     Fe<P> r;
-    for (int i = 0; i < P::N; ++i) r.v[i] = (u32)rand() * 2654435761u + (u32)rand();
-    r.v[P::N - 1] &= (1u << ((P::BITS - 1) % 32)) - 1;   // < 2^(BITS-1) < p
-    return r;
+    for (;;) {
+        for (int i = 0; i < P::N; ++i) r.v[i] = (u32)rand() * 2654435761u + (u32)rand();
+        if (P::BITS % 32) r.v[P::N - 1] &= (1u << (P::BITS % 32)) - 1;
+        bool lt = false;
+        for (int i = P::N - 1; i >= 0; --i) if (r.v[i] != P::mod(i)) { lt = r.v[i] < P::mod(i); break; }
+        if (lt) return r;
+    }
 }
 template <class P> bool eq(const Fe<P>& a, const Fe<P>& b) { return a.equals(b); }
-template <class P> int test(const char* name) {
+template <class P, bool FQ2 = true> int test(const char* name) {
     int bad = 0;
     typedef Fe<P> F; typedef Fu<P> U;
     for (int it = 0; it < 2000; ++it) {
@@ -32,15 +36,20 @@ template <class P> int test(const char* name) {
         if (!eq(fu_to_fe(fu_mul2_inl(ua, ub, ub, ua)), fe_dbl(fe_mul(a, b)))) { if (bad++ < 3) printf("%s mul2 mismatch\n", name); }
         if (!eq(fu_to_fe(fu_sqr_inl(ua)), fe_mul(a, a))) { if (bad++ < 3) printf("%s sqr mismatch\n", name); }
         if (!eq(fu_to_fe(fu_sqr_inl(fe_sub_k<4>(ua, ub))), fe_sqr(fe_sub(a, b)))) { if (bad++ < 3) printf("%s sqr(loose) mismatch\n", name); }
-        // Fq2
+        // Fq2 (base fields only)
+        if constexpr (FQ2) {
         Fe2<P> A{a, b}, Bq{b, fe_add(a, a)};
         Fu2<P> uA = fu_from_fe(A), uB = fu_from_fe(Bq);
         Fe2<P> m1 = fe_mul(A, Bq), m2 = fu_to_fe(ec_mul(uA, uB));
         if (!m1.equals(m2)) { if (bad++ < 3) printf("%s fq2 mul mismatch\n", name); }
         Fe2<P> s1 = fe_sqr(A), s2 = fu_to_fe(ec_sqr(uA));
         if (!s1.equals(s2)) { if (bad++ < 3) printf("%s fq2 sqr mismatch\n", name); }
+        }
     }
     printf("%s: %d failures\n", name, bad);
     return bad;
 }
-int main() { return test<Bn254Fq>("bn254") + test<Bls381Fq>("bls381"); }
+int main() {
+    return test<Bn254Fq>("bn254") + test<Bls381Fq>("bls381") + test<Bls377Fq>("bls377") + test<Bn254Fr, false>("bn254 Fr") + test<Bls381Fr, false>("bls381 Fr") +
+           test<Bls377Fr, false>("bls377 Fr");
+}

@@ -557,3 +557,29 @@ def test_error_paths(ctx):
         rp, col, val = oc.csr(0)
         col = col.copy(); col[0] = 10 ** 6
         native.ConstraintSystem(ctx, 0, oc.n, oc.l, oc.w, [(rp, col, val), oc.csr(1), oc.csr(2)])
+
+
+def _structured_ntt_configs():
+    """(tune name, value, sizes): every pass structure at its smallest sizes"""
+    return [("ntt_single_max_log", 10, (2, 5, 10)), ("ntt_single_max_log", 1, (5, 6)), ("ntt_max_sublog", 3, (7, 9))]
+
+
+@pytest.mark.parametrize("config", _structured_ntt_configs(), ids=["single-pass", "two-passes", "three-passes"])
+@pytest.mark.parametrize("curve_id", [0, 1, 2])
+def test_ntt_structured(curve_id, config):
+    """Zeros, constants, spikes, alternating and half-filled vectors, powers of the root and of the coset generator (tests/
+    ntt_structured.py) through every direction, pass structure and both settings of ntt_fuse_first: butterflies that compute a - a,
+    (r - 1) + (r - 1) and runs of zeros, against the oracle and the closed forms.  BLS12-377 rides along (curve id 2)."""
+    import bls377_ref
+    from ntt_structured import check_structured
+    curve = (BN254, BLS12_381, bls377_ref.CURVE)[curve_id]
+    knob, value, sizes = config
+    c2 = native.Context(0, emu_library())       # a fresh plan cache for the tune
+    try:
+        c2.tune(knob, value)
+        for fuse in (1, 0):
+            c2.tune("ntt_fuse_first", fuse)
+            for logn in sizes:
+                check_structured(c2, curve, logn)
+    finally:
+        c2.close()

@@ -1,6 +1,8 @@
 """Unsaturated-limb field (zokrates_amd/csrc/fieldu.cuh) against the saturated Montgomery field of field.cuh, compiled for
 the host with g++: every operation the MSM kernels use (conversions, mul, mul2, add/sub with bias, weak reduction, the
-zero test, Fq2 mul/sqr, XYZZ mixed add / add / doubling incl. the exceptional branches) on both curves."""
+zero test, Fq2 mul/sqr, XYZZ mixed add / add / doubling incl. the exceptional branches) on all three curves (BLS12-377 with its
+own non-residue); the single-field operations also on the three scalar fields the transform passes compute in.  Operands are
+uniform below p.  tests/test_fieldu_contract.py takes the same operations to the edges of their written preconditions."""
 import os
 import subprocess
 

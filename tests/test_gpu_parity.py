@@ -368,3 +368,27 @@ def test_lone_proofs_hold_their_g1_lanes_for_the_g2_accumulation(setting):
                 assert proofs == [want] * 5
     finally:
         c2.close()
+
+
+@pytest.mark.parametrize("config", [(None, 0, (2, 5, 10)), (None, 0, (11, 13)), ("ntt_max_sublog", 3, (7, 9))], ids=["single-pass", "two-passes", "three-passes"])
+@pytest.mark.parametrize("curve_id", [0, 1, 2])
+def test_ntt_structured(curve_id, config):
+    """The structured vectors of tests/ntt_structured.py (zeros, constants at r - 1 and 1, spikes, alternating, half-filled, powers of
+    the root and of the coset generator) through every direction on the device: single pass, two passes (2^11, 2^13), three passes
+    (ntt_max_sublog = 3 on a fresh context), both settings of ntt_fuse_first; all three curves (BLS12-377: curve id 2, reference
+    oracle.groth16.Domain over tests/bls377_ref.py's constants, closed forms alone above 2^10 where they exist)."""
+    import bls377_ref
+    from ntt_structured import check_structured
+    curve = (BN254, BLS12_381, bls377_ref.CURVE)[curve_id]
+    knob, value, sizes = config
+    c2 = native.Context(0)                      # a fresh plan cache for the tunes
+    try:
+        assert "EMULATOR" not in c2.describe()
+        if knob:
+            c2.tune(knob, value)
+        for fuse in (1, 0):
+            c2.tune("ntt_fuse_first", fuse)
+            for logn in sizes:
+                check_structured(c2, curve, logn)
+    finally:
+        c2.close()

@@ -2406,6 +2406,23 @@ struct Prover {
         stream_sync(s);
     }
 
+    // fields 4 and 5 of zkhip_field_op: Fr and Fq in the unsaturated limbs of the transform passes and the G1 kernels (k_field_op_unsat)
+    template <class F>
+    static void field_op_unsat_api(zkhip_ctx* ctx, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+        Stream s = ctx->stream;
+        const size_t bytes = count * sizeof(F);
+        ctx->cur->va.ensure(bytes); ctx->cur->vb.ensure(bytes);
+        dev_h2d(ctx->cur->va.p, a, bytes, s);
+        dev_h2d(ctx->cur->vb.p, b, bytes, s);
+        const unsigned T = 64, B = blocks_for(count, T);
+        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
+        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->vb), count);
+        ZK_LAUNCH((k_field_op_unsat<typename F::Params>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->va), count, op);
+        ZK_LAUNCH((k_from_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
+        dev_d2h(out, ctx->cur->va.p, bytes, s);
+        stream_sync(s);
+    }
+
     static void r1cs_load(zkhip_ctx* ctx, zkhip_r1cs* cs, const u64* const rp[3], const u32* const col[3], const uint8_t* const val[3]) {
         Stream s = ctx->stream;
         std::vector<u64> long_rows, huge_rows;
@@ -2507,7 +2524,9 @@ static void field_op_dispatch(zkhip_ctx* ctx, int field, int op, u64 count, cons
     if (field == 0) Prover<C>::template field_op_api<typename C::Fr>(ctx, op, count, a, b, out);
     else if (field == 1) Prover<C>::template field_op_api<typename C::Fq>(ctx, op, count, a, b, out);
     else if (field == 2) Prover<C>::template field_op_fq2_api<false>(ctx, op, count, a, b, out);
-    else Prover<C>::template field_op_fq2_api<true>(ctx, op, count, a, b, out);
+    else if (field == 3) Prover<C>::template field_op_fq2_api<true>(ctx, op, count, a, b, out);
+    else if (field == 4) Prover<C>::template field_op_unsat_api<typename C::Fr>(ctx, op, count, a, b, out);
+    else Prover<C>::template field_op_unsat_api<typename C::Fq>(ctx, op, count, a, b, out);
 }
 template <class C>
 static int ntt_log1_of(zkhip_ctx* ctx, int logN) { return get_plan<C>(ctx, logN)->split(); }

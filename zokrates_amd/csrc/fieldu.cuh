@@ -11,8 +11,17 @@
 // the integer value may be a small multiple of p above the canonical one.  Invariants (checked by the bounds notes in
 // ec.cuh and by the parity tests):
 //     TIGHT: every limb <= 2^B + 8 (the top limb carries the value's overflow); all stored elements are TIGHT;
-//     mul / mul2 accept TIGHT operands with values < 8p and return TIGHT results with value < 2p;
-//     add, dbl, sub<K> finish with one parallel carry round (no ripple): TIGHT out; sub<K>(a, b) = a + K*p - b needs b < K*p.
+//     mul accepts TIGHT operands with values < 8p and returns a TIGHT result with value < 2p (64 p^2 / R' + p, R' >= 2^6 p);
+//     mul2 the same over the base fields (128 p^2 / R' + p with their R' >= 2^7 p; over a 255-bit scalar field it would be < 3p:
+//     only the curve code sums products);
+//     add, dbl, sub<K> finish with one parallel carry round (no ripple): TIGHT out; sub<K>(a, b) = a + K*p - b needs b < K*p and
+//     b's TOP LIMB <= (K p)_top - 2: the bias holds 4 back from its top limb and the carry round returns at least 2 of them, so
+//     a b whose top limb is (K p)_top - 1 or (K p)_top (the last 2^-17 ... 2^-22 below K p) can leave the top limb wrapped
+//     (the ZK_CHECK_OVERFLOW builds abort on a top limb that does wrap: ZK_SUB_TOP_CHECK).  Every caller keeps a whole p between its
+//     subtrahend and K p: over the base fields a product (< 1.5p) or an affine coordinate (< p + p / 128) against 2p, 2S and Y
+//     (< 4p after their own bounds, ec.cuh) and the c1 of an Fq2 square (< 6p) against their K; over the scalar fields (R' >= 2^6 p:
+//     a product is < 2p) the transforms subtract fe_relax outputs and products (< 3p) against 4p and their sums (< 6p) against 8p
+//     (kernels_ntt.cuh), and the conversions and rp_* helpers subtract nothing.
 // Only the curve kernels use this type; boundaries convert from/to the saturated Montgomery form of field.cuh
 // (fu_from_fe / fu_to_fe), so nothing outside the MSM sees it.  Results are exact group elements either way.
 #pragma once
@@ -219,17 +228,25 @@ ZK_HD Fu<P> fe_dbl(const Fu<P>& a) {
     ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) t[i] = a.v[i] << 1;
     return fu_norm<P>(t);
 }
-// a + K*p - b for K in {2, 4, 8, 16}; needs value(b) < K*p
+// a + K*p - b for K in {2, 4, 8, 16}; needs value(b) < K*p and b's top limb <= (K p)_top - 2 (see the invariants above)
+#if defined(ZK_CHECK_OVERFLOW) && !defined(__HIP_DEVICE_COMPILE__)
+// host builds of the tests: the top limb of a carried difference, a_top + bias_top - b_top + the carry it receives, must not be negative
+#define ZK_SUB_TOP_CHECK(a_top, bias_top, b_top, carry, who) do { if ((long long)(a_top) + (long long)(bias_top) - (long long)(b_top) + (long long)(carry) < 0) { fprintf(stderr, "%s: the top limb wraps (subtrahend's top limb %u against the bias's %u)\n", who, (unsigned)(b_top), (unsigned)(bias_top)); abort(); } } while (0)
+#else
+#define ZK_SUB_TOP_CHECK(a_top, bias_top, b_top, carry, who) ((void)0)
+#endif
 template <int K, class P>
 ZK_HD Fu<P> fe_sub_k(const Fu<P>& a, const Fu<P>& b) {
     typedef UConst<P> C;
     static_assert(K == 2 || K == 4 || K == 8 || K == 16, "fe_sub_k: K in {2, 4, 8, 16}");
     u32 t[Fu<P>::N];
     ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) t[i] = a.v[i] + (K == 2 ? C::bias2(i) : K == 4 ? C::bias4(i) : K == 8 ? C::bias8(i) : C::bias16(i)) - b.v[i];
+    ZK_SUB_TOP_CHECK(a.v[Fu<P>::N - 1], (K == 2 ? C::bias2(Fu<P>::N - 1) : K == 4 ? C::bias4(Fu<P>::N - 1) : K == 8 ? C::bias8(Fu<P>::N - 1) : C::bias16(Fu<P>::N - 1)),
+                     b.v[Fu<P>::N - 1], t[Fu<P>::N - 2] >> Fu<P>::B, "fe_sub_k");
     return fu_norm<P>(t);
 }
 template <class P> ZK_HD Fu<P> fe_sub(const Fu<P>& a, const Fu<P>& b) { return fe_sub_k<4>(a, b); }
-// negation of an AFFINE coordinate (value < 2p, as produced by fu_from_fe): the result is again < 2p, so a negated base
+// negation of an AFFINE coordinate (value < 2p with top limb <= (2p)_top - 2, as produced by fu_from_fe): the result is again < 2p, so a negated base
 // obeys the same bounds as any other; the all-zero sentinel of the point at infinity stays all-zero
 template <class P> ZK_HD Fu<P> fe_neg(const Fu<P>& a) { return a.is_zero() ? a : fe_sub_k<2>(Fu<P>::zero(), a); }
 
@@ -242,7 +259,8 @@ template <class P> ZK_HD Fu<P> fe_neg(const Fu<P>& a) { return a.is_zero() ? a :
 #else
 #define ZK_LAZY_TOP_CHECK(P_, bias_top, b_top, who) ((void)0)
 #endif
-// 2p - a WITHOUT the carry round, for a TIGHT a with value < 2p (a product, an affine coordinate): limbs up to 2^(B+1) + 2^B, so
+// 2p - a WITHOUT the carry round, for a TIGHT a with value < 2p and top limb <= (2p)_top - 2 (a product, an affine coordinate):
+// limbs up to 2^(B+1) + 2^B, so
 // the result is ONLY good as one operand of a single product (fu_mul_inl) or of a two-product sum (fu_mul2_inl) whose other
 // operands are TIGHT — N * 2^(2B+1.6) + the reduction's N * 2^(2B) stay far below 2^64 — and saves the 25 instructions of
 // the carry round where a negated value is multiplied at once (the base's y of a negative digit, PPP in the fused Y3).
@@ -253,7 +271,8 @@ ZK_HD Fu<P> fe_neg_lazy(const Fu<P>& a) {
     ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) r.v[i] = UConst<P>::nbias2(i) - a.v[i];
     return r;
 }
-// a + K p - b and a + b WITHOUT the carry round, for TIGHT a and b (value(b) < K p): limbs up to 2^(B+2), so the result is ONLY
+// a + K p - b and a + b WITHOUT the carry round, for TIGHT a and b (value(b) < K p, b's top limb <= (K p)_top - 2): limbs up to
+// 2^(B+2), so the result is ONLY
 // good as the operand of a single product whose other operand is TIGHT with limbs < 2^B exactly — a twiddle factor unpacked
 // from its table: N * 2^(2B+2) + the reduction's N * 2^(2B) < 2^64 for both limb widths.  The butterflies of the transforms
 // multiply most of their sums and differences at once (kernels_ntt.cuh): 25 instructions less each.
@@ -279,11 +298,12 @@ ZK_HD Fu<P> fe_cneg_for_mul(const Fu<P>& y, bool neg) {
     ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) r.v[i] = neg ? UConst<P>::nbias2(i) - y.v[i] : y.v[i];
     return r;
 }
-// neg ? 2p - y : y, normalised (TIGHT, < 2p): the y of a base that is not the point at infinity with the sign of its digit
+// neg ? 2p - y : y, normalised (TIGHT, < 2p): the y of a base that is not the point at infinity (as fe_neg's operand) with the sign of its digit
 template <class P>
 ZK_HD Fu<P> fe_cneg(const Fu<P>& y, bool neg) {
     u32 t[Fu<P>::N];
     ZK_UNROLL for (int i = 0; i < Fu<P>::N; ++i) t[i] = neg ? UConst<P>::bias2(i) - y.v[i] : y.v[i];
+    if (neg) ZK_SUB_TOP_CHECK(0u, UConst<P>::bias2(Fu<P>::N - 1), y.v[Fu<P>::N - 1], t[Fu<P>::N - 2] >> Fu<P>::B, "fe_cneg");
     return fu_norm<P>(t);
 }
 // c ? a : b, limb by limb (a v_cndmask each): where two lanes of a wavefront need different values in the same registers
@@ -571,7 +591,8 @@ ZK_HD Fu<P> fu_beta_times(const Fu<P>& a) {   // BETA * a, TIGHT in, TIGHT out
 }
 // (a0 + a1 u)(b0 + b1 u) = (a0 b0 - BETA a1 b1) + (a0 b1 + a1 b0) u: two sums of two products, each reduced once
 // (the same 4 x N^2 + 2 x N^2 multiply-adds as Karatsuba's three full products, but one negation instead of five
-// additions, and results that stay below 2p whatever the operands)
+// additions, and results that stay below 2p whatever the operands: TIGHT components < 8p, and b1 — negated against 8p — with
+// top limb <= (8p)_top - 2 as every subtrahend, see the invariants at the top)
 template <class P, bool LOOSE = false>
 ZK_HD Fu2<P> fu2_mul_inl(const Fu2<P>& a, const Fu2<P>& b) {
     // 8p - b1 without its carry round (limbs < 2^(B+1) + 2^B): it is multiplied at once, in a column of two products whose other
@@ -605,7 +626,7 @@ ZK_HD Fu2<P> fu2_sqr_inl(const Fu2<P>& a) {
 //   c0 = a0 b0 + a1 (8p - b1),   c1 = (a0 + a1)(b0 + b1) - a0 b0 + a1 (8p - b1)      [a1 (8p - b1) = -a1 b1 mod p]
 // Column k of (a0 + a1)(b0 + b1) is the sum of the columns of a0 b0, a0 b1, a1 b0, a1 b1, so subtracting column k of a0 b0
 // never goes negative; both reductions run side by side.  5 N^2 multiply-adds instead of 6 N^2.
-// Operands: TIGHT, a < 4p per component, b < 2p per component.
+// Operands: TIGHT, a < 4p per component, b < 2p per component (b1 is negated against 8p: far inside sub<8>'s top-limb bound).
 template <class P>
 ZK_HD Fu2<P> fu2_mul_kara(const Fu2<P>& a, const Fu2<P>& b) {
     // (BETA != 1: c0 wants BETA a1 (8p - b1) and c1 the unscaled a1 (8p - b1) — a fourth limb product, so the plain form serves)
@@ -654,7 +675,8 @@ ZK_HD Fu2<P> fu2_mul_kara(const Fu2<P>& a, const Fu2<P>& b) {
     r.c1.v[N - 1] = (u32)acc1;
     return r;
 }
-// a*b - c*d in Fq2 with one reduction per component (four limb products each): the tail of the mixed addition's Y3
+// a*b - c*d in Fq2 with one reduction per component (four limb products each): the tail of the mixed addition's Y3.
+// Components TIGHT < 8p; b1, d0 and d1 are negated against 8p: top limb <= (8p)_top - 2 (the callers' are < 2p and < 4p).
 template <class P, bool LOOSE = false>
 ZK_HD Fu2<P> fu2_mulsub_inl(const Fu2<P>& a, const Fu2<P>& b, const Fu2<P>& c, const Fu2<P>& d) {
     // c0 = a0 b0 - a1 b1 - c0 d0 + c1 d1;  c1 = a0 b1 + a1 b0 - c0 d1 - c1 d0      (negations as 8p - x)
@@ -782,7 +804,7 @@ template <class P> struct FuUnpack<Fu2<P>> { ZK_HD static Fu2<P> get(const u32* 
 
 template <class P> ZK_HD Fu2<P> fu_from_fe(const Fe2<P>& a) { return {fu_from_fe(a.c0), fu_from_fe(a.c1)}; }
 template <class P> ZK_HD Fe2<P> fu_to_fe(const Fu2<P>& a) { return {fu_to_fe(a.c0), fu_to_fe(a.c1)}; }
-// 1 / (a0 + a1 u) = (a0 - a1 u) / (a0^2 + BETA a1^2)
+// 1 / (a0 + a1 u) = (a0 - a1 u) / (a0^2 + BETA a1^2); components TIGHT < 8p, a1 (negated by sub<8>) with top limb <= (8p)_top - 2
 template <class P>
 ZK_HD Fu2<P> ec_inv(const Fu2<P>& a) {
     Fu<P> n;

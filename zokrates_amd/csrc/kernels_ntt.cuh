@@ -415,12 +415,63 @@ template <class P>
 __device__ __forceinline__ Fu<P> fu_mul_ntt(const Fu<P>& a, const Fu<P>& b) {
     return ZK_NTT_LOOSE ? fu_mul_loose(a, b) : fu_mul_inl(a, b);
 }
+// TEST ONLY (fields 4 and 5 of zkhip_field_op): the single-field unsaturated arithmetic on Fr (what every transform pass computes in)
+// and on Fq (the G1 kernels), as the device compiles it — the lazy forms inside the one product their comments allow.  Operands arrive
+// in the saturated Montgomery form and enter through fu_from_fe (TIGHT, < p + p / 64); a factor that stands for a twiddle goes through
+// rp_canon and fu_unpack, i.e. comes "from its table" with limbs < 2^B exactly; results < 2p leave through rp_canon / fu_unpack /
+// fu_to_fe, larger ones through fe_relax and fu_to_fe.
+// op: 0 add, 1 sub<2>, 2 mul, 3 sqr, 4 sub<4>, 5 / 6 mul and sqr with loose quotient digits (where the field has the room), 7 relax(8x),
+// 8, 9, 10 the hot forms on X = 3x (< 6p) and Y = 4y (< 8p): X * Y, X * X, X * Y - X * (4x); 11 x3_numerator(x, y, y) = x - 3y;
+// the butterfly shapes of the transforms: 12 (x - y) y by sub_k_lazy<4>, 13 (3x - 7y) x by sub_k_lazy<8>, 14 (x + y) x by add_lazy,
+// each through fu_mul_ntt; 15 mul(neg_lazy(y), x) = -x y.
+template <class P>
+__global__ void k_field_op_unsat(const Fe<P>* __restrict__ a, const Fe<P>* __restrict__ b, Fe<P>* __restrict__ out, u64 n, int op) {
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    typedef Fu<P> U;
+    const U ux = fu_from_fe(a[i]), uy = fu_from_fe(b[i]);
+    U r;
+    bool below_2p = true;
+    switch (op) {
+    case 0: r = fe_add(ux, uy); below_2p = false; break;
+    case 1: r = fe_sub_k<2>(ux, uy); below_2p = false; break;
+    case 2: r = fu_mul_inl(ux, uy); break;
+    case 3: r = fu_sqr_inl(ux); break;
+    case 4: r = fe_sub_k<4>(ux, uy); below_2p = false; break;
+    case 5: r = fu_mul_loose(ux, uy); break;
+    case 6: r = fu_sqr_loose(ux); break;
+    case 7: r = fe_relax(fe_dbl(fe_dbl(fe_dbl(ux)))); below_2p = false; break;
+    case 8: case 9: case 10: {
+        const U X = fe_add(fe_dbl(ux), ux), Y = fe_dbl(fe_dbl(uy));      // TIGHT (a carry round each), < 6p and < 8p
+        r = op == 8 ? fu_mul_loose(X, Y) : op == 9 ? fu_sqr_loose(X) : fe_sub_k<2>(fu_mul_loose(X, Y), fu_mul_loose(X, fe_dbl(fe_dbl(ux))));
+        below_2p = op != 10;
+    } break;
+    case 11: r = fe_relax(fu_x3_numerator(ux, uy, uy)); below_2p = false; break;
+    case 12: case 13: case 14: {
+        const Fe<P> cx = rp_canon(ux), cy = rp_canon(uy);
+        const U wx = fu_unpack<P>(cx.v), wy = fu_unpack<P>(cy.v);          // the factor as a table holds it: limbs < 2^B exactly
+        if (op == 12) r = fu_mul_ntt<P>(fe_sub_k_lazy<4>(ux, uy), wy);
+        else if (op == 13) {
+            const U y2 = fe_dbl(uy);
+            r = fu_mul_ntt<P>(fe_sub_k_lazy<8>(fe_add(fe_dbl(ux), ux), fe_add(fe_add(fe_dbl(y2), y2), uy)), wx);      // 7y < 8p - p / 2
+        } else r = fu_mul_ntt<P>(fe_add_lazy(ux, uy), wx);
+    } break;
+    default: r = fu_mul_inl(fe_neg_lazy(uy), ux); break;
+    }
+    if (below_2p) {
+        const Fe<P> c = rp_canon(r);
+        r = fu_unpack<P>(c.v);
+    }
+    out[i] = fu_to_fe(r);
+}
 // In-place DIF over `nseq` sequences of n = 2^logn points; the result is left in bit-reversed index order.
 // Radix-4 butterflies = two radix-2 stages each:
 //   (a, b, c, d) at i, i+q, i+2q, i+3q (q = L/4)  ->  a+b+c+d | (a-b+c-d) w^2pos | (a-c + w4(b-d)) w^pos | (a-c - w4(b-d)) w^3pos
-// Value bounds (fieldu.cuh): inputs < 2p; sums/differences < 12p; products < 2p; the untwiddled output is brought back
-// below 2p by fe_relax.  The last round of an even-length transform has trivial twiddles and leaves values < 12p, which
-// the store path of the passes accepts.
+// Value bounds (fieldu.cuh): inputs < 3p (what fe_relax leaves: a loaded element, the untwiddled output of the round before; the
+// twiddled outputs are products, < 2p); t0, t2 < 6p and t1 < 7p, so every subtrahend keeps its K (t2 against 8p, c, d and t3 against
+// 4p) and the sums and differences stay < 14p; their products with a factor < 2p are < 2p (R' >= 2^6 p); the untwiddled output
+// a + b + c + d < 12p is brought back below 3p by fe_relax.  The last round of an even-length transform has trivial twiddles and
+// leaves values < 14p, which the store path of the passes accepts (< 32p).
 // (first_done: the round of length n has been done on the way in — ntt_first_round below — and the data in LDS is its output)
 template <class P>
 __device__ __forceinline__ void lds_ntt_dif4(u32* lds, int PL, int SS, int logn, int nseq, const u32* __restrict__ plan, u32 plen, bool first_done = false) {

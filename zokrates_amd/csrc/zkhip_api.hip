@@ -597,7 +597,7 @@ int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op,
                        uint8_t* out) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
     return guarded(ctx, [&] {
-        require(a && b && out && op >= 0 && field >= 0 && field <= 3 && op <= (field < 2 ? 2 : field == 2 ? 4 : 10), ZKHIP_ERR_BAD_ARG, "bad argument");
+        require(a && b && out && op >= 0 && field >= 0 && field <= 5 && op <= (field < 2 ? 2 : field == 2 ? 4 : field == 3 ? 10 : 15), ZKHIP_ERR_BAD_ARG, "bad argument");
         ops_for(curve)->field_op(ctx, field, op, count, a, b, out);
     });
 }

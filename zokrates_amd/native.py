@@ -277,10 +277,11 @@ class Context:
         return out.tobytes()
 
     def field_op(self, curve_id, field, op, a, b):
-        nb = 32 if field == 0 else FQ_BYTES[curve_id] * (2 if field >= 2 else 1)     # (fields 2, 3: Fq2 — include/zkhip.h)
+        nb = 32 if field in (0, 4) else FQ_BYTES[curve_id] * (2 if field in (2, 3) else 1)     # (fields 2, 3: Fq2; 4, 5: unsaturated Fr, Fq — include/zkhip.h)
         a = _u8(a); b = _u8(b, a.size)
         out = np.zeros(a.size, dtype=np.uint8)
-        code = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "mul_call": 5, "sqr_call": 6, "mulsub": 7, "mul_wide": 8, "sqr_wide": 9, "mulsub_wide": 10}[op]
+        code = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "mul_call": 5, "sqr_call": 6, "mulsub": 7, "mul_wide": 8, "sqr_wide": 9, "mulsub_wide": 10,
+                "sub4": 4, "mul_loose": 5, "sqr_loose": 6, "relax8": 7, "x3_numerator": 11, "bf_sub4": 12, "bf_sub8": 13, "bf_add": 14, "mul_neg_lazy": 15}[op]      # (fields 4, 5)
         self._check(self.lib.L.zkhip_field_op(self.h, curve_id, field, code, a.size // nb, _ptr(a), _ptr(b), _ptr(out)))
         return out
 
