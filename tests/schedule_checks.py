@@ -11,7 +11,7 @@ from zokrates_amd import native
 def schedule_invariance(c2, logn=5, kinds=("dense", "sha")):
     """The order in which a proof's kernels are released (`z_gate`), A / B1 / L as one launch or three (`fuse_z`) and the
     slices per launch (`msm_fused_waves`) are scheduling only: the proof bytes do not move, single or pipelined,
-    Groth16 or GM17.  """
+    Groth16 or GM17; nor do they move with the window width of the key's tables (`msm_c`), which decides the placement pass of the sort."""
     from oracle import gm17
     for kind in kinds:
         oc = cpu.Circuit.synth(0, (1 << logn) - 2, 0x5C4ED + logn, kind)
@@ -34,22 +34,24 @@ def schedule_invariance(c2, logn=5, kinds=("dense", "sha")):
                     g = native.prove_gm17(c2, gpk, cs, z, 21, 22, 23)
                     gwant = gwant or g
                     assert g == gwant, (kind, gate, fuse, waves)
-            # the placement pass of the sort, one level (round 5) against two (round 6), and the lone-proof layouts: the same bytes
-            for two_level, lone in ((0, 0), (1, 3), (0, 1)):
-                c2.tune("sort_two_level", two_level); c2.tune("lone_sched", lone); c2.tune("fold_lines", two_level + lone % 2)
-                c2.tune("fold_hop", two_level + lone % 2)      # (the fold chains on second streams of their lanes: never / every lane / the G2 lane)
-                assert native.prove_g16(c2, pk, cs, z, *rs[0]) == want[0], (kind, two_level, lone)
-                proofs, _ = native.prove_g16_batch(c2, pk, cs, np.concatenate([z] * len(rs)), rs)
-                assert proofs == want, (kind, two_level, lone)
-                assert native.prove_gm17(c2, gpk, cs, z, 21, 22, 23) == gwant
+            # the placement pass of the sort, one level (k_msm_place: fewer than 256 buckets per window) against two (coarse bins, then tiles): the
+            # same key under the widest one-level window, c = 8, and the narrowest two-level one, c = 9 (K = 2^(c-1) >= 2^MSM_COARSE_BITS) — the same bytes
+            for c in (8, 9):
+                c2.tune("msm_c", c)
+                pk_c = native.ProvingKey(c2, 0, cpu.ProvingKey.setup(oc, tox).serialize())
+                gpk_c = native.ProvingKey(c2, 0, cpu.Gm17ProvingKey.setup(oc, cpu.gm17_toxic_bytes(gtox)).serialize(), scheme="gm17")
+                assert native.prove_g16(c2, pk_c, cs, z, *rs[0]) == want[0], (kind, c)
+                proofs, _ = native.prove_g16_batch(c2, pk_c, cs, np.concatenate([z] * len(rs)), rs)
+                assert proofs == want, (kind, c)
+                assert native.prove_gm17(c2, gpk_c, cs, z, 21, 22, 23) == gwant, (kind, c)
         finally:
-            c2.tune("z_gate", 1); c2.tune("fuse_z", 1); c2.tune("msm_fused_waves", 0); c2.tune("sort_two_level", 1); c2.tune("lone_sched", 0); c2.tune("fold_lines", 0); c2.tune("fold_hop", 0)
+            c2.tune("z_gate", 1); c2.tune("fuse_z", 1); c2.tune("msm_fused_waves", 0); c2.tune("msm_c", 0)
         assert gwant == cpu.gm17_trapdoor(oc, cpu.gm17_toxic_bytes(gtox), z, 21, 23)
 
 
 def stream_plan_invariance(make_ctx, logn=5):
     """A resident prover's stream plan (ZKHIP_TUNE_PIPE_PLAN, core.cuh make_pipe_streams: the context's streams made in one go at its
-    first proof, the fold chains on streams of their own, a lone proof's witness map on another) is placement only: lone proofs, a
+    first proof, a lone proof's witness map on one of its own) is placement only: lone proofs, a
     pipelined batch, a bound key and GM17 give the bytes the oracle gives.  The plan is chosen before the first proof and refused after."""
     from oracle import gm17
     import pytest

@@ -440,18 +440,18 @@ def test_cli_end_to_end(tmp_path, scheme):
 # ------------------------------------------------------------------ 7. scheduling knobs
 def test_schedule_invariance():
     """The knobs tests/schedule_checks.py turns for BN254 (that helper is tied to curve 0 and the C++ oracle): release order, fused or
-    separate launches, slices per launch, the sort's placement pass, the lone-proof layouts — the bytes of a BLS12-377 proof do not move."""
+    separate launches, slices per launch, the sort's placement pass (by the window width of the key's tables) — the bytes of a BLS12-377 proof do not move."""
     c2 = native.Context(0, emu_library())
     try:
         cs, z, ncs = _system(c2, 30, "sha", seed=0x5C4ED)
         zb = le(z)
         tox, gtox = g16.Toxic.from_seed(C), ogm17.Toxic.from_seed(C)
-        pk = native.ProvingKey(c2, CID, native.setup_g16(c2, ncs, _tox5(tox)))
-        gpk = native.ProvingKey(c2, CID, native.setup_gm17(c2, ncs, (gtox.alpha, gtox.beta, gtox.gamma, gtox.t)), scheme="gm17")
+        raw, graw = native.setup_g16(c2, ncs, _tox5(tox)), native.setup_gm17(c2, ncs, (gtox.alpha, gtox.beta, gtox.gamma, gtox.t))
+        pk, gpk = native.ProvingKey(c2, CID, raw), native.ProvingKey(c2, CID, graw, scheme="gm17")
         rs = [(11, 13), (0, 5), (7, 0), (1 << 200, 3)]
         want = [formats.proof_raw(C, ref.g16_trapdoor(cs, tox, z, a, b)) for a, b in rs]
         gwant = formats.proof_raw(C, ref.gm17_trapdoor(cs, gtox, z, 21, 23))
-        def check(tag):
+        def check(tag, pk=pk, gpk=gpk):
             assert native.prove_g16(c2, pk, ncs, zb, *rs[0]) == want[0], tag
             proofs, _ = native.prove_g16_batch(c2, pk, ncs, np.concatenate([zb] * len(rs)), rs)
             assert proofs == want, tag
@@ -460,10 +460,9 @@ def test_schedule_invariance():
             for fuse, waves in ((1, 0), (1, 3), (0, 0)):
                 c2.tune("z_gate", gate); c2.tune("fuse_z", fuse); c2.tune("msm_fused_waves", waves)
                 check((gate, fuse, waves))
-        for two_level, lone in ((0, 0), (1, 3), (0, 1)):
-            c2.tune("sort_two_level", two_level); c2.tune("lone_sched", lone); c2.tune("fold_lines", two_level + lone % 2)
-            c2.tune("fold_hop", two_level + lone % 2)
-            check((two_level, lone))
+        for c in (8, 9):     # the same key under the widest window of the one-level placement pass and the narrowest of the two-level one
+            c2.tune("msm_c", c)
+            check(("msm_c", c), native.ProvingKey(c2, CID, raw), native.ProvingKey(c2, CID, graw, scheme="gm17"))
     finally:
         c2.close()
 

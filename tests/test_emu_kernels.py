@@ -123,8 +123,8 @@ def test_msm_fold_fallback(ctx):
 @pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
 def test_msm_fold_meets_equal_and_opposite_sums(ctx, curve):
     """The fold adds bucket SUMS, and two of them can be the same point or opposite ones: the same base under two digits (buckets of one
-    row and of one column: the line sums and the scan both pair them), a bucket whose slices hold equal partial sums, sums that cancel.
-    xyzz_add_from's doubling takes the addition's own tail with other inputs (ec.cuh); both fold layouts must agree with the oracle."""
+    row and of one column: the row / column sums and the scan both pair them), a bucket whose slices hold equal partial sums, sums that cancel.
+    xyzz_add_from's doubling takes the addition's own tail with other inputs (ec.cuh); the fold must agree with the oracle."""
     rnd = random.Random(12)
     G1, G2 = groups(curve)
     P1, Q1 = (G1.amul(G1.gen, rnd.randrange(1, curve.r)) for _ in range(2))
@@ -144,15 +144,12 @@ def test_msm_fold_meets_equal_and_opposite_sums(ctx, curve):
             b2 = np.frombuffer(b"".join(formats.ser_g2(curve, P) for P in p2), dtype=np.uint8)
             want1, want2 = cpu.msm(curve.curve_id, 1, b1, le(ks)), cpu.msm(curve.curve_id, 2, b2, le(ks))
             ctx.tune("msm_c", c)
-            for lines in (1, 0):
-                ctx.tune("fold_lines", lines)
-                for min_slice in (1, 2):
-                    ctx.tune("msm_min_slice", min_slice)
-                    assert ctx.msm(curve.curve_id, 1, b1, le(ks)) == want1, (c, ks, lines, min_slice)
-                    assert ctx.msm(curve.curve_id, 2, b2, le(ks)) == want2, (c, ks, lines, min_slice)
+            for min_slice in (1, 2):
+                ctx.tune("msm_min_slice", min_slice)
+                assert ctx.msm(curve.curve_id, 1, b1, le(ks)) == want1, (c, ks, min_slice)
+                assert ctx.msm(curve.curve_id, 2, b2, le(ks)) == want2, (c, ks, min_slice)
     finally:
         ctx.tune("msm_c", 0)
-        ctx.tune("fold_lines", 0)
         ctx.tune("msm_min_slice", 8)
 
 

@@ -42,16 +42,14 @@ def test_gpu_what_does_not_bind(gctx):
     T.test_what_does_not_bind(gctx)
 
 
-@pytest.mark.parametrize("sched", [1, 2, 3])
-def test_gpu_lone_proof_layouts(sched):
-    """ZKHIP_TUNE_LONE_SCHED: a lone proof's G2 accumulation at one workgroup per CU, its G1 lanes behind the h sort — scheduling
-    only: the same bytes at every setting, bound and as loaded, both curves, and batches untouched."""
+def test_gpu_lone_proof_layouts():
+    """A lone proof's layout (its G2 lane first, the G1 lanes held for it over a bound key: g2_head_start) against a resident batch's: the
+    same bytes lone, host or resident assignment, and in a batch of five, bound and as loaded, both curves."""
     import numpy as np
     from oracle import cpu
     from oracle import groth16 as g16
     c2 = native.Context(0)
     try:
-        c2.tune("lone_sched", sched)
         for curve in (BN254, BLS12_381):
             oc = cpu.Circuit.synth(curve.curve_id, 3000, 0x5EED00D0, "sha")
             tox = cpu.toxic_bytes(g16.Toxic.from_seed(curve))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time of the transform passes alone (one stream) under a few settings of one knob, alternating in ONE process:
-usage: ntt_probe.py <tunable> v1 v2 ...   e.g.  ntt_probe.py ntt_skew_us 0 4 8 12 16
+usage: ntt_probe.py <tunable> v1 v2 ...   e.g.  ntt_probe.py ntt_cols 1 2 4
 prints kernel_ntt_ms of lone serial proofs over a bound 2^20 key (8 pass-vectors + the pointwise kernel) per setting."""
 import json
 import os

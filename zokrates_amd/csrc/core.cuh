@@ -122,15 +122,6 @@ struct MsmLane {
     bool high_priority = false;
     DBuf lane_key, heavy, partial, bucket, rows, cols;
     Event done = nullptr;
-    Stream fold_stream = 0;   // a second stream for the lane's fold chain (zkhip_ctx::fold_hop; made on first use: lane_fold_stream)
-    bool fold_made = false;
-    bool fold_owned = true;   // (false: one stream per lane TYPE, shared by the slots and owned by the context — make_pipe_streams)
-    Event acc_done = nullptr; // ... which waits for this event behind the lane's accumulation
-    bool lone_launch = false; // THIS launch of the lane belongs to a lone proof: its fold hops only to the lane's lone fold stream, if the plan made one
-    Stream lone_fold_stream = 0;   // ("gl" / "zl" / "hl" of the stream plan: slot 0's lanes)
-    bool lone_fold_made = false;
-    bool share_cu = false;    // THIS launch of the lane: one accumulation workgroup per CU (LDS padding) at raised wave priority — a lone proof's
-                              // G2 lane (zkhip_ctx::lone_sched); reset by msm_run_tables
 };
 static constexpr int ZK_NLANES = 5;   // A, B1, L (G1), B2 (G2) over z; H over h
 static constexpr int ZK_NSLOTS = 4;   // most proofs in flight (zkhip_prove_g16*_batch pipelines consecutive proofs; ctx->nslots of them are used)
@@ -150,8 +141,6 @@ struct ProofSlot {
     Event half_ready = nullptr;                           // a member of a multi-GPU proof: its half of the witness map (a or b on the coset) is in va
     int half = -1;                                        // which half this proof's head computed (-1: the whole witness map)
     bool lone = false;                                    // (enqueue_head -> enqueue_tail)
-    Stream fold_slot = 0;                                 // one stream for the fold chains of this slot's three lanes ("f" of the stream plan)
-    bool fold_slot_made = false;
     bool ready = false;        // streams and events exist (slot_init)
     // the proof currently in flight in this slot
     bool busy = false;
@@ -179,30 +168,13 @@ struct zkhip_ctx {
     u32 msm_lanes = 0;        // slices of the sorted list (0 = one per resident work-item)
     u32 msm_min_slice = 8;    // finest cut of the sorted list
     bool heavy_runs = true;   // k_msm_heavy_reduce before the fold (ZKHIP_MSM_HEAVY_RUNS=0: the row's workgroup sums a heavy bucket alone)
-    int heavy_threads = 64;   // work-items per workgroup of k_msm_heavy_reduce (64 / 128 / 256; ZKHIP_HEAVY_THREADS).  The kernel is launched whether or not
-                              // a heavy bucket exists (the list is on the device) and must find a place before it can return: one wave and 9 / 18 KB of
-                              // LDS (G1 / G2) instead of four and 36 / 73 is a place found sooner beside the accumulations, and a run of a heavy bucket is
-                              // 8 serial additions + 6 tree levels instead of 2 + 8.  Lone dense proofs: median 9.61 against 9.78 ms over three processes
-                              // of 40 each, the stdlib SHA-256 circuit (which HAS heavy buckets) and the others level (profiles/r7s_*, r7q_*)
     int fold_hg = 32;         // shares a column of rows is cut into in k_msm_fold_cols (a power of two <= 256; ZKHIP_FOLD_HG): 128 rows = 4 serial additions +
                               // 5 tree levels instead of 16 + 3 at 8 (the fold is a chain of dependent additions: Poseidon BLS12-381 8.95 -> 7.85 ms single)
     bool fold_scan = true;    // scan form of the last fold step (else double-and-add)
-    int fold_lines = 0;       // rows and columns of the bucket matrix in one launch (k_msm_fold_lines): 0 never (the rows-then-columns pair), 1 always,
-                              // 2 for launches over ONE table.  Measured and left OFF (profiles/r6m_fold_layouts_ab.txt): twice the workgroups of the
-                              // row pass — over three tables (A, B1, L) they no longer fit the machine in one round (290 us against 178 + 108), over
-                              // one table the launch saved is all there is (210 against 119 + 98); 110-112 proofs/s against 115-116 (ZKHIP_FOLD_LINES)
     bool fuse_z = true;       // A, B1 and L of a proof (one sorted list) as ONE slicing / accumulation / fold launch each
     int msm_fused_waves = 0;  // accumulation waves per SIMD of that launch (0 = per point type)
     int msm_g1_waves = 0, msm_g2_waves = 0;   // slices per SIMD lane of a single-table G1 / G2 accumulation (0 = per point type)
     int z_gate = 1;           // which accumulations over z wait for the witness map of their proof: 0 none, 1 the G1 lanes, 2 all
-    int lone_sched = 0;       // how a LONE proof (the single-proof entry points; nothing else of the context in flight) is laid out — bits:
-                              // 1: its G2 accumulation takes ONE workgroup per CU (dynamic LDS padded to more than half a CU's) at raised wave
-                              //    priority: the short kernels of the witness map and of the sorts find a place at once instead of waiting for a
-                              //    round of accumulation workgroups to retire (a 0.65 ms witness map took 3.4 ms beside a machine-filling G2
-                              //    accumulation, the h sort 3.3 ms instead of 0.5: profiles/r6a_lone_bound_proof_gantt.txt);
-                              // 2: its G1 lanes over z wait for the h SORT as well (else for the witness map only): that sort then runs beside
-                              //    the G2 lane alone, and the H accumulation can start with the others
-                              // (ZKHIP_LONE_SCHED / ZKHIP_TUNE_LONE_SCHED; batches are untouched)
     int g2_head_start = 1;    // a LONE proof over a curve whose G2 accumulation runs one wave per SIMD: its G1 lanes also wait for the end of
                               // that accumulation — 0 never, 1 over a bound key, 2 always (ZKHIP_G2_HEAD_START; Prover::enqueue)
     int split_min_log = 18;   // smallest domain (log2) whose witness map the members of a multi-GPU proof split between them (below: every
@@ -210,24 +182,13 @@ struct zkhip_ctx {
     int ntt_single_max = 10;  // largest domain handled by one LDS-resident pass
     int ntt_max_sublog = 11;  // largest sub-transform of a pass (2^11 elements staged per sequence); domains above twice this take three passes
     int ntt_cols = 2;         // adjacent columns per workgroup of the cols pass (64-byte rows in HBM at 2)
-    int fold_hop = 0;         // the fold chain of a lane on a stream (hardware queue) of its own behind the accumulation: 0 never, 1 every lane,
-                              // 2 the G2 lane only (ZKHIP_FOLD_HOP).  A dispatch with workgroups still to place holds its queue's pipe; a fold
-                              // that shares the pipe of a later accumulation waits for that accumulation's last round.
-    int stream_skew = 0;      // streams made and left idle before a slot's lanes make theirs (ZKHIP_STREAM_SKEW): shifts which hardware queue a lane gets
-    std::vector<Stream> skew_streams;
+    std::vector<Stream> idle_streams;   // made and left idle: the fillers between the pipes of a stream plan (make_pipe_streams)
     std::string pipe_plan;    // which dispatcher ("pipe") each stream of a resident prover sits on (ZKHIP_PIPES; make_pipe_streams below)
     bool pipes_made = false;
     Stream ntt_lone_stream = 0;              // the witness map of a LONE proof ("n" of the plan), where the plan gives it a pipe of its own choosing
     bool ntt_lone_made = false;
-    Stream fold_shared[3] = {0, 0, 0};       // the fold streams of the lanes Z, G, H when the plan gives one per type
-    bool fold_shared_made[3] = {false, false, false};
     int ntt_fuse_first = 1;   // the first butterfly round of a pass done on the elements as they are fetched (kernels_ntt.cuh ntt_first_round; ZKHIP_NTT_FUSE_FIRST=0: every round through LDS)
-    int ntt_skew_us = 0;      // start skew of a transform pass's first round of workgroups (kernels_ntt.cuh NttSkew; ZKHIP_NTT_SKEW_US)
     u32 sort_wgs = 256;       // workgroups of a counting-sort pass (chunks x windows): fewer = longer runs per (workgroup, bucket)
-    int sort_two_level = 1;   // the placement pass of the sort in two levels (coarse bins of 256 buckets, then tiles: kernels_msm.cuh 1b); 0: round 5's
-                              // one-level k_msm_place (ZKHIP_SORT_TWO_LEVEL)
-    int sort_kh_log = 15;     // log2 of the counters of one sort workgroup's LDS histogram (ZKHIP_SORT_KH_LOG: development knob — a smaller
-                              // histogram leaves LDS to the kernels beside it and reads the digits once more per halving)
     int tenants = 1;          // contexts of one zkhip_multi that share this context's device (their keys are sized for a share of its memory)
     int nslots = 3;           // proofs in flight in the batch calls (<= ZK_NSLOTS; measured 2 / 3 / 4: 72.0 / 76.0 / 74.8 proofs/s)
     bool checked = false;     // zkhip_ctx_set_checked: the single-GPU prove calls test Az o Bz == Cz on the device and refuse a proof that fails
@@ -250,10 +211,10 @@ struct zkhip_ctx {
 // (tools/pipe_probe.hip, profiles/r6s_pipe_probe.txt).  A proof's fold chains, transforms and sorts are short kernels that
 // arrive while accumulations are being placed; which pipe their streams share with which accumulation used to be an accident
 // of the order of first use.  The plan names the pipe (0..3, relative to one another) of every stream of a resident prover:
-//   M main (staging, z sort)  N witness map + h sort  O copy-out  |  per slot: Z, G, H the lanes of A/B1/L, B2 and H;
-//   z, g, h a second stream of that lane TYPE for its fold chain (absent: the fold stays behind its accumulation);
-//   f one stream per slot for the fold chains of its three lanes; gl / zl / hl a fold stream of slot 0's lane used by LONE proofs only
-// e.g. "M=3,N=3,O=3,G=0,Z=1,H=2,g=3,z=3,h=3"; a name followed by a slot number ("G1=2") overrides that slot.  All streams of
+//   M main (staging, z sort)  N witness map + h sort  n a lone proof's witness map  O copy-out  |  per slot: Z, G, H the lanes of
+//   A/B1/L, B2 and H.  A lane's fold chain stays on the stream of its accumulation (second streams for the folds — per lane type,
+//   per slot, for lone proofs only — were measured and left out: profiles/r6r_fold_hop_and_stream_order_ab.txt, r6t_*, r6w_*)
+// e.g. "M=3,N=3,O=3,G=0,Z=1,H=2"; a name followed by a slot number ("G1=2") overrides that slot.  All streams of
 // the plan are made in one go, in pipe order (idle streams fill the gaps), the first time a proof is enqueued.
 // the plan of a resident prover (ZKHIP_TUNE_PIPE_PLAN = 1): found by a local search over the pipe of every stream, scored on four workloads at
 // once — dense 2^20 BN254, stdlib SHA-256 2^20, the Poseidon chain on BLS12-381 2^18, GM17 2^20 — batches AND lone proofs (tools/plan_search.py,
@@ -290,59 +251,31 @@ static inline void make_pipe_streams(zkhip_ctx* ctx) {
     if ((c = find("O")) >= 0 && !ctx->out_made) want.push_back({&ctx->out_stream, &ctx->out_made, false, c, false});
     static const char names[3] = {'Z', 'G', 'H'};
     static const int lane_of[3] = {0, 3, 4};
-    for (int t = 0; t < 3; ++t) {       // a fold stream per lane type ("g=3"), unless the plan names slots ("g0=3")
-        const std::string low(1, (char)(names[t] + 32));
-        if ((c = find(low)) >= 0 && find(low + "0") < 0) want.push_back({&ctx->fold_shared[t], &ctx->fold_shared_made[t], true, c, false});
-    }
     for (int k = 0; k < std::min(ctx->nslots, ZK_NSLOTS); ++k)
         for (int t = 0; t < 3; ++t) {
             MsmLane& lane = ctx->slots[k].lanes[lane_of[t]];
-            const std::string up(1, names[t]), low(1, (char)(names[t] + 32)), num = std::to_string(k);
-            c = find(up + num); if (c < 0) c = find(up);
+            const std::string up(1, names[t]);
+            c = find(up + std::to_string(k)); if (c < 0) c = find(up);
             if (c >= 0 && !lane.made) want.push_back({&lane.stream, &lane.made, t == 1 && ctx->g2_first, c, false});
-            c = find(low + num);
-            if (c >= 0 && !lane.fold_made) want.push_back({&lane.fold_stream, &lane.fold_made, true, c, false});
         }
-    for (int t = 0; t < 3; ++t) {       // slot 0's lanes in a LONE proof: "gl=3" — the fold of that lane hops to a stream of its own
-        MsmLane& lane = ctx->slots[0].lanes[lane_of[t]];
-        if ((c = find(std::string(1, (char)(names[t] + 32)) + "l")) >= 0 && !lane.lone_fold_made) want.push_back({&lane.lone_fold_stream, &lane.lone_fold_made, true, c, false});
-    }
-    for (int k = 0; k < std::min(ctx->nslots, ZK_NSLOTS); ++k) {
-        c = find("f" + std::to_string(k)); if (c < 0) c = find("f");
-        if (c >= 0 && !ctx->slots[k].fold_slot_made) want.push_back({&ctx->slots[k].fold_slot, &ctx->slots[k].fold_slot_made, true, c, false});
-    }
     size_t left = want.size();
     for (int t = 0; left; ++t) {
         PipeWant* pick = nullptr;
         for (auto& w : want) if (!w.done && w.cls == (t & 3)) { pick = &w; break; }
         if (pick) { *pick->target = pick->high ? stream_create_high_priority() : stream_create(); *pick->made = true; pick->done = true; --left; }
-        else ctx->skew_streams.push_back(stream_create_low_priority());      // (an idle queue of a priority nothing else uses)
+        else ctx->idle_streams.push_back(stream_create_low_priority());      // (an idle queue of a priority nothing else uses)
     }
-    for (int k = 0; k < ZK_NSLOTS; ++k)
-        if (ctx->slots[k].fold_slot_made)
-            for (int t = 0; t < 3; ++t) {
-                MsmLane& lane = ctx->slots[k].lanes[lane_of[t]];
-                if (!lane.fold_made) { lane.fold_stream = ctx->slots[k].fold_slot; lane.fold_made = true; lane.fold_owned = false; }
-            }
-    for (int t = 0; t < 3; ++t)
-        if (ctx->fold_shared_made[t])
-            for (int k = 0; k < ZK_NSLOTS; ++k) {
-                MsmLane& lane = ctx->slots[k].lanes[lane_of[t]];
-                if (!lane.fold_made) { lane.fold_stream = ctx->fold_shared[t]; lane.fold_made = true; lane.fold_owned = false; }
-            }
     ctx->ws = ctx->stream;
 }
 // streams and events of one proof slot, made the first time the slot is used
 static inline void slot_init(zkhip_ctx* ctx, ProofSlot& sl) {
     if (sl.ready) return;
-    while ((int)ctx->skew_streams.size() < ctx->stream_skew) ctx->skew_streams.push_back(stream_create());
     for (auto& so : sl.sorts) so.ready = event_create();
     for (int k = 0; k < ZK_NLANES; ++k) {
         // lane 3 is the G2 MSM: the longest accumulation AND the longest fold tail of a proof; at high priority its
         // workgroups are dispatched first, it finishes early and its tail hides under the G1 accumulations
         sl.lanes[k].high_priority = k == 3 && ctx->g2_first;       // (the stream itself is made when a launch first needs it: lane_stream)
         sl.lanes[k].done = event_create();
-        sl.lanes[k].acc_done = event_create();
         sl.acc_b[k] = event_create();
         sl.acc_e[k] = event_create();
     }
@@ -357,10 +290,6 @@ static inline void slot_init(zkhip_ctx* ctx, ProofSlot& sl) {
 static inline Stream lane_stream(MsmLane& lane) {
     if (!lane.made) { lane.stream = lane.high_priority ? stream_create_high_priority() : stream_create(); lane.made = true; }
     return lane.stream;
-}
-static inline Stream lane_fold_stream(MsmLane& lane) {
-    if (!lane.fold_made) { lane.fold_stream = stream_create_high_priority(); lane.fold_made = true; }
-    return lane.fold_stream;
 }
 static inline Stream ctx_out_stream(zkhip_ctx* ctx) {
     if (!ctx->out_made) { ctx->out_stream = stream_create(); ctx->out_made = true; }
@@ -569,12 +498,6 @@ static NttPlan<C>* get_plan(zkhip_ctx* ctx, int logN) {
     return pl;
 }
 
-// the start skew of a pass whose workgroups take `smem` bytes of LDS each: the first round = as many workgroups as the device holds
-static inline NttSkew ntt_skew(const zkhip_ctx* ctx, size_t smem) {
-    if (ctx->ntt_skew_us <= 0) return NttSkew{0, 0};
-    const u32 per_cu = (u32)std::max<size_t>(1, std::min<size_t>(4, (size_t)160 * 1024 / std::max<size_t>(smem, 1)));
-    return NttSkew{(u32)ctx->ntt_skew_us * 100u, (u32)ctx->cus * per_cu};
-}
 // `nvec` vectors of N elements, vec_stride elements apart, go through one launch (grid.y)
 // the pass over N1: columns of the N1 x Nb matrix
 template <class C>
@@ -582,7 +505,7 @@ static void ntt_cols(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool 
                      int canon = 0, const typename C::Fr* minus = nullptr) {
     typedef typename C::Fr Fr;
     ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3((unsigned)(pl->Nb / pl->C_cols), nvec), dim3(pl->threads_cols), pl->smem_cols, ctx->ws, data, vec_stride,
-              pl->log1, (u32)pl->Nb, pl->C_cols, ptr<u32>(pl->plan1[inverse ? 1 : 0]), pl->plen1, post, canon, minus, (u64)0, ~(u64)0, ntt_skew(ctx, pl->smem_cols), ctx->ntt_fuse_first);
+              pl->log1, (u32)pl->Nb, pl->C_cols, ptr<u32>(pl->plan1[inverse ? 1 : 0]), pl->plen1, post, canon, minus, (u64)0, ~(u64)0, ctx->ntt_fuse_first);
 }
 // three passes only — the pass over N2: columns of the N2 x N3 matrix of every outer index (grid.z).  `post_mask`: Nb - 1 for
 // the per-block twiddles, all ones for a table as long as the vector.
@@ -590,7 +513,7 @@ template <class C>
 static void ntt_mid(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool inverse, const typename C::Fr* post, u64 post_mask, int nvec, u64 vec_stride) {
     typedef typename C::Fr Fr;
     ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3(pl->N3 / pl->C_mid, nvec, pl->N1), dim3(pl->threads_mid), pl->smem_mid, ctx->ws, data, vec_stride,
-              pl->log2, pl->N3, pl->C_mid, ptr<u32>(pl->plan2[inverse ? 1 : 0]), pl->plen2, post, 0, (const Fr*)nullptr, pl->Nb, post_mask, ntt_skew(ctx, pl->smem_mid), ctx->ntt_fuse_first);
+              pl->log2, pl->N3, pl->C_mid, ptr<u32>(pl->plan2[inverse ? 1 : 0]), pl->plen2, post, 0, (const Fr*)nullptr, pl->Nb, post_mask, ctx->ntt_fuse_first);
 }
 // the pass over the last factor: contiguous sequences
 template <class C>
@@ -601,7 +524,7 @@ static void ntt_rows(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool 
     const int lg = three ? pl->log3 : pl->log2;
     ZK_LAUNCH((k_ntt_rows<typename Fr::Params>), dim3((unsigned)((pl->N >> lg) / pl->R_rows), nvec), dim3(pl->threads_rows), pl->smem_rows, ctx->ws, data, vec_stride,
               lg, pl->R_rows, ptr<u32>((three ? pl->plan3 : pl->plan2)[inverse ? 1 : 0]), three ? pl->plen3 : pl->plen2, post, canon, minus, post_mask,
-              ntt_skew(ctx, pl->smem_rows), ctx->ntt_fuse_first);
+              ctx->ntt_fuse_first);
 }
 // natural order in -> sigma order out
 template <class C>
@@ -736,13 +659,13 @@ static inline void msm_prepare(zkhip_ctx* ctx, Stream s, MsmSort& so, const u32*
     // global atomics (one per touched bucket per workgroup) well below one per digit
     // (a window of more than 16 bits has more buckets than one histogram holds: its workgroups come in `halves`, each reading the
     // chunk's digits and keeping the ones of its own range of buckets)
-    const u32 kh = std::min(sh.K, std::min(MSM_SORT_MAX_KH, 1u << ctx->sort_kh_log)), halves = sh.K / kh;
+    const u32 kh = std::min(sh.K, MSM_SORT_MAX_KH), halves = sh.K / kh;
     const u64 want_chunks = halves > 1 ? std::max<u64>(1, ctx->sort_wgs / (sh.W * halves)) : std::max<u64>(1, (ctx->sort_wgs + sh.W - 1) / sh.W);
     const u64 max_chunks = std::max<u64>(1, sh.n / (2 * (u64)kh));
     const u64 sort_chunks = std::min(want_chunks, max_chunks);
     const u64 chunk = (sh.n + sort_chunks - 1) / sort_chunks;
     const size_t hist_bytes = (size_t)kh * 4;
-    const bool two_level = ctx->sort_two_level && sh.K >= (1u << MSM_COARSE_BITS) && sh.K <= (1u << 16);
+    const bool two_level = sh.K >= (1u << MSM_COARSE_BITS) && sh.K <= (1u << 16);
     const u32 nbins = (u32)(nk >> MSM_COARSE_BITS);
     so.cnt.ensure(nk * 4);
     so.cursor.ensure(nk * 4);
@@ -1747,7 +1670,6 @@ struct Prover {
         host_sums(sl, Wmax);
         Xyzz<Fq>* hs1 = (Xyzz<Fq>*)sl.h_ws;                    // the host mirrors of ws1 / ws2: every lane copies its own sums out
         Xyzz<Fq2>* hs2 = (Xyzz<Fq2>*)((uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        const int lone_sched = (lone && !ctx->serial) ? ctx->lone_sched : 0;
         // An accumulation kernel is sized to fill the machine, saturates the integer multiplier and nothing preempts it:
         // whatever arrives beside it waits for a place or crawls (kernel traces, profiles/r2_single_proof_traces.md: a
         // 0.14 ms mat-vec took 4 ms, a 0.2 ms transform pass 3 ms), h arrives late and the H MSM trails alone behind
@@ -1759,19 +1681,12 @@ struct Prover {
         if (pk->z_n) {
             msm_prepare(ctx, st, sl.sorts[0], (const u32*)d_scalars + pk->z_lo * 8, shz, pk->z_n);
             if (pk->thin_mask) msm_prepare(ctx, st, sl.sorts[2], (const u32*)d_scalars + pk->z_lo * 8, shz, pk->z_n, ptr<u32>(pk->thin_keep), &sl.sorts[0]);
-            if (gate < 2) {
-                sl.lanes[3].share_cu = (lone_sched & 1) != 0;
-                sl.lanes[3].lone_launch = lone;
-                msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], nullptr, hs2);   // longest first
-            }
+            if (gate < 2) msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], nullptr, hs2);   // longest first
         }
 
         // ---- K1-K4 and the h-sort, on the NTT stream: the main stream is free for the next proof's staging and z-sort
         Stream wn = ctx->serial ? st : slot_ntt_stream(ctx, sl);
         stream_wait_event(wn, sl.ev[0]);
-        // (lone_sched bit 4: a lone proof's witness map waits for the sort of the assignment — the sort's kernels have the machine to
-        // themselves and the G2 accumulation starts that much sooner; the witness map then runs beside it)
-        if ((lone_sched & 4) && pk->z_n) stream_wait_event(wn, sl.sorts[0].ready);
         event_record(sl.ev[1], wn);
         ctx->ws = wn;
         witness_map(ctx, cs, pl, bound, half, sl.check_idx >= 0);
@@ -1792,7 +1707,6 @@ struct Prover {
         Xyzz<Fq>* ws1 = ptr<Xyzz<Fq>>(sl.ws1);
         Xyzz<Fq>* hs1 = (Xyzz<Fq>*)sl.h_ws;
         Xyzz<Fq2>* hs2 = (Xyzz<Fq2>*)((uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        const int lone_sched = (lone && !ctx->serial) ? ctx->lone_sched : 0;
         const int gate = z_gate(ctx);
         const MsmSort& sort_b = (pk->thin_mask & 8) ? sl.sorts[2] : sl.sorts[0];
         const bool inf_b2 = (pk->thin_mask & 8) ? pk->inf_many_thin[3] : pk->inf_many[3];
@@ -1806,15 +1720,9 @@ struct Prover {
         }
         event_record(sl.ev[2], wn);
 
-        // (lone_sched bit 2: the h sort goes out BEFORE the G1 lanes over z, which then wait for it — it runs beside the G2 lane alone)
-        const bool h_sort_first = (lone_sched & 2) != 0 && pk->h_n && gate;
-        if (h_sort_first) msm_prepare(ctx, wn, sl.sorts[1], h_scalars + pk->h_lo * 8, shh, pk->h_n);
         if (pk->z_n) {
-            const Event h_ready = !gate ? nullptr : h_sort_first ? sl.sorts[1].ready : sl.ev[2];
-            if (gate >= 2) {
-                sl.lanes[3].lone_launch = lone;
-                msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], h_ready, hs2);
-            }
+            const Event h_ready = gate ? sl.ev[2] : nullptr;
+            if (gate >= 2) msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], h_ready, hs2);
             // A G2 accumulation at one wave per SIMD (BLS12-381: the wave takes the SIMD's whole register file) shares no SIMD with a
             // G1 wave: G1 workgroups that arrive while some of its workgroups are still waiting for a place take the places, and the
             // G2 lane — the longest chain of such a proof — finishes that much later.  The witness map used to be the head start; a
@@ -1829,7 +1737,6 @@ struct Prover {
                 event_record(sl.g1_go, st);
                 g1_after = sl.g1_go;
             }
-            if (lone) sl.lanes[0].lone_launch = sl.lanes[1].lone_launch = sl.lanes[2].lone_launch = true;
             run_z_g1(ctx, sl, pk, shz, ws1, Wmax, g1_after, bound, hs1);
         } else {
             empty_msm(ctx, sl, ws1, 3 * Wmax, ptr<Xyzz<Fq2>>(sl.ws2), Wmax, 0, 4);
@@ -1837,9 +1744,8 @@ struct Prover {
 
         // ---- H = MSM(h_query, h) in sigma order (the zero-padded tail pairs with infinity bases)
         if (pk->h_n) {
-            if (!h_sort_first) msm_prepare(ctx, wn, sl.sorts[1], h_scalars + pk->h_lo * 8, shh, pk->h_n);
+            msm_prepare(ctx, wn, sl.sorts[1], h_scalars + pk->h_lo * 8, shh, pk->h_n);
             // (a bound key: U in natural order against H' — the same MSM machinery, other bases)
-            if (lone) sl.lanes[4].lone_launch = true;
             msm_run<Fq>(ctx, sl.lanes[4], sl.sorts[1], bound ? pk->h_bound.p : pk->h_sigma.p, with_inf(shh, bound ? pk->inf_many_bound[1] : pk->inf_many[4]),
                         ws1 + 3 * Wmax, sl.acc_b[3], sl.acc_e[3], nullptr, hs1 + 3 * Wmax);
         } else {

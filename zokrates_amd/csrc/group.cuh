@@ -49,11 +49,7 @@ void msm_run_tables(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void
     const int wpe = ctx->msm_waves ? ctx->msm_waves : (nt > 1 ? std::max(1, (ctx->msm_fused_waves ? ctx->msm_fused_waves : MsmTuning<F>::FUSED_WPE)) : single);
     const u64 machine = ctx->msm_lanes ? (u64)ctx->msm_lanes : (u64)ctx->cus * 4 * 64 * wpe / (nt > 1 && !ctx->msm_waves ? nt : 1);
     const u32 nlanes = (u32)std::max<u64>(1, std::min<u64>(machine, (sh.n * (u64)sh.W + ctx->msm_min_slice - 1) / ctx->msm_min_slice));
-    const bool share = lane.share_cu && !ctx->serial;
-    lane.share_cu = false;
-    const bool lone_launch = lane.lone_launch;
-    lane.lone_launch = false;
-    const MsmCut cut{nlanes, ctx->msm_min_slice, (u32)std::min<u64>(sh.n * (u64)sh.levels, 0x7fffffffu), share ? 1u : 0u};
+    const MsmCut cut{nlanes, ctx->msm_min_slice, (u32)std::min<u64>(sh.n * (u64)sh.levels, 0x7fffffffu)};
     const u64 partial_stride = (u64)sh.nkeys + nlanes;
     lane.heavy.ensure(((size_t)sh.nkeys + 1) * 4);            // [0] = count, [1..] = keys
     lane.lane_key.ensure((size_t)nlanes * 4);
@@ -71,9 +67,7 @@ void msm_run_tables(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void
               ptr<u32>(lane.heavy));
     if (accum_after && !ctx->serial) stream_wait_event(s, accum_after);   // (the slicing above only needs the sort)
     if (ev_begin) event_record(ev_begin, s);
-    // (share: padded beyond half of the CU's 160 KiB, so that a second workgroup of this launch does not fit beside the first — the
-    // other half of the LDS and of the registers stays free for whatever else arrives)
-    const size_t acc_lds = share ? std::max<size_t>(msm_accum_lds_bytes<F>(), (size_t)84 * 1024) : msm_accum_lds_bytes<F>();
+    const size_t acc_lds = msm_accum_lds_bytes<F>();
     if (ctx->skip_inf_mode == 1 || (ctx->skip_inf_mode == 0 && sh.skip_inf)) {
         if (acc_lds > 64 * 1024) lds_opt_in(ctx, (const void*)k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, true>);
         ZK_LAUNCH((k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, true>), dim3(blocks_for(nlanes, T), nt), dim3(T), acc_lds, s, tables, ptr<u32>(so.off), ptr<u32>(so.sorted),
@@ -84,40 +78,22 @@ void msm_run_tables(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void
                   ptr<u32>(lane.lane_key), ptr<Xyzz<F>>(lane.partial), partial_stride, sh.nkeys, cut);
     }
     if (ev_end) event_record(ev_end, s);
-    // the fold chain on another stream (hardware queue) than the accumulation: a lone proof's — only where the stream plan made the lane
-    // a lone fold stream (the hop is an event on the proof's critical path); a batch's — the lane's fold stream of the plan, or zkhip_ctx::fold_hop
-    // (a lone proof's G2 lane — the first to finish, its fold chain the longest — also takes the lane's batch fold stream: 10.3-10.9 ms without, 9.7-9.9 with)
-    const bool lone_hop = lone_launch && (lane.lone_fold_made || (MsmTuning<F>::IS_EXT && lane.fold_made));
-    if (!ctx->serial && (lone_launch ? lone_hop : (lane.fold_made || ctx->fold_hop == 1 || (ctx->fold_hop == 2 && MsmTuning<F>::IS_EXT)))) {
-        event_record(lane.acc_done, s);
-        s = (lone_launch && lane.lone_fold_made) ? lane.lone_fold_stream : lane_fold_stream(lane);
-        stream_wait_event(s, lane.acc_done);
-    }
+    // (the fold chain stays on the stream of its accumulation)
     if (ctx->heavy_runs) {
         lds_opt_in(ctx, (const void*)k_msm_heavy_reduce<F>);
-        const unsigned TH = (unsigned)ctx->heavy_threads;
+        const unsigned TH = MSM_HEAVY_THREADS;
         ZK_LAUNCH((k_msm_heavy_reduce<F>), dim3(MSM_HEAVY_CHUNKS, nt), dim3(TH), (size_t)TH * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.partial), partial_stride,
                   ptr<u32>(so.off), sh.nkeys, cut, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy));
     }
     FoldDigits digs{};
-    const u32 widest = std::max(sh.H, sh.Lw);
-    if ((ctx->fold_lines == 1 || (ctx->fold_lines == 2 && nt == 1)) && widest <= 256) {
-        // rows and columns of the bucket matrix in ONE launch (kernels_msm.cuh 5a')
-        const unsigned TL = std::max<u32>(64, widest);
-        lds_opt_in(ctx, (const void*)k_msm_fold_lines<F>);
-        ZK_LAUNCH((k_msm_fold_lines<F>), dim3(widest, sh.sets * 2, nt), dim3(TL), (size_t)TL * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.partial), partial_stride,
-                  ptr<u32>(so.off), sh.nkeys, cut, sh.K, sh.Lw, sh.H, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy), ctx->heavy_runs ? 1u : 0u,
-                  ptr<Xyzz<F>>(lane.rows), ptr<Xyzz<F>>(lane.cols));
-    } else {
-        ZK_LAUNCH((k_msm_fold_rows<F>), dim3(sh.H, sh.sets, nt), dim3(sh.Lw), (size_t)sh.Lw * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.partial), partial_stride,
-                  ptr<u32>(so.off), sh.nkeys, cut, sh.K, sh.Lw, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy), ctx->heavy_runs ? 1u : 0u, ptr<Xyzz<F>>(lane.bucket),
-                  ptr<Xyzz<F>>(lane.rows));
-        // column sums of the K = H x Lw buckets of a set; work-item (lo, hg) adds RG / HG rows serially
-        const u32 RG = sh.H;
-        const u32 HG = std::max<u32>(1, std::min<u32>((u32)ctx->fold_hg, RG)), CW = std::min<u32>(sh.Lw, 256 / HG), NG = sh.H / RG;
-        ZK_LAUNCH((k_msm_fold_cols<F>), dim3(sh.Lw / CW, sh.sets * NG, nt), dim3(CW, HG), (size_t)CW * HG * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.bucket), (u64)sh.K,
-                  (u64)sh.nkeys, sh.Lw, sh.H, RG, ptr<Xyzz<F>>(lane.cols));
-    }
+    ZK_LAUNCH((k_msm_fold_rows<F>), dim3(sh.H, sh.sets, nt), dim3(sh.Lw), (size_t)sh.Lw * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.partial), partial_stride,
+              ptr<u32>(so.off), sh.nkeys, cut, sh.K, sh.Lw, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy), ctx->heavy_runs ? 1u : 0u, ptr<Xyzz<F>>(lane.bucket),
+              ptr<Xyzz<F>>(lane.rows));
+    // column sums of the K = H x Lw buckets of a set; work-item (lo, hg) adds RG / HG rows serially
+    const u32 RG = sh.H;
+    const u32 HG = std::max<u32>(1, std::min<u32>((u32)ctx->fold_hg, RG)), CW = std::min<u32>(sh.Lw, 256 / HG), NG = sh.H / RG;
+    ZK_LAUNCH((k_msm_fold_cols<F>), dim3(sh.Lw / CW, sh.sets * NG, nt), dim3(CW, HG), (size_t)CW * HG * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.bucket), (u64)sh.K,
+              (u64)sh.nkeys, sh.Lw, sh.H, RG, ptr<Xyzz<F>>(lane.cols));
     digs.d[0] = FoldDigit{lane.cols.p, sh.Lw, 1, 0};
     digs.d[1] = FoldDigit{lane.rows.p, sh.H, 0, (u32)ilog2_floor(sh.Lw)};
     // the scan form of the last fold step: one workgroup of <= 256 work-items per digit; the double-and-add form (two digits

@@ -607,8 +607,7 @@ static __global__ void k_scan_add(u32* __restrict__ off, const u32* __restrict__
 // The list (length total = off[nkeys], known only on the device) is cut into nlanes slices of P = max(ceil(total / nlanes),
 // min_slice) entries: with nlanes = the number of work-items the machine holds, every work-item of the accumulation
 // kernel does the same number of additions in ONE round of workgroups, whatever the scalars look like.
-struct MsmCut { u32 nlanes, min_slice; u32 table_len; u32 prio; };   // table_len: entries of a base table (levels x points), for the checked build;
-                                                                      // prio: the accumulation's waves raise their issue priority (a lone proof's G2 lane: core.cuh lone_sched)
+struct MsmCut { u32 nlanes, min_slice; u32 table_len; };   // table_len: entries of a base table (levels x points), for the checked build
 static __device__ __forceinline__ u32 msm_slice_len(const u32* __restrict__ off, u32 nkeys, MsmCut cut) {
     const u32 total = off[nkeys];
     const u32 P = (total + cut.nlanes - 1) / cut.nlanes;
@@ -688,9 +687,6 @@ template <class F, int WPE, bool SKIP_INF>
 __global__ void __launch_bounds__(256, WPE) k_msm_accum(MsmTables tables, const u32* __restrict__ off, const u32* __restrict__ sorted,
                                                     const u32* __restrict__ lane_key, Xyzz<F>* __restrict__ partial, u64 partial_stride, u32 nkeys, MsmCut cut) {
     constexpr int NW2 = 2 * AffPacked<F>::NW;
-#ifndef ZK_EMU
-    if (cut.prio) __builtin_amdgcn_s_setprio(2);       // (wave-uniform: a kernel argument)
-#endif
     const AffPacked<F>* __restrict__ bases = (const AffPacked<F>*)tables.p[blockIdx.y];   // blockIdx.y: which MSM of the launch
     partial += (u64)blockIdx.y * partial_stride;
     const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -907,6 +903,12 @@ __device__ __forceinline__ Xyzz<F> xyzz_mul_small(const Xyzz<F>& p, u32 k) {
 //     into MSM_HEAVY_CHUNKS runs, workgroup c sums run c of every heavy bucket into the run's first slot, and the row's
 //     workgroup below only adds the run heads.  With an empty list the kernel returns at once.
 static constexpr u32 MSM_HEAVY_CHUNKS = 64;
+// work-items per workgroup of k_msm_heavy_reduce.  The kernel is launched whether or not a heavy bucket exists (the list is on the
+// device) and must find a place before it can return: one wave and 9 / 18 KB of LDS (G1 / G2) instead of four and 36 / 73 at 256 is a
+// place found sooner beside the accumulations, and a run of a heavy bucket is 8 serial additions + 6 tree levels instead of 2 + 8.
+// Lone dense proofs: median 9.61 against 9.78 ms over three processes of 40 each, the stdlib SHA-256 circuit (which HAS heavy
+// buckets) and the others level (profiles/r7s_*, r7q_*)
+static constexpr unsigned MSM_HEAVY_THREADS = 64;
 struct HeavyRun {
     u32 g0, g1, len;     // the bucket's lanes [g0, g1], lanes per run
 };
@@ -974,56 +976,6 @@ __global__ void __launch_bounds__(256, MsmTuning<F>::COLD_WPE) k_msm_fold_rows(X
     sh[lo] = v;
     block_tree_sum<F>(sh);
     if (lo == 0) rows[(u64)j * gridDim.x + hi] = sh[0];
-}
-// 5a'. rows AND columns in one launch (H, Lw <= 256: every resident key).  The column sums do not need the row pass: a workgroup
-//     per LINE of the H x Lw bucket matrix — blockIdx.y = 2 set + dir; dir 0: row blockIdx.x, one work-item per lo; dir 1: column
-//     blockIdx.x, one work-item per hi — combines its buckets' partials and tree-sums them; the bucket values are computed twice
-//     (a few additions per bucket, against the ~240 that made it) and never stored.  One kernel and 3-5 + 8 dependent additions
-//     where round 5 ran two (rows, then columns over the stored bucket values: 8 serial + 5 tree levels more) — the fold is a chain
-//     of dependent additions at the end of every MSM, and at the end of a lone proof nothing hides it.
-//     Heavy buckets: the whole workgroup sums the bucket's partials (or the run heads k_msm_heavy_reduce left) and hands the total
-//     to the bucket's work-item through LDS — nothing is written back, the other direction's workgroup reads the same slots.
-template <class F>
-__global__ void __launch_bounds__(256, MsmTuning<F>::COLD_WPE) k_msm_fold_lines(const Xyzz<F>* __restrict__ partial, u64 partial_stride, const u32* __restrict__ off, u32 nkeys,
-                                                                                MsmCut cut, u32 K, u32 Lw, u32 H, const u32* __restrict__ heavy_list,
-                                                                                const u32* __restrict__ heavy_count, u32 heavy_runs, Xyzz<F>* __restrict__ rows,
-                                                                                Xyzz<F>* __restrict__ cols) {
-    ZK_PRIO_HIGH();
-    ZK_DYN_SMEM(smem);
-    Xyzz<F>* sh = (Xyzz<F>*)smem;
-    const u32 sets = gridDim.y >> 1, j = blockIdx.y >> 1, dir = blockIdx.y & 1u, line = blockIdx.x, t = threadIdx.x;
-    const u32 len = dir ? H : Lw, nlines = dir ? Lw : H;       // work-items of this line, lines of this direction
-    if (line >= nlines) return;                                // (uniform: the grid is max(H, Lw) wide)
-    partial += (u64)blockIdx.z * partial_stride;               // blockIdx.z: which MSM of the launch
-    const u32 P = msm_slice_len(off, nkeys, cut);
-    const u32 set0 = j * K;
-    const bool live = t < len;
-    const u32 key = set0 + (dir ? t * Lw + line : line * Lw + t);
-    Xyzz<F> v = Xyzz<F>::inf();
-    bool have = !live;
-    const u32 nh = *heavy_count;
-    for (u32 h = 0; h < nh; ++h) {
-        const u32 hk = heavy_list[h];
-        const u32 rel = hk - set0;                             // (unsigned: a key of another set wraps far beyond K)
-        if (rel >= K || (dir ? rel % Lw : rel / Lw) != line) continue;     // (uniform over the workgroup)
-        const HeavyRun r = msm_heavy_run(off, hk, P);
-        const u32 step = heavy_runs ? r.len : 1;               // heavy_runs: k_msm_heavy_reduce left one sum per run, at the run's first slot
-        Xyzz<F> s = Xyzz<F>::inf();
-        for (u64 g = r.g0 + (u64)t * step; g <= r.g1; g += (u64)blockDim.x * step) xyzz_add_from(s, &partial[(u64)hk + g]);
-        sh[t] = s;
-        block_tree_sum_reg<F>(sh, s, blockDim.x);
-        if (t == 0) sh[0] = s;
-        __syncthreads();
-        if (live && key == hk) { v = sh[0]; have = true; }
-        __syncthreads();
-    }
-    if (!have) {
-        ZK_ASSERT_IDX(key < nkeys && (u64)key + (off[key + 1] ? (off[key + 1] - 1) / P : 0) < partial_stride);
-        v = msm_bucket_sum<F>(partial, off, key, P);
-    }
-    sh[t] = v;
-    block_tree_sum_reg<F>(sh, v, blockDim.x);
-    if (t == 0) (dir ? cols : rows)[((u64)blockIdx.z * sets + j) * nlines + line] = v;
 }
 // 5b. column sums: work-item (lo, hg) adds its share of the rows serially, then the HG shares are tree-added.
 //     blockDim = (CW, HG); grid = (Lw / CW, sets * NG, MSMs of the launch).  The H rows of a set are cut into NG = H / RG groups

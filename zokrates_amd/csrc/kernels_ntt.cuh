@@ -635,26 +635,6 @@ static __device__ __forceinline__ void ntt_tile_of(u32& tile, u32& vec) {
         vec = r >> 3;
     }
 }
-// Start skew.  A pass is load -> five butterfly rounds -> store per workgroup, and a launch over a 2^20 domain is exactly TWO rounds
-// of workgroups (the machine's LDS holds half the elements): dispatched together, every workgroup of a round loads at the same time
-// (a 32 MiB burst: ~7 us with the multipliers idle), computes at the same time (HBM idle), stores at the same time — the memory
-// phases and the arithmetic of a pass add up instead of overlapping (46 us of VALU issue + 18 us of HBM time = the 64 us per
-// pass-vector of rounds 3-5).  So the workgroups of the FIRST round (linear number < first_round) wait a pseudo-random time below
-// `skew_ticks` (wall clock, 10 ns) before they load: co-resident workgroups drift apart, one's loads land under the other's
-// butterflies, and the drift carries into the second round.  A scheduling aid: 0 = off (ZKHIP_TUNE_NTT_SKEW_US), no effect on results.
-struct NttSkew { u32 ticks, first_round; };
-static __device__ __forceinline__ void ntt_start_skew(NttSkew sk) {
-#ifndef ZK_EMU
-    if (!sk.ticks) return;
-    const u32 L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (L >= sk.first_round) return;
-    const u32 d = ((L * 2654435761u) >> 12) % sk.ticks;
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < d) __builtin_amdgcn_s_sleep(4);
-#else
-    (void)sk;
-#endif
-}
 // "cols" pass: the matrix is n1 x n2 row-major; this workgroup owns columns [c0, c0 + C).  grid.y = vectors
 // (consecutive vectors are vec_stride elements apart).
 // workgroups of 512 work-items per CU the transform kernels are compiled for (4: 64 VGPRs, a few spilled; 3: 85 VGPRs)
@@ -667,11 +647,10 @@ static __device__ __forceinline__ void ntt_start_skew(NttSkew sk) {
 template <class P>
 __global__ void __launch_bounds__(512, ZK_NTT_WGS_PER_CU) k_ntt_cols(Fe<P>* __restrict__ data_, u64 vec_stride, int log_n1, u32 n2, int C, const u32* __restrict__ plan,
                                                      u32 plen, const Fe<P>* __restrict__ post_, int canon, const Fe<P>* __restrict__ minus_ = nullptr,
-                                                     u64 batch_stride = 0, u64 post_mask = ~(u64)0, NttSkew skew = NttSkew{0, 0}, int fuse_first = 1) {
+                                                     u64 batch_stride = 0, u64 post_mask = ~(u64)0, int fuse_first = 1) {
     ZK_PRIO_HIGH();
     ZK_DYN_SMEM(smem);
     static_assert(P::N == 8, "Fr is 8 x 32-bit words");
-    ntt_start_skew(skew);
     u32* lds = (u32*)smem;
     u32 tile, vec;
     ntt_tile_of(tile, vec);
@@ -736,10 +715,9 @@ __global__ void __launch_bounds__(512, ZK_NTT_WGS_PER_CU) k_ntt_cols(Fe<P>* __re
 template <class P>
 __global__ void __launch_bounds__(512, ZK_NTT_WGS_PER_CU) k_ntt_rows(Fe<P>* __restrict__ data_, u64 vec_stride, int log_n2, int R, const u32* __restrict__ plan, u32 plen,
                                                      const Fe<P>* __restrict__ post_, int canon, const Fe<P>* __restrict__ minus_ = nullptr,
-                                                     u64 post_mask = ~(u64)0, NttSkew skew = NttSkew{0, 0}, int fuse_first = 1) {
+                                                     u64 post_mask = ~(u64)0, int fuse_first = 1) {
     ZK_PRIO_HIGH();
     ZK_DYN_SMEM(smem);
-    ntt_start_skew(skew);
     u32* lds = (u32*)smem;
     u32 tile, vec;
     ntt_tile_of(tile, vec);
