@@ -123,6 +123,68 @@ def run_device_checks(ctx, curve, n, seed, kind="dense", extra_public=0, verify=
     return cs, z, dcs, pk, raw
 
 
+_long_batch = {}
+
+
+def long_batch_case():
+    """The circuit, key bytes, seven blinding triples (one with r + d1 == 0) and the closed-form proofs of run_long_batch_checks:
+    computed once, shared by the emulator and the GPU test, read only."""
+    if not _long_batch:
+        from oracle import cpu
+        curve = BN254
+        cs, z = circuit(curve, 7, 71, extra_public=1)
+        mats = [csr_of(cs.A), csr_of(cs.B), csr_of(cs.C)]
+        oc = cpu.Circuit.from_csr(curve.curve_id, cs.n, cs.l, cs.w, mats)
+        tb = cpu.gm17_toxic_bytes(gm17.Toxic.from_seed(curve))
+        raw = cpu.Gm17ProvingKey.setup(oc, tb).serialize()
+        rnd = random.Random(71)
+        rnds = [tuple(rnd.randrange(curve.r) for _ in range(3)) for _ in range(7)]
+        rnds[5] = (rnds[5][0], rnds[5][1], curve.r - rnds[5][0])
+        assert len(set(rnds)) == 7 and len({(d1 + r_) % curve.r for d1, _, r_ in rnds}) == 7
+        want = [cpu.gm17_trapdoor(oc, tb, le(z), d1, r_) for d1, _, r_ in rnds]
+        zbad = list(z)
+        zbad[-1] = (zbad[-1] + 1) % curve.r                      # the last wire: only the last row's C mentions it
+        dot = lambda row, v: sum(c * v[j] for j, c in row)
+        bad = [i for i in range(cs.n) if (dot(cs.A[i], zbad) * dot(cs.B[i], zbad) - dot(cs.C[i], zbad)) % curve.r]
+        assert bad == [cs.n - 1] and cs.is_satisfied(z, curve.r)
+        _long_batch.update(cs=cs, mats=mats, raw=raw, rnds=rnds, want=want, zb=le(z), zbad=le(zbad), bad_row=bad[0])
+    return _long_batch
+
+
+def run_long_batch_checks(ctx):
+    """A resident batch of 2 * nslots + 1 = 7 proofs: every slot is used again within one call, twice.  Each proof against the closed
+    form; over the key as loaded and over the bound key; three proofs in flight and one.  Then checked mode: proof 4 of the 7 with one
+    broken row is named, alone, the other six are written, and the unchecked batch right behind it succeeds."""
+    case = long_batch_case()
+    cs, rnds, want = case["cs"], case["rnds"], case["want"]
+    dcs = native.ConstraintSystem(ctx, 0, cs.n, cs.l, cs.w, case["mats"])
+    pk = native.ProvingKey(ctx, 0, case["raw"], scheme="gm17")
+    za, zbad = native.Assignment(ctx, dcs, case["zb"]), native.Assignment(ctx, dcs, case["zbad"])
+    try:
+        for bound in (False, True):
+            if bound:
+                pk.bind(dcs)
+                assert pk.is_bound(dcs)
+            for slots in (3, 1):
+                ctx.tune("slots", slots)
+                assert native.prove_gm17_resident_batch(ctx, pk, dcs, [za] * 7, rnds)[0] == want, (bound, slots)
+            ctx.tune("slots", 3)
+            assert ctx.set_checked(True) is False
+            with pytest.raises(native.ZkhipError) as e:
+                native.prove_gm17_resident_batch(ctx, pk, dcs, [za] * 4 + [zbad] + [za] * 2, rnds)
+            assert e.value.code == -5 and e.value.unsatisfied == ctx.unsatisfied() == [(4, case["bad_row"], 1)], bound
+            assert "proof 4 of 7: constraint %d of %d is not satisfied (1 in all)" % (case["bad_row"], cs.n) in str(e.value)
+            assert e.value.proofs[:4] + e.value.proofs[5:] == want[:4] + want[5:] and e.value.proofs[4] == bytes(len(want[4])), bound
+            assert ctx.set_checked(False) is True
+            assert native.prove_gm17_resident_batch(ctx, pk, dcs, [za] * 7, rnds)[0] == want, bound
+            assert ctx.unsatisfied() == []
+    finally:
+        ctx.set_checked(False)
+        ctx.tune("slots", 3)
+        for h in (za, zbad, pk, dcs):
+            h.close()
+
+
 def run_error_checks(ctx):
     curve = BN254
     cs, z, dcs, pk, raw = run_device_checks(ctx, curve, 5, 31, verify=False, light=True)
@@ -182,6 +244,22 @@ def test_emu_gm17_errors(emu_ctx):
     run_error_checks(emu_ctx)
 
 
+def test_emu_gm17_batch_longer_than_the_slots(emu_ctx):
+    run_long_batch_checks(emu_ctx)
+
+
+def test_slot_sums_layout_host(tmp_path):
+    """tests/host/slot_sums_layout.cpp under ASan + UBSan: the layout of a slot's window sums (SlotSums, shared by both provers),
+    every accessor written through to the last byte of buffers of exactly the stated sizes.  A stand-alone program on the CPU."""
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "slot_sums_layout")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DZK_EMU", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(here, "..", "zokrates_amd", "csrc"), os.path.join(here, "host", "slot_sums_layout.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "0 failures" in out.stdout, out.stdout + out.stderr
+
+
 # ------------------------------------------------------------------ GPU parity
 @pytest.fixture(scope="module")
 def gpu_ctx():
@@ -206,6 +284,11 @@ def test_gpu_gm17_two_pass(gpu_ctx):
 @pytest.mark.gpu
 def test_gpu_gm17_errors(gpu_ctx):
     run_error_checks(gpu_ctx)
+
+
+@pytest.mark.gpu
+def test_gpu_gm17_batch_longer_than_the_slots(gpu_ctx):
+    run_long_batch_checks(gpu_ctx)
 
 
 @pytest.mark.gpu

@@ -893,6 +893,49 @@ struct zkhip_assignment {
 
 namespace zk {
 
+// ------------------------------------------------------------------ the window sums of a proof slot
+// What the five lanes of a proof over `pk` leave, and where: `G1 ws1[4][Wmax]` (A, B1, L over z; H over h) and `G2 ws2[Wmax]` (B2) on
+// the device, and the slot's pinned record on the host — a mirror of both (every lane copies its own sums out), the word of the
+// canonical check behind them and, 8 bytes on, the 16-byte verdict of checked mode.  The only place that knows this layout.
+template <class C>
+struct SlotSums {
+    typedef Xyzz<typename C::Fq> G1;
+    typedef Xyzz<typename C::Fq2> G2;
+    MsmShape shz, shh;   // the MSMs over z / over h
+    int Wmax;            // sums per MSM (2: the tables carry the window multiples)
+    // (a sharded key covers only its index range of the bases; the shapes are recomputed from the key's own (c, sets): a key whose
+    // numbers this build cannot run is refused, never paired with a sort of another window width)
+    SlotSums(const zkhip_ctx* ctx, const zkhip_pk* pk)
+        : shz(msm_shape(ctx, pk->z_n, C::Fr::Params::BITS, true, pk->c_z, pk->s_z)), shh(msm_shape(ctx, pk->h_n, C::Fr::Params::BITS, true, pk->c_h, pk->s_h)) {
+        require(shz.c == pk->c_z && shh.c == pk->c_h && (int)shz.sets == pk->s_z && (int)shh.sets == pk->s_h, ZKHIP_ERR_BAD_ARG,
+                "the key's tables were built for a window width this build cannot sort: reload the key");
+        Wmax = (int)std::max(shz.nsums(), shh.nsums());
+    }
+    size_t b1() const { return (size_t)4 * Wmax * sizeof(G1); }
+    size_t b2() const { return (size_t)Wmax * sizeof(G2); }
+    size_t lane_bytes() const { return (size_t)Wmax * sizeof(G1); }
+    size_t record_bytes() const { return b1() + b2() + 24; }
+    template <class T> T* lane(T* g1_sums, int k) const { return g1_sums + (size_t)k * Wmax; }   // MSM k of 4 x Wmax G1 sums, wherever they are
+    G1* ws1(const ProofSlot& sl, int k) const { return lane(ptr<G1>(sl.ws1), k); }
+    G2* ws2(const ProofSlot& sl) const { return ptr<G2>(sl.ws2); }
+    G1* hs1(const ProofSlot& sl, int k) const { return lane((G1*)sl.h_ws, k); }
+    G2* hs2(const ProofSlot& sl) const { return (G2*)((uint8_t*)sl.h_ws + b1()); }
+    uint8_t* zflag(const ProofSlot& sl) const { return (uint8_t*)sl.h_ws + b1() + b2(); }
+    uint8_t* verdict(const ProofSlot& sl) const { return zflag(sl) + 8; }
+    u32 zflag_word(const ProofSlot& sl) const { u32 f; memcpy(&f, zflag(sl), 4); return f; }
+    // the slot's buffers, large enough for this key
+    void reserve(ProofSlot& sl) const {
+        sl.ws1.ensure(b1());
+        sl.ws2.ensure(b2());
+        if (sl.h_ws_cap < record_bytes()) {
+            host_free_pinned(sl.h_ws);
+            sl.h_ws = nullptr; sl.h_ws_cap = 0;
+            sl.h_ws = host_alloc_pinned(record_bytes());
+            sl.h_ws_cap = record_bytes();
+        }
+    }
+};
+
 template <class C>
 struct PkLoader {
     typedef typename C::Fq Fq;
@@ -1064,7 +1107,8 @@ struct PkLoader {
     }
     // levels 1 .. W-1 of the five tables of a key whose level 0 is in place (zkhip_pk_import of a compact image)
     static void table_levels(zkhip_ctx* ctx, zkhip_pk* pk) {
-        const MsmShape shz = msm_shape(ctx, pk->z_n, C::Fr::Params::BITS, true, pk->c_z, pk->s_z), shh = msm_shape(ctx, pk->h_n, C::Fr::Params::BITS, true, pk->c_h, pk->s_h);
+        const SlotSums<C> ly(ctx, pk);
+        const MsmShape &shz = ly.shz, &shh = ly.shh;
         msm_table_levels<Fq>(ctx, pk->a_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
         msm_table_levels<Fq>(ctx, pk->b1_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
         msm_table_levels<Fq>(ctx, pk->l_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
@@ -1248,9 +1292,8 @@ struct PkLoader {
     // this key's index ranges of H' / L' as MSM tables (level 0 from `h_src` / `l_src`: this key's RANGES, h_n / z_n points, on the
     // host or — `on_device` — on this device), the window multiples behind them, the counts the accumulation kernel is chosen from
     static void install_bound(zkhip_ctx* ctx, zkhip_pk* pk, const void* h_src, const void* l_src, bool on_device, const u64 fp[2]) {
-        typedef typename C::Fr Fr;
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
+        const SlotSums<C> ly(ctx, pk);
+        const MsmShape &shz = ly.shz, &shh = ly.shh;
         const u64 g1 = packed_point_bytes<Fq>();
         {
             size_t free_b = 0, total_b = 0;
@@ -1447,6 +1490,7 @@ struct Prover {
     typedef typename C::Fr Fr;
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
+    typedef SlotSums<C> Lay;
     static constexpr int FQB = Fq::BYTES;
 
     static CsrDev csr(const zkhip_r1cs* cs, int k) { return CsrDev{ptr<u64>(cs->rp[k]), ptr<u32>(cs->col[k]), cs->val[k].p}; }
@@ -1526,11 +1570,11 @@ struct Prover {
     static void enqueue_check(ProofSlot& sl, const Fr* a, const Fr* b, const Fr* c, u64 n, Stream s) {
         ZK_LAUNCH((k_r1cs_check<typename Fr::Params>), dim3(blocks_for(n, 256)), dim3(256), 0, s, a, b, c, n, ptr<unsigned long long>(sl.verdict));
     }
-    // the slot's finished proof failed its check: noted in the context (`record`: the pinned record at its zflag word)
-    static bool unsatisfied(zkhip_ctx* ctx, const ProofSlot& sl, const uint8_t* record) {
+    // the slot's finished proof failed its check: noted in the context
+    static bool unsatisfied(zkhip_ctx* ctx, const ProofSlot& sl, const Lay& ly) {
         if (sl.check_idx < 0) return false;
         u64 v[2];
-        memcpy(v, record + 8, 16);
+        memcpy(v, ly.verdict(sl), 16);
         if (!v[1]) return false;
         ctx->unsat.push_back({(u32)sl.check_idx, v[0], v[1]});
         return true;
@@ -1556,17 +1600,11 @@ struct Prover {
         Stream s = ctx->stream;
         ctx->ws = s;
         const u64 m = cs->l + cs->w, n = cs->n;
-        if (z_host) {
-            upload_z(ctx, sl.scalars, m, z_host, sl.zflag);
-        } else {
-            sl.zflag.ensure(4);
-            dev_memset(sl.zflag.p, 0, 4, s);      // a resident assignment was checked when it was uploaded
-        }
+        const Fr* z = stage_z(ctx, sl, m, m + 2, z_host, z_dev, true, true);
         sl.zmont.ensure(m * 32);
-        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, s, (const Fr*)(z_host ? sl.scalars.p : z_dev), ptr<Fr>(sl.zmont), m, k_to_rp());
+        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, s, z, ptr<Fr>(sl.zmont), m, k_to_rp());
         sl.vc.ensure(3 * std::max<u64>(n, 1) * sizeof(Fr));
         Fr *ra = ptr<Fr>(sl.vc), *rb = ra + n, *rc = rb + n;
-        verdict_reset(sl, s);
         if (n) matvec(ctx, cs, ptr<Fr>(sl.zmont), ra, rb, rc, n, 0, n);
         enqueue_check(sl, ra, rb, rc, n, s);
         u32 flag = 0;
@@ -1576,17 +1614,36 @@ struct Prover {
         require_canonical(flag);
     }
 
-    // z -> HBM (canonical integers; slots m, m+1 are reserved for r, s)
-    static void upload_z(zkhip_ctx* ctx, DBuf& dst, u64 m, const uint8_t* z, DBuf& flag) {
+    // z -> HBM (canonical integers) into a buffer of `cap` entries: the prover's hold what it appends to the m of the assignment (the
+    // blinding pair; GM17: the extension)
+    static void upload_z(zkhip_ctx* ctx, DBuf& dst, u64 m, u64 cap, const uint8_t* z, DBuf& flag) {
         Fr z0 = fe_from_bytes_canon<Fr>(z);
         Fr one = Fr::zero(); one.v[0] = 1;
         require(z0.equals(one), ZKHIP_ERR_BAD_ARG, "z[0] must be 1 (ark instance variable 0 is the constant ONE)");
-        dst.ensure((m + 2) * 32);
+        dst.ensure(cap * 32);
         dev_h2d(dst.p, z, m * 32, ctx->stream);
         // every entry must be a canonical field element (checked on the device; the verdict is read with the results)
         flag.ensure(4);
         dev_memset(flag.p, 0, 4, ctx->stream);
         ZK_LAUNCH((k_check_canonical<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, ctx->stream, ptr<Fr>(dst), m, ptr<u32>(flag));
+    }
+    // the assignment into the slot, from host memory or from a resident one (checked when it was uploaded: a clean zflag word), and
+    // the verdict of a checked proof reset behind it.  Returns where it is: a resident one stays where it was if the caller only
+    // reads it (`in_place`; the provers append to theirs)
+    static const Fr* stage_z(zkhip_ctx* ctx, ProofSlot& sl, u64 m, u64 cap, const uint8_t* z_host, const void* z_dev, bool checked, bool in_place = false) {
+        Stream st = ctx->stream;
+        if (z_host) {
+            upload_z(ctx, sl.scalars, m, cap, z_host, sl.zflag);
+        } else {
+            if (!in_place) {
+                sl.scalars.ensure(cap * 32);
+                dev_d2d(sl.scalars.p, z_dev, m * 32, st);
+            }
+            sl.zflag.ensure(4);
+            dev_memset(sl.zflag.p, 0, 4, st);
+        }
+        if (checked) verdict_reset(sl, st);
+        return (z_host || !in_place) ? ptr<Fr>(sl.scalars) : (const Fr*)z_dev;
     }
     static void require_canonical(u32 flag) {
         require(flag == 0, ZKHIP_ERR_BAD_ARG, "an assignment entry is not a canonical field element (>= r)");
@@ -1601,88 +1658,63 @@ struct Prover {
         ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, s, (const Fr*)d_scalars, ptr<Fr>(ctx->cur->zmont), m, pl->k_to_rp);
     }
 
-    // ---- enqueue: every kernel and copy of one proof, no host synchronisation
-    // src_dev != nullptr: the assignment is already in HBM (copied device-to-device into the slot); else z is a host buffer
+    // ---- enqueue: every kernel and copy of one proof, no host synchronisation.  Both schemes run the same machine — the assignment
+    // and the blinding scalars staged into a slot (open_slot, stage_z), the digits of S = [z.., r, s] sorted once and the G2 lane
+    // started (start_z_lanes), a witness map of the scheme's own on a second stream, the G1 lanes over z released when h is ready,
+    // the H lane, the copies out (lanes_after_h) — and differ in the middle: Groth16's is witness_map below, GM17's Gm17::enqueue.
+    // z_dev != nullptr: the assignment is already in HBM (copied device-to-device into the slot); else z is a host buffer
     // `lone`: nothing else of this context is in flight beside this proof (the single-proof entry points; a batch pipelines)
-    static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* src_dev,
+    static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
                         const uint8_t* r, const uint8_t* s_, bool lone = false, int check_idx = -1) {
-        enqueue_head(ctx, sl, pk, cs, z_host, src_dev, r, s_, lone, -1, check_idx);
+        enqueue_head(ctx, sl, pk, cs, z_host, z_dev, r, s_, lone, -1, check_idx);
         enqueue_tail(ctx, sl, pk, cs);
     }
     // whether a proof over (pk, cs) may be split between members: a bound key (its proof needs a and b on the coset and nothing else
     // of the witness map) over a domain where two transforms cost more than the exchange
     static bool can_split(const zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs) {
-        return pk->scheme == 0 && pk->bound_uid != 0 && pk->bound_uid == cs->uid && pk->logN >= ctx->split_min_log;
+        return pk->scheme == 0 && is_bound(pk, cs) && pk->logN >= ctx->split_min_log;
+    }
+    static bool is_bound(const zkhip_pk* pk, const zkhip_r1cs* cs) { return pk->bound_uid != 0 && pk->bound_uid == cs->uid; }   // (zkhip_pk_bind_r1cs; a shard: its ranges of H' / L')
+    // a free slot made the current one, with its streams and events, and the plan of the key's domain
+    static NttPlan<C>* open_slot(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk) {
+        require(!sl.busy, ZKHIP_ERR_DEVICE, "internal: proof slot still in flight");
+        make_pipe_streams(ctx);     // (a resident prover's first proof: every stream of the plan, in pipe order)
+        slot_init(ctx, sl);
+        NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
+        require(pl->split() == pk->ntt_log1, ZKHIP_ERR_BAD_ARG, "the key's h bases were ordered for another NTT split (NTT_SINGLE_MAX_LOG changed): reload the key");
+        sl.t_start = std::chrono::steady_clock::now();
+        ctx->cur = &sl;
+        ctx->ws = ctx->stream;
+        return pl;
     }
     // the staged scalars, the sort of the assignment, the G2 lane and the witness map — all of it (`half` = -1) or the vector `half`
     // (0: a, 1: b) of a bound key's, after which sl.half_ready is recorded and the caller brings the other vector into
     // sl.va + (1 - half) * N before enqueue_tail
-    static void enqueue_head(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* src_dev,
+    static void enqueue_head(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
                              const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1) {
         require(pk->curve == C::ID && cs->curve == C::ID, ZKHIP_ERR_BAD_ARG, "curve mismatch between key and constraint system");
         require(pk->scheme == 0, ZKHIP_ERR_BAD_ARG, "this is a GM17 proving key: use zkhip_prove_gm17");
         require(pk->m == cs->l + cs->w && pk->w == cs->w && pk->N == cs->N, ZKHIP_ERR_BAD_ARG,
                 "proving key does not match the constraint system (m, w or domain size)");
-        require(!sl.busy, ZKHIP_ERR_DEVICE, "internal: proof slot still in flight");
-        make_pipe_streams(ctx);     // (a resident prover's first proof: every stream of the plan, in pipe order)
-        slot_init(ctx, sl);
-        const u64 m = pk->m, N = pk->N;
-        const bool bound = pk->bound_uid != 0 && pk->bound_uid == cs->uid;   // (zkhip_pk_bind_r1cs; a shard: its ranges of H' / L')
+        const bool bound = is_bound(pk, cs);
         require(half < 0 || (bound && half <= 1), ZKHIP_ERR_BAD_ARG, "internal: only a proof over a bound key splits its witness map");
+        Fr rr = fe_from_bytes_canon<Fr>(r), ss = fe_from_bytes_canon<Fr>(s_);
+        require(canon_lt_mod(rr) && canon_lt_mod(ss), ZKHIP_ERR_BAD_ARG, "r or s not a canonical field element");
+        NttPlan<C>* pl = open_slot(ctx, sl, pk);
         sl.half = half;
         sl.lone = lone;
         sl.check_idx = half < 0 ? check_idx : -1;
-        Fr rr = fe_from_bytes_canon<Fr>(r), ss = fe_from_bytes_canon<Fr>(s_);
-        require(canon_lt_mod(rr) && canon_lt_mod(ss), ZKHIP_ERR_BAD_ARG, "r or s not a canonical field element");
-        NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
-        require(pl->split() == pk->ntt_log1, ZKHIP_ERR_BAD_ARG, "the key's h bases were ordered for another NTT split (NTT_SINGLE_MAX_LOG changed): reload the key");
-        sl.t_start = std::chrono::steady_clock::now();
         memcpy(sl.r, r, 32);
         memcpy(sl.s, s_, 32);
-        ctx->cur = &sl;
         Stream st = ctx->stream;
-        ctx->ws = st;
-        if (z_host) {
-            upload_z(ctx, sl.scalars, m, z_host, sl.zflag);
-        } else {
-            sl.scalars.ensure((m + 2) * 32);
-            dev_d2d(sl.scalars.p, src_dev, m * 32, st);
-            sl.zflag.ensure(4);
-            dev_memset(sl.zflag.p, 0, 4, st);      // a resident assignment was checked when it was uploaded
-        }
-        if (sl.check_idx >= 0) verdict_reset(sl, st);
-        void* d_scalars = sl.scalars.p;
-        stage_scalars(ctx, pl, d_scalars, m, r, s_);
+        stage_z(ctx, sl, pk->m, pk->m + 2, z_host, z_dev, sl.check_idx >= 0);
+        stage_scalars(ctx, pl, sl.scalars.p, pk->m, r, s_);
         event_record(sl.ev[0], st);
 
         // ---- MSMs over S = [z_0..z_{m-1}, r, s]: A, B1, L in G1 and B2 in G2 share one digit/sort pass
-        // (a sharded key covers only its index range of the bases, and pairs them with the same range of the scalars)
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        // (the shape is recomputed from the key's own (c, sets): a key whose numbers this build cannot run is refused, never
-        // paired with a sort of another window width)
-        require(shz.c == pk->c_z && shh.c == pk->c_h && (int)shz.sets == pk->s_z && (int)shh.sets == pk->s_h, ZKHIP_ERR_BAD_ARG,
-                "the key's tables were built for a window width this build cannot sort: reload the key");
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());   // sums per MSM (2: the tables carry the window multiples)
-        sl.ws1.ensure((size_t)4 * Wmax * sizeof(Xyzz<Fq>));   // 4 G1 MSMs + 1 G2 MSM
-        sl.ws2.ensure((size_t)Wmax * sizeof(Xyzz<Fq2>));
-        Xyzz<Fq>* ws1 = ptr<Xyzz<Fq>>(sl.ws1);
-        host_sums(sl, Wmax);
-        Xyzz<Fq>* hs1 = (Xyzz<Fq>*)sl.h_ws;                    // the host mirrors of ws1 / ws2: every lane copies its own sums out
-        Xyzz<Fq2>* hs2 = (Xyzz<Fq2>*)((uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        // An accumulation kernel is sized to fill the machine, saturates the integer multiplier and nothing preempts it:
-        // whatever arrives beside it waits for a place or crawls (kernel traces, profiles/r2_single_proof_traces.md: a
-        // 0.14 ms mat-vec took 4 ms, a 0.2 ms transform pass 3 ms), h arrives late and the H MSM trails alone behind
-        // everything.  So the G2 lane (the longest chain of a proof) starts at once, the witness map runs beside it, and
-        // the G1 lanes over z wait for h (`z_gate`; 2 = the G2 lane waits as well).
-        const int gate = z_gate(ctx);
-        const MsmSort& sort_b = (pk->thin_mask & 8) ? sl.sorts[2] : sl.sorts[0];   // the list b2_ext pairs with (zkhip_pk::thin_mask)
-        const bool inf_b2 = (pk->thin_mask & 8) ? pk->inf_many_thin[3] : pk->inf_many[3];
-        if (pk->z_n) {
-            msm_prepare(ctx, st, sl.sorts[0], (const u32*)d_scalars + pk->z_lo * 8, shz, pk->z_n);
-            if (pk->thin_mask) msm_prepare(ctx, st, sl.sorts[2], (const u32*)d_scalars + pk->z_lo * 8, shz, pk->z_n, ptr<u32>(pk->thin_keep), &sl.sorts[0]);
-            if (gate < 2) msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], nullptr, hs2);   // longest first
-        }
+        const Lay ly(ctx, pk);
+        ly.reserve(sl);
+        start_z_lanes(ctx, sl, pk, ly);
 
         // ---- K1-K4 and the h-sort, on the NTT stream: the main stream is free for the next proof's staging and z-sort
         Stream wn = ctx->serial ? st : slot_ntt_stream(ctx, sl);
@@ -1696,33 +1728,48 @@ struct Prover {
     // ... and the rest: (the product of the two halves,) the G1 lanes over z, the h sort and the H MSM, the copies out
     static void enqueue_tail(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs) {
         const u64 N = pk->N;
-        const bool bound = pk->bound_uid != 0 && pk->bound_uid == cs->uid, lone = sl.lone;
-        NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
         ctx->cur = &sl;
-        Stream st = ctx->stream;
-        Stream wn = ctx->serial ? st : slot_ntt_stream(ctx, sl);
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        Xyzz<Fq>* ws1 = ptr<Xyzz<Fq>>(sl.ws1);
-        Xyzz<Fq>* hs1 = (Xyzz<Fq>*)sl.h_ws;
-        Xyzz<Fq2>* hs2 = (Xyzz<Fq2>*)((uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        const int gate = z_gate(ctx);
-        const MsmSort& sort_b = (pk->thin_mask & 8) ? sl.sorts[2] : sl.sorts[0];
-        const bool inf_b2 = (pk->thin_mask & 8) ? pk->inf_many_thin[3] : pk->inf_many[3];
+        Stream wn = ctx->serial ? ctx->stream : slot_ntt_stream(ctx, sl);
         // where the H MSM's scalars are: the first vector — except for a split proof, whose product goes to the THIRD (c's, idle over a
         // bound key): its own half stays as it is for the partner that may still be copying it
         const u32* h_scalars = ptr<u32>(sl.va) + (sl.half >= 0 ? 2 * N * 8 : 0);
         if (sl.half >= 0) {
             // both vectors are on the coset now (the other one arrived on this stream): U_j = a_j b_j / Z(g), canonical integers
             Fr* a = ptr<Fr>(sl.va);
-            ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, wn, a, a + N, fe_from_mont(pl->zinv), a + 2 * N, N);
+            ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, wn, a, a + N, fe_from_mont(get_plan<C>(ctx, pk->logN)->zinv), a + 2 * N, N);
         }
-        event_record(sl.ev[2], wn);
+        lanes_after_h(ctx, sl, pk, Lay(ctx, pk), is_bound(pk, cs), sl.lone, h_scalars, wn);
+    }
 
+    // ---- the z lanes' start: the digits of S sorted once on the main stream — and once more without the variables a family of
+    // tables holds at infinity (zkhip_pk::thin_mask) — and the G2 lane, the longest chain of a proof.
+    // An accumulation kernel is sized to fill the machine, saturates the integer multiplier and nothing preempts it:
+    // whatever arrives beside it waits for a place or crawls (kernel traces, profiles/r2_single_proof_traces.md: a
+    // 0.14 ms mat-vec took 4 ms, a 0.2 ms transform pass 3 ms), h arrives late and the H MSM trails alone behind
+    // everything.  So the G2 lane starts at once, the witness map runs beside it, and the G1 lanes over z wait for h
+    // (`z_gate`; 2 = the G2 lane waits as well).
+    static void start_z_lanes(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const Lay& ly) {
+        if (!pk->z_n) return;
+        // (a sharded key pairs its index range of the bases with the same range of the scalars)
+        const u32* digits = ptr<u32>(sl.scalars) + pk->z_lo * 8;
+        msm_prepare(ctx, ctx->stream, sl.sorts[0], digits, ly.shz, pk->z_n);
+        if (pk->thin_mask) msm_prepare(ctx, ctx->stream, sl.sorts[2], digits, ly.shz, pk->z_n, ptr<u32>(pk->thin_keep), &sl.sorts[0]);
+        if (z_gate(ctx) < 2) run_g2(ctx, sl, pk, ly, nullptr);
+    }
+    static void run_g2(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const Lay& ly, Event after) {
+        const bool thin = pk->thin_mask & 8;   // the list b2_ext pairs with
+        msm_run<Fq2>(ctx, sl.lanes[3], sl.sorts[thin ? 2 : 0], pk->b2_ext.p, with_inf(ly.shz, thin ? pk->inf_many_thin[3] : pk->inf_many[3]), ly.ws2(sl),
+                     sl.acc_b[4], sl.acc_e[4], after, ly.hs2(sl));
+    }
+    // ---- the lanes after h: its scalars (canonical integers, the order of the key's h bases) are at `h_scalars`, written on `wn`.
+    // "h ready" is recorded there; the G2 lane if z_gate held it, the G1 lanes over z, the h sort on `wn` and the H lane, the copies out.
+    static void lanes_after_h(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const Lay& ly, bool bound, bool lone, const u32* h_scalars, Stream wn) {
+        Stream st = ctx->stream;
+        event_record(sl.ev[2], wn);
         if (pk->z_n) {
+            const int gate = z_gate(ctx);
             const Event h_ready = gate ? sl.ev[2] : nullptr;
-            if (gate >= 2) msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], h_ready, hs2);
+            if (gate >= 2) run_g2(ctx, sl, pk, ly, h_ready);
             // A G2 accumulation at one wave per SIMD (BLS12-381: the wave takes the SIMD's whole register file) shares no SIMD with a
             // G1 wave: G1 workgroups that arrive while some of its workgroups are still waiting for a place take the places, and the
             // G2 lane — the longest chain of such a proof — finishes that much later.  The witness map used to be the head start; a
@@ -1737,35 +1784,32 @@ struct Prover {
                 event_record(sl.g1_go, st);
                 g1_after = sl.g1_go;
             }
-            run_z_g1(ctx, sl, pk, shz, ws1, Wmax, g1_after, bound, hs1);
+            run_z_g1(ctx, sl, pk, ly, g1_after, bound);
         } else {
-            empty_msm(ctx, sl, ws1, 3 * Wmax, ptr<Xyzz<Fq2>>(sl.ws2), Wmax, 0, 4);
+            empty_msm(ctx, sl, ly, true);
         }
-
-        // ---- H = MSM(h_query, h) in sigma order (the zero-padded tail pairs with infinity bases)
+        // ---- H = MSM(h bases, h) in their order (sigma; the zero-padded tail pairs with infinity bases.  A bound key: the quotient's
+        // evaluations in natural order against H' — the same MSM machinery, other bases)
         if (pk->h_n) {
-            msm_prepare(ctx, wn, sl.sorts[1], h_scalars + pk->h_lo * 8, shh, pk->h_n);
-            // (a bound key: U in natural order against H' — the same MSM machinery, other bases)
-            msm_run<Fq>(ctx, sl.lanes[4], sl.sorts[1], bound ? pk->h_bound.p : pk->h_sigma.p, with_inf(shh, bound ? pk->inf_many_bound[1] : pk->inf_many[4]),
-                        ws1 + 3 * Wmax, sl.acc_b[3], sl.acc_e[3], nullptr, hs1 + 3 * Wmax);
+            msm_prepare(ctx, wn, sl.sorts[1], h_scalars + pk->h_lo * 8, ly.shh, pk->h_n);
+            msm_run<Fq>(ctx, sl.lanes[4], sl.sorts[1], bound ? pk->h_bound.p : pk->h_sigma.p, with_inf(ly.shh, bound ? pk->inf_many_bound[1] : pk->inf_many[4]),
+                        ly.ws1(sl, 3), sl.acc_b[3], sl.acc_e[3], nullptr, ly.hs1(sl, 3));
         } else {
-            empty_msm(ctx, sl, ws1 + 3 * Wmax, Wmax, nullptr, 0, 4, 5);
+            empty_msm(ctx, sl, ly, false);
         }
-
-        copy_out(ctx, sl, Wmax);
+        copy_out(ctx, sl, ly);
     }
 
-    // ---- A, B1, L: the three G1 MSMs over the sorted assignment (window sums to ws1 + {0, 1, 2} * Wmax)
+    // ---- A, B1, L: the three G1 MSMs over the sorted assignment (window sums to MSMs 0, 1, 2 of ws1)
     // (`bound`: L' in l's place, on the common list whatever l's family is — its public entries are finite)
-    static void run_z_g1(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const MsmShape& shz, Xyzz<Fq>* ws1, int Wmax, Event h_ready, bool bound = false,
-                         Xyzz<Fq>* hs1 = nullptr) {
+    static void run_z_g1(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const Lay& ly, Event h_ready, bool bound) {
         const void* tab[3] = {pk->a_ext.p, pk->b1_ext.p, bound ? pk->l_bound.p : pk->l_ext.p};
         auto thin = [&](int k) { return (bound && k == 2) ? 0u : (pk->thin_mask >> k) & 1u; };
         auto inf_many = [&](int k) { return (bound && k == 2) ? pk->inf_many_bound[0] : thin(k) ? pk->inf_many_thin[k] : pk->inf_many[k]; };
         if (!ctx->fuse_z) {
             for (int k = 0; k < 3; ++k)
-                msm_run<Fq>(ctx, sl.lanes[k], thin(k) ? sl.sorts[2] : sl.sorts[0], tab[k], with_inf(shz, inf_many(k)), ws1 + k * Wmax, sl.acc_b[k], sl.acc_e[k], h_ready,
-                            hs1 ? hs1 + k * Wmax : nullptr);
+                msm_run<Fq>(ctx, sl.lanes[k], thin(k) ? sl.sorts[2] : sl.sorts[0], tab[k], with_inf(ly.shz, inf_many(k)), ly.ws1(sl, k), sl.acc_b[k], sl.acc_e[k], h_ready,
+                            ly.hs1(sl, k));
             return;
         }
         // One launch per sorted list: the tables on the common list together, the tables on the thinned list together (up to three
@@ -1781,8 +1825,8 @@ struct Prover {
             for (int q = 0; q < nm; ++q) { tabs[q] = tab[member[q]]; many = many || inf_many(member[q]); }
             // destination slots: lead, then every `step` slots (any subset of {0, 1, 2} is an arithmetic progression)
             const int step = nm > 1 ? member[1] - member[0] : 1;
-            msm_run_tables<Fq>(ctx, sl.lanes[lead], which ? sl.sorts[2] : sl.sorts[0], tabs, nm, with_inf(shz, many), ws1 + lead * Wmax, (u32)(step * Wmax),
-                               sl.acc_b[lead], sl.acc_e[lead], h_ready, hs1 ? hs1 + lead * Wmax : nullptr);
+            msm_run_tables<Fq>(ctx, sl.lanes[lead], which ? sl.sorts[2] : sl.sorts[0], tabs, nm, with_inf(ly.shz, many), ly.ws1(sl, lead), (u32)(step * ly.Wmax),
+                               sl.acc_b[lead], sl.acc_e[lead], h_ready, ly.hs1(sl, lead));
             Stream s0 = ctx->serial ? ctx->stream : lane_stream(sl.lanes[lead]);
             for (int q = 1; q < nm; ++q) {
                 event_record(sl.acc_b[member[q]], s0);
@@ -1792,55 +1836,35 @@ struct Prover {
         }
     }
 
-    // the slot's pinned host copy of the window sums (4 G1 MSMs, the G2 MSM, the verdict word of the canonical check and, 8 bytes
-    // on, the 16-byte verdict of checked mode)
-    static void host_sums(ProofSlot& sl, int Wmax) {
-        const size_t b1 = (size_t)4 * Wmax * sizeof(Xyzz<Fq>), b2 = (size_t)Wmax * sizeof(Xyzz<Fq2>);
-        if (sl.h_ws_cap < b1 + b2 + 24) {
-            host_free_pinned(sl.h_ws);
-            sl.h_ws = nullptr; sl.h_ws_cap = 0;
-            sl.h_ws = host_alloc_pinned(b1 + b2 + 24);
-            sl.h_ws_cap = b1 + b2 + 24;
-        }
-    }
-    // where that record's zflag word is
-    static const uint8_t* host_record(const zkhip_ctx* ctx, const ProofSlot& sl, const zkhip_pk* pk) {
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        return (const uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>) + (size_t)Wmax * sizeof(Xyzz<Fq2>);
-    }
     // ---- the end of a proof's device work: every lane has copied its window sums out behind its fold (msm_run_tables) and recorded
     // `done`; a stream of its own — the main stream is free for the next proof — waits for all of them, fetches the verdict of the
     // canonical check and records "all done"
-    static void copy_out(zkhip_ctx* ctx, ProofSlot& sl, int Wmax) {
+    static void copy_out(zkhip_ctx* ctx, ProofSlot& sl, const Lay& ly) {
         Stream st = ctx->stream;
         Stream so = ctx->serial ? st : ctx_out_stream(ctx);
         for (int k = 0; k < ZK_NLANES; ++k) stream_wait_event(so, sl.lanes[k].done);
-        const size_t b1 = (size_t)4 * Wmax * sizeof(Xyzz<Fq>), b2 = (size_t)Wmax * sizeof(Xyzz<Fq2>);
         sl.zflag.ensure(4);
-        dev_d2h_pinned((uint8_t*)sl.h_ws + b1 + b2, sl.zflag.p, 4, so);   // written on the main stream before ev[0], which every lane waits for
+        dev_d2h_pinned(ly.zflag(sl), sl.zflag.p, 4, so);   // written on the main stream before ev[0], which every lane waits for
         if (sl.check_idx >= 0) {
             stream_wait_event(so, sl.ev[2]);      // "h ready": recorded behind the check on the stream of the witness map
-            dev_d2h_pinned((uint8_t*)sl.h_ws + b1 + b2 + 8, sl.verdict.p, 16, so);
+            dev_d2h_pinned(ly.verdict(sl), sl.verdict.p, 16, so);
         }
         event_record(sl.ev[3], so);
         sl.busy = true;
     }
 
-    // a rank whose range is empty (more ranks than points): all-infinity window sums, events recorded so that the
-    // bookkeeping of the slot stays uniform
-    static void empty_msm(zkhip_ctx* ctx, ProofSlot& sl, Xyzz<Fq>* ws1, size_t n1, Xyzz<Fq2>* ws2, size_t n2, int lane_from, int lane_to) {
+    // a rank whose range is empty (more ranks than points): all-infinity window sums on the device and in the host mirror (nothing is
+    // in flight for them), events recorded so that the bookkeeping of the slot stays uniform.  `over_z`: the four lanes over z, else H's
+    static void empty_msm(zkhip_ctx* ctx, ProofSlot& sl, const Lay& ly, bool over_z) {
         Stream st = ctx->stream;
-        if (n1) {
-            dev_memset(ws1, 0, n1 * sizeof(Xyzz<Fq>), st);
-            memset((uint8_t*)sl.h_ws + ((const uint8_t*)ws1 - (const uint8_t*)sl.ws1.p), 0, n1 * sizeof(Xyzz<Fq>));     // (the host mirror: nothing is in flight for these slots)
+        const int k0 = over_z ? 0 : 3, nk = over_z ? 3 : 1;
+        dev_memset(ly.ws1(sl, k0), 0, nk * ly.lane_bytes(), st);
+        memset(ly.hs1(sl, k0), 0, nk * ly.lane_bytes());
+        if (over_z) {
+            dev_memset(ly.ws2(sl), 0, ly.b2(), st);
+            memset(ly.hs2(sl), 0, ly.b2());
         }
-        if (n2) {
-            dev_memset(ws2, 0, n2 * sizeof(Xyzz<Fq2>), st);
-            memset((uint8_t*)sl.h_ws + (size_t)4 * n2 * sizeof(Xyzz<Fq>) + ((const uint8_t*)ws2 - (const uint8_t*)sl.ws2.p), 0, n2 * sizeof(Xyzz<Fq2>));   // (n2 = Wmax: the G2 sums follow the 4 x Wmax G1 sums)
-        }
-        for (int k = lane_from; k < lane_to; ++k) {
+        for (int k = over_z ? 0 : 4; k < (over_z ? 4 : 5); ++k) {
             const int e = k == 3 ? 4 : k == 4 ? 3 : k;   // lane 3 (B2) times with event pair 4, lane 4 (H) with pair 3
             event_record(sl.acc_b[e], st);
             event_record(sl.acc_e[e], st);
@@ -1858,22 +1882,16 @@ struct Prover {
         require(sl.busy, ZKHIP_ERR_DEVICE, "internal: no proof in flight in this slot");
         event_sync(sl.ev[3]);
         sl.busy = false;
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        const Xyzz<Fq>* h_ws1 = (const Xyzz<Fq>*)sl.h_ws;
-        const Xyzz<Fq2>* h_ws2 = (const Xyzz<Fq2>*)((const uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        u32 zflag;
-        memcpy(&zflag, (const uint8_t*)(h_ws2 + Wmax), 4);
-        require_canonical(zflag);
+        const Lay ly(ctx, pk);
+        require_canonical(ly.zflag_word(sl));
         // five independent Horner chains (W x c doublings each): one host thread per MSM, the G2 chain on this one
         Sums g;
         HostThreads th;
-        th.run([&] { g.a = msm_combine(&h_ws1[0 * Wmax], shz); });
-        th.run([&] { g.b1 = msm_combine(&h_ws1[1 * Wmax], shz); });
-        th.run([&] { g.l = msm_combine(&h_ws1[2 * Wmax], shz); });
-        th.run([&] { g.h = msm_combine(&h_ws1[3 * Wmax], shh); });
-        g.b2 = msm_combine(h_ws2, shz);
+        th.run([&] { g.a = msm_combine(ly.hs1(sl, 0), ly.shz); });
+        th.run([&] { g.b1 = msm_combine(ly.hs1(sl, 1), ly.shz); });
+        th.run([&] { g.l = msm_combine(ly.hs1(sl, 2), ly.shz); });
+        th.run([&] { g.h = msm_combine(ly.hs1(sl, 3), ly.shh); });
+        g.b2 = msm_combine(ly.hs2(sl), ly.shz);
         th.join();
         return g;
     }
@@ -1891,29 +1909,32 @@ struct Prover {
         assemble_tail(g, sA, rB1, rsD, out);
     }
     static void assemble_tail(const Sums& g, const Xyzz<Fq>& sA, const Xyzz<Fq>& rB1, const Xyzz<Fq>& rsD, uint8_t* out) {
-        const Xyzz<Fq>&gA = g.a, &gL = g.l, &gH = g.h;
-        const Xyzz<Fq2>& gB2 = g.b2;
         Xyzz<Fq> gC = xyzz_add(sA, rB1);
         gC = xyzz_add(gC, xyzz_neg(rsD));
-        gC = xyzz_add(gC, gL);
-        gC = xyzz_add(gC, gH);
+        gC = xyzz_add(gC, g.l);
+        gC = xyzz_add(gC, g.h);
         Aff<Fq> pa, pc;
         Aff<Fq2> pb;
         {
             HostThreads th;               // three inversions: one thread each
-            th.run([&] { pa = xyzz_to_affine(gA); });
+            th.run([&] { pa = xyzz_to_affine(g.a); });
             th.run([&] { pc = xyzz_to_affine(gC); });
-            pb = xyzz_to_affine(gB2);
+            pb = xyzz_to_affine(g.b2);
         }
-        memset(out, 0, 8 * FQB + 3);
-        if (!gA.is_inf()) { write_fe(pa.x, out); write_fe(pa.y, out + FQB); }
-        if (!gB2.is_inf()) {
+        write_proof(g.a.is_inf(), pa, g.b2.is_inf(), pb, gC.is_inf(), pc, out);
+    }
+    // the proof as both schemes write it: A (G1), B (G2), C (G1) as canonical affine coordinates, and a flag per point at infinity
+    static void write_proof(bool inf_a, const Aff<Fq>& pa, bool inf_b, const Aff<Fq2>& pb, bool inf_c, const Aff<Fq>& pc, uint8_t* out) {
+        memset(out, 0, PROOF_BYTES);
+        if (!inf_a) { write_fe(pa.x, out); write_fe(pa.y, out + FQB); }
+        if (!inf_b) {
             write_fe(pb.x.c0, out + 2 * FQB); write_fe(pb.x.c1, out + 3 * FQB);
             write_fe(pb.y.c0, out + 4 * FQB); write_fe(pb.y.c1, out + 5 * FQB);
         }
-        if (!gC.is_inf()) { write_fe(pc.x, out + 6 * FQB); write_fe(pc.y, out + 7 * FQB); }
-        out[8 * FQB] = gA.is_inf(); out[8 * FQB + 1] = gB2.is_inf(); out[8 * FQB + 2] = gC.is_inf();
+        if (!inf_c) { write_fe(pc.x, out + 6 * FQB); write_fe(pc.y, out + 7 * FQB); }
+        out[8 * FQB] = inf_a; out[8 * FQB + 1] = inf_b; out[8 * FQB + 2] = inf_c;
     }
+    static constexpr size_t PROOF_BYTES = 8 * FQB + 3;
     static void fill_timings(ProofSlot& sl, zkhip_timings* tm, std::chrono::steady_clock::time_point t_fin) {
         const auto t_end = std::chrono::steady_clock::now();
         if (tm) {
@@ -1936,11 +1957,7 @@ struct Prover {
     static void finish(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, uint8_t* out, zkhip_timings* tm) {
         require(pk->world == 1, ZKHIP_ERR_BAD_ARG, "this proving key is one shard of a multi-GPU key: use zkhip_prove_g16_partial + zkhip_combine_g16");
         require(sl.busy, ZKHIP_ERR_DEVICE, "internal: no proof in flight in this slot");
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        const Xyzz<Fq>* h_ws1 = (const Xyzz<Fq>*)sl.h_ws;
-        const Xyzz<Fq2>* h_ws2 = (const Xyzz<Fq2>*)((const uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
+        const Lay ly(ctx, pk);
         const Fr rr = fe_from_bytes_canon<Fr>(sl.r), ss = fe_from_bytes_canon<Fr>(sl.s);
         Sums g;
         Xyzz<Fq> sA, rB1, rsD;
@@ -1949,16 +1966,16 @@ struct Prover {
             HostThreads th;
             th.run([&] { rsD = rs_delta(pk, rr, ss); });
             event_sync(sl.lanes[3].done);
-            g.b2 = msm_combine(h_ws2, shz);
+            g.b2 = msm_combine(ly.hs2(sl), ly.shz);
             for (int k = 0; k < 3; ++k) event_sync(sl.lanes[k].done);
-            g.a = msm_combine(&h_ws1[0 * Wmax], shz);
-            g.b1 = msm_combine(&h_ws1[1 * Wmax], shz);
+            g.a = msm_combine(ly.hs1(sl, 0), ly.shz);
+            g.b1 = msm_combine(ly.hs1(sl, 1), ly.shz);
             th.run([&] { sA = xyzz_mul_limbs(g.a, ss.v, Fr::N); });
             th.run([&] { rB1 = xyzz_mul_limbs(g.b1, rr.v, Fr::N); });
-            g.l = msm_combine(&h_ws1[2 * Wmax], shz);
+            g.l = msm_combine(ly.hs1(sl, 2), ly.shz);
             event_sync(sl.lanes[4].done);
             t_fin = std::chrono::steady_clock::now();
-            g.h = msm_combine(&h_ws1[3 * Wmax], shh);
+            g.h = msm_combine(ly.hs1(sl, 3), ly.shh);
             event_sync(sl.ev[3]);
             th.join();
         } catch (...) {
@@ -1966,10 +1983,8 @@ struct Prover {
             throw;
         }
         sl.busy = false;
-        u32 zflag;
-        memcpy(&zflag, (const uint8_t*)(h_ws2 + Wmax), 4);
-        require_canonical(zflag);
-        if (unsatisfied(ctx, sl, (const uint8_t*)(h_ws2 + Wmax))) memset(out, 0, 8 * FQB + 3);      // a refused proof: all zero
+        require_canonical(ly.zflag_word(sl));
+        if (unsatisfied(ctx, sl, ly)) memset(out, 0, PROOF_BYTES);      // a refused proof: all zero
         else assemble_tail(g, sA, rB1, rsD, out);
         fill_timings(sl, tm, t_fin);
     }
@@ -1993,7 +2008,10 @@ struct Prover {
         const Aff<F> a = xyzz_to_affine(p);
         return {a.x, a.y, F::one(), F::one()};
     }
-    static void canonicalise(Sums& g) {
+    // one rank's share of the proof in flight in `sl`: the five partial sums as canonical XYZZ records (saturated Montgomery limbs)
+    static void emit_partial(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, uint8_t* partial_out, zkhip_timings* tm) {
+        Sums g = collect(ctx, sl, pk);
+        const auto t_fin = std::chrono::steady_clock::now();
         HostThreads th;
         th.run([&] { g.a = canonical(g.a); });
         th.run([&] { g.b1 = canonical(g.b1); });
@@ -2001,16 +2019,13 @@ struct Prover {
         th.run([&] { g.h = canonical(g.h); });
         g.b2 = canonical(g.b2);
         th.join();
+        memcpy(partial_out, &g, sizeof(g));
+        fill_timings(sl, tm, t_fin);
     }
-    // one rank's share of a proof: the five partial sums as canonical XYZZ records (saturated Montgomery limbs)
     static void prove_partial(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const uint8_t* r,
                               const uint8_t* s_, uint8_t* partial_out, zkhip_timings* tm) {
         enqueue(ctx, ctx->slots[0], pk, cs, z_host, z_dev, r, s_);
-        Sums g = collect(ctx, ctx->slots[0], pk);
-        const auto t_fin = std::chrono::steady_clock::now();
-        canonicalise(g);
-        memcpy(partial_out, &g, sizeof(g));
-        fill_timings(ctx->slots[0], tm, t_fin);
+        emit_partial(ctx, ctx->slots[0], pk, partial_out, tm);
     }
     // ---- a member's share of a proof whose witness map is SPLIT between the members (a bound key: the proof needs a and b on the
     // coset; the members of even rank transform a, those of odd rank b, and partners exchange — north_star's "NTT domain shard"):
@@ -2020,94 +2035,83 @@ struct Prover {
     //   split_end_*     the tail, and the member's result as prove_partial / prove_device_sums leave it.
     static void split_begin(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const uint8_t* r,
                             const uint8_t* s_, int half) {
-        require(pk->bound_uid != 0 && pk->bound_uid == cs->uid && pk->scheme == 0 && (half == 0 || half == 1), ZKHIP_ERR_BAD_ARG,
+        require(is_bound(pk, cs) && pk->scheme == 0 && (half == 0 || half == 1), ZKHIP_ERR_BAD_ARG,
                 "only a Groth16 proof over a key bound to its constraint system splits its witness map (half = 0: a, 1: b)");
         enqueue_head(ctx, ctx->slots[0], pk, cs, z_host, z_dev, r, s_, false, half);
     }
     static const void* split_half_ptr(zkhip_ctx* ctx, const zkhip_pk* pk, int half) { return ptr<Fr>(ctx->slots[0].va) + (u64)half * pk->N; }
+    // the slot of the split proof in flight, and the stream its halves travel on
+    static ProofSlot& split_slot(zkhip_ctx* ctx, Stream* wn = nullptr) {
+        require(ctx->slots[0].half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
+        if (wn) *wn = ctx->serial ? ctx->stream : ctx_ntt_stream(ctx);
+        return ctx->slots[0];
+    }
     static void split_fetch(zkhip_ctx* ctx, const zkhip_pk* pk, const void* src, int src_device, Event src_ready) {
-        ProofSlot& sl = ctx->slots[0];
-        require(sl.half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
-        Stream wn = ctx->serial ? ctx->stream : ctx_ntt_stream(ctx);
+        Stream wn;
+        ProofSlot& sl = split_slot(ctx, &wn);
         if (src_ready) event_sync(src_ready);           // (the partner's stream, possibly on another device: waited for on the host)
         dev_copy_between(ptr<Fr>(sl.va) + (u64)(1 - sl.half) * pk->N, ctx->device, src, src_device, pk->N * sizeof(Fr), wn);
     }
     static void split_fetch_host(zkhip_ctx* ctx, const zkhip_pk* pk, const uint8_t* other_half) {
-        ProofSlot& sl = ctx->slots[0];
-        require(sl.half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
-        Stream wn = ctx->serial ? ctx->stream : ctx_ntt_stream(ctx);
+        Stream wn;
+        ProofSlot& sl = split_slot(ctx, &wn);
         dev_h2d(ptr<Fr>(sl.va) + (u64)(1 - sl.half) * pk->N, other_half, pk->N * sizeof(Fr), wn);
     }
     static void split_half_out(zkhip_ctx* ctx, const zkhip_pk* pk, uint8_t* out) {
-        ProofSlot& sl = ctx->slots[0];
-        require(sl.half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
-        Stream wn = ctx->serial ? ctx->stream : ctx_ntt_stream(ctx);
+        Stream wn;
+        ProofSlot& sl = split_slot(ctx, &wn);
         dev_d2h(out, ptr<Fr>(sl.va) + (u64)sl.half * pk->N, pk->N * sizeof(Fr), wn);
         stream_sync(wn);
     }
     static void split_end_partial(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, uint8_t* partial_out, zkhip_timings* tm) {
-        ProofSlot& sl = ctx->slots[0];
-        require(sl.half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
-        enqueue_tail(ctx, sl, pk, cs);
-        Sums g = collect(ctx, sl, pk);
-        const auto t_fin = std::chrono::steady_clock::now();
-        canonicalise(g);
-        memcpy(partial_out, &g, sizeof(g));
-        fill_timings(sl, tm, t_fin);
+        enqueue_tail(ctx, split_slot(ctx), pk, cs);
+        emit_partial(ctx, ctx->slots[0], pk, partial_out, tm);
     }
     static void split_end_device_sums(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2,
                                       zkhip_timings* tm) {
-        ProofSlot& sl = ctx->slots[0];
-        require(sl.half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
-        enqueue_tail(ctx, sl, pk, cs);
-        wait_device_sums(ctx, sl, pk, d_ws1, b1, d_ws2, b2);
-        fill_timings(sl, tm, std::chrono::steady_clock::now());
+        enqueue_tail(ctx, split_slot(ctx), pk, cs);
+        hand_out_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2, tm);
     }
     // one rank's share of a proof, left ON THE DEVICE: the raw bucket-set sums of its five MSMs (ws1: 4 G1 MSMs x Wmax XYZZ
     // sums, ws2: the G2 MSM), for an exchange that never touches host memory (zkhip_multi_use_rccl: RCCL all-gather over
     // xGMI).  Valid until the slot's next proof.
     static void prove_device_sums(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const uint8_t* r,
                                   const uint8_t* s_, const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2, zkhip_timings* tm) {
-        ProofSlot& sl = ctx->slots[0];
-        enqueue(ctx, sl, pk, cs, z_host, nullptr, r, s_);
-        wait_device_sums(ctx, sl, pk, d_ws1, b1, d_ws2, b2);
-        fill_timings(sl, tm, std::chrono::steady_clock::now());
+        enqueue(ctx, ctx->slots[0], pk, cs, z_host, nullptr, r, s_);
+        hand_out_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2, tm);
     }
-    static void wait_device_sums(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2) {
+    // wait for the proof in flight in `sl` and hand those sums out
+    static void hand_out_sums(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2,
+                              zkhip_timings* tm) {
         require(sl.busy, ZKHIP_ERR_DEVICE, "internal: no proof in flight in this slot");
         event_sync(sl.ev[3]);
         sl.busy = false;
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        *b1 = (size_t)4 * Wmax * sizeof(Xyzz<Fq>);
-        *b2 = (size_t)Wmax * sizeof(Xyzz<Fq2>);
-        u32 zflag;
-        memcpy(&zflag, (const uint8_t*)sl.h_ws + *b1 + *b2, 4);
-        require_canonical(zflag);
+        const Lay ly(ctx, pk);
+        *b1 = ly.b1();
+        *b2 = ly.b2();
+        require_canonical(ly.zflag_word(sl));
         *d_ws1 = sl.ws1.p;
         *d_ws2 = sl.ws2.p;
+        fill_timings(sl, tm, std::chrono::steady_clock::now());
     }
     // the same sums, gathered into host memory (one rank's ws1 | ws2), as a partial record for `combine` (not canonical:
     // these never leave the process)
     static void record_from_sums(zkhip_ctx* ctx, const zkhip_pk* pk, const uint8_t* ws1, const uint8_t* ws2, uint8_t* record_out) {
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        std::vector<Xyzz<Fq>> a1((size_t)4 * Wmax);
-        std::vector<Xyzz<Fq2>> a2((size_t)Wmax);
-        memcpy(a1.data(), ws1, a1.size() * sizeof(Xyzz<Fq>));
-        memcpy(a2.data(), ws2, a2.size() * sizeof(Xyzz<Fq2>));
+        const Lay ly(ctx, pk);
+        std::vector<Xyzz<Fq>> a1(ly.b1() / sizeof(Xyzz<Fq>));
+        std::vector<Xyzz<Fq2>> a2(ly.b2() / sizeof(Xyzz<Fq2>));
+        memcpy(a1.data(), ws1, ly.b1());
+        memcpy(a2.data(), ws2, ly.b2());
         Sums g;
-        g.a = msm_combine(&a1[0 * Wmax], shz);
-        g.b1 = msm_combine(&a1[1 * Wmax], shz);
-        g.l = msm_combine(&a1[2 * Wmax], shz);
-        g.h = msm_combine(&a1[3 * Wmax], shh);
-        g.b2 = msm_combine(a2.data(), shz);
+        g.a = msm_combine(ly.lane(a1.data(), 0), ly.shz);
+        g.b1 = msm_combine(ly.lane(a1.data(), 1), ly.shz);
+        g.l = msm_combine(ly.lane(a1.data(), 2), ly.shz);
+        g.h = msm_combine(ly.lane(a1.data(), 3), ly.shh);
+        g.b2 = msm_combine(a2.data(), ly.shz);
         memcpy(record_out, &g, sizeof(g));
     }
-    // sum of the ranks' partial results, then the assembly
-    static void combine(const zkhip_pk* pk, u32 count, const uint8_t* partials, const uint8_t* r, const uint8_t* s_, uint8_t* out) {
+    // sum of the ranks' partial results ...
+    static Sums sum_partials(u32 count, const uint8_t* partials) {
         Sums t;
         t.a = t.b1 = t.l = t.h = Xyzz<Fq>::inf();
         t.b2 = Xyzz<Fq2>::inf();
@@ -2117,33 +2121,30 @@ struct Prover {
             t.a = xyzz_add(t.a, g.a); t.b1 = xyzz_add(t.b1, g.b1); t.l = xyzz_add(t.l, g.l); t.h = xyzz_add(t.h, g.h);
             t.b2 = xyzz_add(t.b2, g.b2);
         }
+        return t;
+    }
+    // ... then the assembly
+    static void combine(const zkhip_pk* pk, u32 count, const uint8_t* partials, const uint8_t* r, const uint8_t* s_, uint8_t* out) {
+        const Sums t = sum_partials(count, partials);
         Fr rr = fe_from_bytes_canon<Fr>(r), ss = fe_from_bytes_canon<Fr>(s_);
         require(canon_lt_mod(rr) && canon_lt_mod(ss), ZKHIP_ERR_BAD_ARG, "r or s not a canonical field element");
         assemble(pk, t, r, s_, out);
     }
     static constexpr size_t PARTIAL_BYTES = sizeof(Sums);
 
-    // one proof from a host assignment / from an assignment resident in HBM
-    static void prove_host(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z, const uint8_t* r, const uint8_t* s_,
-                           uint8_t* out, zkhip_timings* tm) {
+    // one proof, from a host assignment (`z_host`) or from one resident in HBM (`z_dev`)
+    static void prove(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const uint8_t* r, const uint8_t* s_,
+                      uint8_t* out, zkhip_timings* tm) {
         ctx->unsat.clear();
-        enqueue(ctx, ctx->slots[0], pk, cs, z, nullptr, r, s_, true, ctx->checked ? 0 : -1);
+        enqueue(ctx, ctx->slots[0], pk, cs, z_host, z_dev, r, s_, true, ctx->checked ? 0 : -1);
         finish(ctx, ctx->slots[0], pk, out, tm);
         raise_unsatisfied(ctx, 1, cs);
     }
-    static void prove_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, void* d_scalars, const uint8_t* r, const uint8_t* s_,
-                               uint8_t* out, zkhip_timings* tm) {
-        ctx->unsat.clear();
-        enqueue(ctx, ctx->slots[0], pk, cs, nullptr, d_scalars, r, s_, true, ctx->checked ? 0 : -1);
-        finish(ctx, ctx->slots[0], pk, out, tm);
-        raise_unsatisfied(ctx, 1, cs);
-    }
-    // `count` proofs, two in flight: while the GPU works on proof i the host finishes proof i-1 and enqueues proof i+1,
-    // so the latency-bound tail of one proof (the H fold) overlaps the MSMs of the next.
-    // z_host: count x m x 32 B, or nullptr with z_dev[i] = device pointers of resident assignments.
-    static void prove_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 count, const uint8_t* z_host, void* const* z_dev,
-                            const uint8_t* rs, uint8_t* proofs_out, zkhip_timings* tm) {
-        const size_t proof_bytes = 8 * FQB + 3;
+    // ---- `count` proofs, ctx->nslots in flight: while the GPU works on proof i the host finishes proof i-(nslots-1) and enqueues proof
+    // i+1, so the latency-bound tail of one proof (the H fold) overlaps the MSMs of the next.  `enq(i, slot)` enqueues proof i,
+    // `fin(j, slot, timings)` finishes proof j; in checked mode the call ends in ZKHIP_ERR_UNSATISFIED if a proof failed.
+    template <class Enq, class Fin>
+    static void run_batch(zkhip_ctx* ctx, const zkhip_r1cs* cs, u32 count, zkhip_timings* tm, Enq enq, Fin fin) {
         zkhip_timings acc, one;
         memset(&acc, 0, sizeof(acc));
         const auto t0 = std::chrono::steady_clock::now();
@@ -2151,12 +2152,10 @@ struct Prover {
         try {
             const u32 NS = (u32)ctx->nslots;   // proofs in flight
             for (u32 i = 0; i < count + NS - 1; ++i) {
-                if (i < count)
-                    enqueue(ctx, ctx->slots[i % NS], pk, cs, z_host ? z_host + (size_t)i * pk->m * 32 : nullptr, z_host ? nullptr : z_dev[i],
-                            rs + (size_t)i * 64, rs + (size_t)i * 64 + 32, false, ctx->checked ? (int)i : -1);
+                if (i < count) enq(i, ctx->slots[i % NS]);
                 if (i >= NS - 1 && i - (NS - 1) < count) {
                     const u32 j = i - (NS - 1);
-                    finish(ctx, ctx->slots[j % NS], pk, proofs_out + (size_t)j * proof_bytes, &one);
+                    fin(j, ctx->slots[j % NS], &one);
                     float* a = (float*)&acc; const float* b = (const float*)&one;
                     for (size_t k = 0; k < sizeof(acc) / sizeof(float); ++k) a[k] += b[k];
                 }
@@ -2172,9 +2171,19 @@ struct Prover {
         }
         raise_unsatisfied(ctx, count, cs);
     }
+    // z_host: count x m x 32 B, or nullptr with z_dev[i] = device pointers of resident assignments; rs: count x (r | s)
+    static void prove_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 count, const uint8_t* z_host, void* const* z_dev,
+                            const uint8_t* rs, uint8_t* proofs_out, zkhip_timings* tm) {
+        run_batch(ctx, cs, count, tm,
+                  [&](u32 i, ProofSlot& sl) {
+                      enqueue(ctx, sl, pk, cs, z_host ? z_host + (size_t)i * pk->m * 32 : nullptr, z_host ? nullptr : z_dev[i], rs + (size_t)i * 64,
+                              rs + (size_t)i * 64 + 32, false, ctx->checked ? (int)i : -1);
+                  },
+                  [&](u32 j, ProofSlot& sl, zkhip_timings* one) { finish(ctx, sl, pk, proofs_out + (size_t)j * PROOF_BYTES, one); });
+    }
     static void assignment_upload(zkhip_ctx* ctx, zkhip_assignment* a, const uint8_t* z) {
         DBuf flag;
-        upload_z(ctx, a->scalars, a->m, z, flag);
+        upload_z(ctx, a->scalars, a->m, a->m + 2, z, flag);
         u32 verdict = 0;
         dev_d2h(&verdict, flag.p, 4, ctx->stream);
         stream_sync(ctx->stream);
@@ -2268,7 +2277,7 @@ struct Prover {
         NttPlan<C>* pl = get_plan<C>(ctx, cs->logN);
         const u64 m = cs->l + cs->w;
         uint8_t zero[32] = {0};
-        upload_z(ctx, ctx->cur->scalars, m, z, ctx->cur->zflag);
+        upload_z(ctx, ctx->cur->scalars, m, m + 2, z, ctx->cur->zflag);
         stage_scalars(ctx, pl, ctx->cur->scalars.p, m, zero, zero);
         witness_map(ctx, cs, pl);
         ctx->cur->vb.ensure(pl->N * sizeof(Fr));
@@ -2278,52 +2287,19 @@ struct Prover {
         stream_sync(ctx->stream);
     }
 
-    template <class F>
-    static void field_op_api(zkhip_ctx* ctx, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+    // zkhip_field_op: count x (a op b) over elements F, canonical integers in and out, in workgroups of T; `launch` runs the kernel
+    // of the field's form on the two Montgomery vectors, result into the first (field_op_dispatch names the six)
+    template <class F, class Launch>
+    static void field_op_api(zkhip_ctx* ctx, u64 count, unsigned T, const uint8_t* a, const uint8_t* b, uint8_t* out, Launch launch) {
         Stream s = ctx->stream;
         const size_t bytes = count * sizeof(F);
         ctx->cur->va.ensure(bytes); ctx->cur->vb.ensure(bytes);
         dev_h2d(ctx->cur->va.p, a, bytes, s);
         dev_h2d(ctx->cur->vb.p, b, bytes, s);
-        const unsigned T = 256, B = blocks_for(count, T);
+        const unsigned B = blocks_for(count, T);
         ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
         ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->vb), count);
-        ZK_LAUNCH((k_field_op<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->va), count, op);
-        ZK_LAUNCH((k_from_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
-        dev_d2h(out, ctx->cur->va.p, bytes, s);
-        stream_sync(s);
-    }
-
-    // fields 2 and 3 of zkhip_field_op: Fq2 in the saturated form and in the MSM kernels' unsaturated one (k_field_op_fq2)
-    template <bool UNSAT>
-    static void field_op_fq2_api(zkhip_ctx* ctx, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-        typedef typename C::Fq2 F;
-        Stream s = ctx->stream;
-        const size_t bytes = count * sizeof(F);
-        ctx->cur->va.ensure(bytes); ctx->cur->vb.ensure(bytes);
-        dev_h2d(ctx->cur->va.p, a, bytes, s);
-        dev_h2d(ctx->cur->vb.p, b, bytes, s);
-        const unsigned T = 64, B = blocks_for(count, T);
-        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
-        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->vb), count);
-        ZK_LAUNCH((k_field_op_fq2<typename F::Params, UNSAT>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->va), count, op);
-        ZK_LAUNCH((k_from_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
-        dev_d2h(out, ctx->cur->va.p, bytes, s);
-        stream_sync(s);
-    }
-
-    // fields 4 and 5 of zkhip_field_op: Fr and Fq in the unsaturated limbs of the transform passes and the G1 kernels (k_field_op_unsat)
-    template <class F>
-    static void field_op_unsat_api(zkhip_ctx* ctx, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-        Stream s = ctx->stream;
-        const size_t bytes = count * sizeof(F);
-        ctx->cur->va.ensure(bytes); ctx->cur->vb.ensure(bytes);
-        dev_h2d(ctx->cur->va.p, a, bytes, s);
-        dev_h2d(ctx->cur->vb.p, b, bytes, s);
-        const unsigned T = 64, B = blocks_for(count, T);
-        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
-        ZK_LAUNCH((k_to_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->vb), count);
-        ZK_LAUNCH((k_field_op_unsat<typename F::Params>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->vb), ptr<F>(ctx->cur->va), count, op);
+        launch(dim3(B), dim3(T), s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->vb));
         ZK_LAUNCH((k_from_mont<F>), dim3(B), dim3(T), 0, s, ptr<F>(ctx->cur->va), ptr<F>(ctx->cur->va), count);
         dev_d2h(out, ctx->cur->va.p, bytes, s);
         stream_sync(s);
@@ -2391,8 +2367,8 @@ struct CurveOps {
     void (*split_end_partial)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, uint8_t*, zkhip_timings*);
     void (*split_end_device_sums)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const void**, size_t*, const void**, size_t*, zkhip_timings*);
     void (*r1cs_load)(zkhip_ctx*, zkhip_r1cs*, const u64* const rp[3], const u32* const col[3], const uint8_t* const val[3]);
-    void (*prove)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, zkhip_timings*);
-    void (*prove_resident)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, void*, const uint8_t*, const uint8_t*, uint8_t*, zkhip_timings*);
+    void (*prove)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t* z_host, const void* z_dev, const uint8_t*, const uint8_t*, uint8_t*,
+                  zkhip_timings*);
     void (*prove_batch)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, u32, const uint8_t*, void* const*, const uint8_t*, uint8_t*, zkhip_timings*);
     void (*prove_partial)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, const uint8_t*, uint8_t*,
                           zkhip_timings*);
@@ -2425,14 +2401,20 @@ struct CurveOps {
     size_t packed_g1_bytes;  // size of one resident G1 base (G2: twice that): lets zkhip_pk_import validate an image's shape
     int fr_bits;             // scalar width: the number of table levels follows from it and the window width
 };
+// fields of zkhip_field_op: 0 Fr, 1 Fq, 2 Fq2 in the saturated form; 3 Fq2, 4 Fr, 5 Fq in the unsaturated limbs of the MSM kernels
+// and the transform passes (k_field_op_fq2, k_field_op_unsat)
 template <class C>
 static void field_op_dispatch(zkhip_ctx* ctx, int field, int op, u64 count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    if (field == 0) Prover<C>::template field_op_api<typename C::Fr>(ctx, op, count, a, b, out);
-    else if (field == 1) Prover<C>::template field_op_api<typename C::Fq>(ctx, op, count, a, b, out);
-    else if (field == 2) Prover<C>::template field_op_fq2_api<false>(ctx, op, count, a, b, out);
-    else if (field == 3) Prover<C>::template field_op_fq2_api<true>(ctx, op, count, a, b, out);
-    else if (field == 4) Prover<C>::template field_op_unsat_api<typename C::Fr>(ctx, op, count, a, b, out);
-    else Prover<C>::template field_op_unsat_api<typename C::Fq>(ctx, op, count, a, b, out);
+    typedef typename C::Fr Fr;
+    typedef typename C::Fq Fq;
+    typedef typename C::Fq2 Fq2;
+    typedef Prover<C> P;
+    if (field == 0) P::template field_op_api<Fr>(ctx, count, 256, a, b, out, [&](dim3 g, dim3 t, Stream s, Fr* x, Fr* y) { ZK_LAUNCH((k_field_op<Fr>), g, t, 0, s, x, y, x, count, op); });
+    else if (field == 1) P::template field_op_api<Fq>(ctx, count, 256, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq* x, Fq* y) { ZK_LAUNCH((k_field_op<Fq>), g, t, 0, s, x, y, x, count, op); });
+    else if (field == 2) P::template field_op_api<Fq2>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq2* x, Fq2* y) { ZK_LAUNCH((k_field_op_fq2<typename Fq2::Params, false>), g, t, 0, s, x, y, x, count, op); });
+    else if (field == 3) P::template field_op_api<Fq2>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq2* x, Fq2* y) { ZK_LAUNCH((k_field_op_fq2<typename Fq2::Params, true>), g, t, 0, s, x, y, x, count, op); });
+    else if (field == 4) P::template field_op_api<Fr>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fr* x, Fr* y) { ZK_LAUNCH((k_field_op_unsat<typename Fr::Params>), g, t, 0, s, x, y, x, count, op); });
+    else P::template field_op_api<Fq>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq* x, Fq* y) { ZK_LAUNCH((k_field_op_unsat<typename Fq::Params>), g, t, 0, s, x, y, x, count, op); });
 }
 template <class C>
 static int ntt_log1_of(zkhip_ctx* ctx, int logN) { return get_plan<C>(ctx, logN)->split(); }
@@ -2463,8 +2445,7 @@ static CurveOps make_curve_ops() {
     o.split_end_partial = &Prover<C>::split_end_partial;
     o.split_end_device_sums = &Prover<C>::split_end_device_sums;
     o.r1cs_load = &Prover<C>::r1cs_load;
-    o.prove = &Prover<C>::prove_host;
-    o.prove_resident = &Prover<C>::prove_resident;
+    o.prove = &Prover<C>::prove;
     o.prove_batch = &Prover<C>::prove_batch;
     o.prove_partial = &Prover<C>::prove_partial;
     o.combine = &Prover<C>::combine;

@@ -22,6 +22,11 @@
 //     + g_gamma2_z_t . h0,  h0 = (U^2 - W)/Z                 lane 4   bases sigma-permuted like h_query
 // with scalars [ext_0..ext_{M-1}, rho, 0]: the four MSMs over the extended assignment share one digit/sort pass, as in
 // the Groth16 prover.  ark folds 2 d1 U + d1^2 Z - d2 into the quotient instead; the sums are the same group elements.
+//
+// The proof-slot driver is the Groth16 prover's (core.cuh, Prover<C>: open_slot, stage_z, start_z_lanes, lanes_after_h, collect,
+// run_batch, emit_partial, hand_out_sums, write_proof; the slot's layout is SlotSums<C>).  What this scheme supplies: the key
+// loader, the middle of `enqueue` (SAP rows and the extension on the main stream, the quotient's transforms on the context's NTT
+// stream) and the host formula for C (`assemble`).
 #pragma once
 
 namespace zk {
@@ -179,42 +184,23 @@ struct Gm17 {
     static Fr add_mod(const Fr& a, const Fr& b) {   // canonical integers
         return fe_from_mont(fe_add(fe_to_mont(a), fe_to_mont(b)));
     }
-    // every kernel and copy of one proof, no host synchronisation (the slot discipline of Prover<C>::enqueue)
-    static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* src_dev,
+    // every kernel and copy of one proof, no host synchronisation: the driver of Prover<C>::enqueue with this scheme's middle — the
+    // SAP rows and the extension of the assignment on the main stream (they feed the z sort), the quotient's transforms on the
+    // context's NTT stream behind them
+    static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
                         const uint8_t* d1, const uint8_t* r, int check_idx = -1) {
         check_match(pk, cs);
-        require(!sl.busy, ZKHIP_ERR_DEVICE, "internal: proof slot still in flight");
-        make_pipe_streams(ctx);
-        slot_init(ctx, sl);
-        sl.check_idx = check_idx;      // (checked mode, Prover<C>::enqueue_check: the test is on the R1CS rows, not on the SAP's)
         const u64 m = cs->l + cs->w, n = cs->n, l = cs->l, M = pk->m, D = pk->N;
         Fr dd = fe_from_bytes_canon<Fr>(d1), rr = fe_from_bytes_canon<Fr>(r);
         require(canon_lt_mod(dd) && canon_lt_mod(rr), ZKHIP_ERR_BAD_ARG, "d1 or r not a canonical field element");
         const Fr rho = add_mod(dd, rr);
-        const bool bound = pk->bound_uid != 0 && pk->bound_uid == cs->uid;   // (zkhip_pk_bind_r1cs: W's share and the last transform live in the bases)
-        NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
-        require(pl->split() == pk->ntt_log1, ZKHIP_ERR_BAD_ARG, "the key's quotient bases were ordered for another NTT split (NTT_SINGLE_MAX_LOG changed): reload the key");
-        sl.t_start = std::chrono::steady_clock::now();
+        const bool bound = P::is_bound(pk, cs);   // (zkhip_pk_bind_r1cs: W's share and the last transform live in the bases)
+        NttPlan<C>* pl = P::open_slot(ctx, sl, pk);
+        sl.check_idx = check_idx;      // (checked mode, Prover<C>::enqueue_check: the test is on the R1CS rows, not on the SAP's)
         memcpy(sl.r, rho.v, 32);
         memset(sl.s, 0, 32);
-        ctx->cur = &sl;
         Stream st = ctx->stream;
-        ctx->ws = st;
-        sl.scalars.ensure((M + 2) * 32);
-        if (z_host) {
-            Fr z0 = fe_from_bytes_canon<Fr>(z_host);
-            Fr one = Fr::zero(); one.v[0] = 1;
-            require(z0.equals(one), ZKHIP_ERR_BAD_ARG, "z[0] must be 1 (ark instance variable 0 is the constant ONE)");
-            dev_h2d(sl.scalars.p, z_host, m * 32, st);
-            sl.zflag.ensure(4);
-            dev_memset(sl.zflag.p, 0, 4, st);
-            ZK_LAUNCH((k_check_canonical<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, st, ptr<Fr>(sl.scalars), m, ptr<u32>(sl.zflag));
-        } else {
-            dev_d2d(sl.scalars.p, src_dev, m * 32, st);
-            sl.zflag.ensure(4);
-            dev_memset(sl.zflag.p, 0, 4, st);
-        }
-        if (check_idx >= 0) P::verdict_reset(sl, st);
+        P::stage_z(ctx, sl, m, M + 2, z_host, z_dev, check_idx >= 0);
         uint8_t* d_scalars = (uint8_t*)sl.scalars.p;
         sl.zmont.ensure(m * 32);
         dev_h2d(d_scalars + M * 32, sl.r, 32, st);
@@ -240,31 +226,11 @@ struct Gm17 {
         event_record(sl.ev[1], st);
 
         // ---- the four MSMs over S = [ext_0..ext_{M-1}, rho, 0] share one digit/sort pass
-        const MsmShape shz = msm_shape(ctx, pk->z_n, Fr::Params::BITS, true, pk->c_z, pk->s_z);
-        const MsmShape shh = msm_shape(ctx, pk->h_n, Fr::Params::BITS, true, pk->c_h, pk->s_h);
-        require(shz.c == pk->c_z && shh.c == pk->c_h && (int)shz.sets == pk->s_z && (int)shh.sets == pk->s_h, ZKHIP_ERR_BAD_ARG,
-                "the key's tables were built for a window width this build cannot sort: reload the key");
-        const int Wmax = (int)std::max(shz.nsums(), shh.nsums());
-        sl.ws1.ensure((size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        sl.ws2.ensure((size_t)Wmax * sizeof(Xyzz<Fq2>));
-        Xyzz<Fq>* ws1 = ptr<Xyzz<Fq>>(sl.ws1);
-        P::host_sums(sl, Wmax);
-        Xyzz<Fq>* hs1 = (Xyzz<Fq>*)sl.h_ws;                    // the host mirrors of ws1 / ws2: every lane copies its own sums out
-        Xyzz<Fq2>* hs2 = (Xyzz<Fq2>*)((uint8_t*)sl.h_ws + (size_t)4 * Wmax * sizeof(Xyzz<Fq>));
-        // (a sharded key covers only its index range of the bases and pairs them with the same range of the scalars)
-        // (the G1 lanes wait for the transforms, as in Prover::enqueue: the G2 lane starts at once)
-        const int gate = z_gate(ctx);
-        const MsmSort& sort_b = (pk->thin_mask & 8) ? sl.sorts[2] : sl.sorts[0];   // the list b2_ext pairs with (zkhip_pk::thin_mask)
-        const bool inf_b2 = (pk->thin_mask & 8) ? pk->inf_many_thin[3] : pk->inf_many[3];
-        if (pk->z_n) {
-            msm_prepare(ctx, st, sl.sorts[0], (const u32*)d_scalars + pk->z_lo * 8, shz, pk->z_n);
-            if (pk->thin_mask) msm_prepare(ctx, st, sl.sorts[2], (const u32*)d_scalars + pk->z_lo * 8, shz, pk->z_n, ptr<u32>(pk->thin_keep), &sl.sorts[0]);
-            if (gate < 2)
-                msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], nullptr, hs2);   // longest first
-        }
+        const typename P::Lay ly(ctx, pk);
+        ly.reserve(sl);
+        P::start_z_lanes(ctx, sl, pk, ly);
 
         // ---- quotient h0 = (U^2 - W)/Z: iNTT + coset NTT of U, pointwise square, coset iNTT minus W's coefficients / Z (sigma order, canonical)
-        // the transforms and the h-sort run on the NTT stream (the SAP rows above feed the z-sort and stay on the main one)
         Stream wn = ctx->serial ? st : ctx_ntt_stream(ctx);
         stream_wait_event(wn, sl.ev[1]);
         ctx->ws = wn;
@@ -286,26 +252,9 @@ struct Gm17 {
         }
         ctx->ws = ctx->stream;
         event_record(sl.ntt_e, wn);
-        event_record(sl.ev[2], wn);
 
-        if (pk->z_n) {
-            const Event h_ready = gate ? sl.ev[2] : nullptr;
-            if (gate >= 2)
-                msm_run<Fq2>(ctx, sl.lanes[3], sort_b, pk->b2_ext.p, with_inf(shz, inf_b2), ptr<Xyzz<Fq2>>(sl.ws2), sl.acc_b[4], sl.acc_e[4], h_ready, hs2);
-            P::run_z_g1(ctx, sl, pk, shz, ws1, Wmax, h_ready, bound, hs1);
-        } else {
-            P::empty_msm(ctx, sl, ws1, 3 * Wmax, ptr<Xyzz<Fq2>>(sl.ws2), Wmax, 0, 4);
-        }
-
-        // ---- G = MSM(g_gamma2_z_t, h0)   (a bound key: U^2 / Z(g) in natural order against G')
-        if (pk->h_n) {
-            msm_prepare(ctx, wn, sl.sorts[1], ptr<u32>(sl.va) + pk->h_lo * 8, shh, pk->h_n);
-            msm_run<Fq>(ctx, sl.lanes[4], sl.sorts[1], bound ? pk->h_bound.p : pk->h_sigma.p, with_inf(shh, bound ? pk->inf_many_bound[1] : pk->inf_many[4]),
-                        ws1 + 3 * Wmax, sl.acc_b[3], sl.acc_e[3], nullptr, hs1 + 3 * Wmax);
-        } else {
-            P::empty_msm(ctx, sl, ws1 + 3 * Wmax, Wmax, nullptr, 0, 4, 5);
-        }
-        P::copy_out(ctx, sl, Wmax);
+        // ---- the lanes over z, and G = MSM(g_gamma2_z_t, h0)   (a bound key: U^2 / Z(g) in natural order against G'); never a lone proof's head start
+        P::lanes_after_h(ctx, sl, pk, ly, bound, false, ptr<u32>(sl.va), wn);
     }
 
     // C = C1 + rho C2 + rho^2 g_gamma2_z2 + G
@@ -315,7 +264,7 @@ struct Gm17 {
         const auto t_fin = std::chrono::steady_clock::now();
         Fr rho;
         memcpy(rho.v, sl.r, 32);
-        if (P::unsatisfied(ctx, sl, P::host_record(ctx, sl, pk))) memset(out, 0, 8 * FQB + 3);      // a refused proof: all zero
+        if (P::unsatisfied(ctx, sl, typename P::Lay(ctx, pk))) memset(out, 0, P::PROOF_BYTES);      // a refused proof: all zero
         else assemble(pk, g, rho, out);
         P::fill_timings(sl, tm, t_fin);
     }
@@ -335,50 +284,27 @@ struct Gm17 {
         Xyzz<Fq> gC = xyzz_add(g.l, t1);
         gC = xyzz_add(gC, t2);
         gC = xyzz_add(gC, g.h);
-        Aff<Fq> pa = xyzz_to_affine(g.a), pc = xyzz_to_affine(gC);
-        Aff<Fq2> pb = xyzz_to_affine(g.b2);
-        memset(out, 0, 8 * FQB + 3);
-        if (!g.a.is_inf()) { write_fe(pa.x, out); write_fe(pa.y, out + FQB); }
-        if (!g.b2.is_inf()) {
-            write_fe(pb.x.c0, out + 2 * FQB); write_fe(pb.x.c1, out + 3 * FQB);
-            write_fe(pb.y.c0, out + 4 * FQB); write_fe(pb.y.c1, out + 5 * FQB);
-        }
-        if (!gC.is_inf()) { write_fe(pc.x, out + 6 * FQB); write_fe(pc.y, out + 7 * FQB); }
-        out[8 * FQB] = g.a.is_inf(); out[8 * FQB + 1] = g.b2.is_inf(); out[8 * FQB + 2] = gC.is_inf();
+        P::write_proof(g.a.is_inf(), xyzz_to_affine(g.a), g.b2.is_inf(), xyzz_to_affine(g.b2), gC.is_inf(), xyzz_to_affine(gC), out);
     }
     // one rank's share of a proof (as Prover<C>::prove_partial): the five partial sums, canonical records
     static void prove_partial(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const uint8_t* rnd,
                               uint8_t* partial_out, zkhip_timings* tm) {
         check_d2(rnd);
         enqueue(ctx, ctx->slots[0], pk, cs, z_host, z_dev, rnd, rnd + 64);
-        typename P::Sums g = P::collect(ctx, ctx->slots[0], pk);
-        const auto t_fin = std::chrono::steady_clock::now();
-        P::canonicalise(g);
-        memcpy(partial_out, &g, sizeof(g));
-        P::fill_timings(ctx->slots[0], tm, t_fin);
+        P::emit_partial(ctx, ctx->slots[0], pk, partial_out, tm);
     }
     // (as Prover<C>::prove_device_sums: the share stays on the device for the RCCL exchange)
     static void prove_device_sums(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const uint8_t* rnd,
                                   const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2, zkhip_timings* tm) {
         check_d2(rnd);
         enqueue(ctx, ctx->slots[0], pk, cs, z_host, nullptr, rnd, rnd + 64);
-        P::wait_device_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2);
-        P::fill_timings(ctx->slots[0], tm, std::chrono::steady_clock::now());
+        P::hand_out_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2, tm);
     }
     static void combine(const zkhip_pk* pk, u32 count, const uint8_t* partials, const uint8_t* rnd, uint8_t* out) {
         check_d2(rnd);
         Fr dd = fe_from_bytes_canon<Fr>(rnd), rr = fe_from_bytes_canon<Fr>(rnd + 64);
         require(canon_lt_mod(dd) && canon_lt_mod(rr), ZKHIP_ERR_BAD_ARG, "d1 or r not a canonical field element");
-        typename P::Sums t;
-        t.a = t.b1 = t.l = t.h = Xyzz<Fq>::inf();
-        t.b2 = Xyzz<Fq2>::inf();
-        for (u32 i = 0; i < count; ++i) {
-            typename P::Sums g;
-            memcpy(&g, partials + (size_t)i * sizeof(g), sizeof(g));
-            t.a = xyzz_add(t.a, g.a); t.b1 = xyzz_add(t.b1, g.b1); t.l = xyzz_add(t.l, g.l); t.h = xyzz_add(t.h, g.h);
-            t.b2 = xyzz_add(t.b2, g.b2);
-        }
-        assemble(pk, t, add_mod(dd, rr), out);
+        assemble(pk, P::sum_partials(count, partials), add_mod(dd, rr), out);
     }
 
     // rnd = d1 | d2 | r (3 x 32 B): d2 is validated and otherwise unused — it cancels out of the proof
@@ -393,40 +319,17 @@ struct Gm17 {
         finish(ctx, ctx->slots[0], pk, out, tm);
         P::raise_unsatisfied(ctx, 1, cs);
     }
-    // `count` proofs, ZK_NSLOTS in flight (see Prover<C>::prove_batch); rnd: count x 96 B
+    // `count` proofs pipelined (Prover<C>::run_batch); rnd: count x 96 B
     static void prove_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 count, const uint8_t* z_host, void* const* z_dev,
                             const uint8_t* rnd, uint8_t* proofs_out, zkhip_timings* tm) {
-        const size_t proof_bytes = 8 * FQB + 3;
         const u64 m = cs->l + cs->w;
-        zkhip_timings acc, one;
-        memset(&acc, 0, sizeof(acc));
-        const auto t0 = std::chrono::steady_clock::now();
-        ctx->unsat.clear();
-        try {
-            const u32 NS = (u32)ctx->nslots;   // proofs in flight
-            for (u32 i = 0; i < count + NS - 1; ++i) {
-                if (i < count) {
-                    check_d2(rnd + (size_t)i * 96);
-                    enqueue(ctx, ctx->slots[i % NS], pk, cs, z_host ? z_host + (size_t)i * m * 32 : nullptr, z_host ? nullptr : z_dev[i],
-                            rnd + (size_t)i * 96, rnd + (size_t)i * 96 + 64, ctx->checked ? (int)i : -1);
-                }
-                if (i >= NS - 1 && i - (NS - 1) < count) {
-                    const u32 j = i - (NS - 1);
-                    finish(ctx, ctx->slots[j % NS], pk, proofs_out + (size_t)j * proof_bytes, &one);
-                    float* a = (float*)&acc; const float* b = (const float*)&one;
-                    for (size_t k = 0; k < sizeof(acc) / sizeof(float); ++k) a[k] += b[k];
-                }
-            }
-        } catch (...) {
-            for (auto& sl : ctx->slots) sl.busy = false;
-            dev_sync_all();
-            throw;
-        }
-        if (tm) {
-            *tm = acc;
-            tm->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        P::raise_unsatisfied(ctx, count, cs);
+        P::run_batch(ctx, cs, count, tm,
+                     [&](u32 i, ProofSlot& sl) {
+                         check_d2(rnd + (size_t)i * 96);
+                         enqueue(ctx, sl, pk, cs, z_host ? z_host + (size_t)i * m * 32 : nullptr, z_host ? nullptr : z_dev[i], rnd + (size_t)i * 96,
+                                 rnd + (size_t)i * 96 + 64, ctx->checked ? (int)i : -1);
+                     },
+                     [&](u32 j, ProofSlot& sl, zkhip_timings* one) { finish(ctx, sl, pk, proofs_out + (size_t)j * P::PROOF_BYTES, one); });
     }
 
     // ------------------------------------------------------------ setup

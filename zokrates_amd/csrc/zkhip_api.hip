@@ -422,7 +422,7 @@ int32_t zkhip_prove_g16(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1
         require(pk && r1cs && z && r && s && proof_out, ZKHIP_ERR_BAD_ARG, "null argument");
         require(pk->world == 1, ZKHIP_ERR_BAD_ARG, "this proving key is one shard of a multi-GPU key: use zkhip_prove_g16_partial + zkhip_combine_g16");
         require(pk->ctx == ctx && r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "key / constraint system belong to another context");
-        ops_for(pk->curve)->prove(ctx, pk, r1cs, z, r, s, proof_out, timings);
+        ops_for(pk->curve)->prove(ctx, pk, r1cs, z, nullptr, r, s, proof_out, timings);
     });
 }
 
@@ -448,7 +448,7 @@ int32_t zkhip_prove_g16_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip
         require(pk->world == 1, ZKHIP_ERR_BAD_ARG, "this proving key is one shard of a multi-GPU key: use zkhip_prove_g16_partial + zkhip_combine_g16");
         require(pk->ctx == ctx && r1cs->ctx == ctx && z->ctx == ctx, ZKHIP_ERR_BAD_ARG, "handles belong to another context");
         require(z->curve == pk->curve && z->m == pk->m, ZKHIP_ERR_BAD_ARG, "assignment does not match the proving key");
-        ops_for(pk->curve)->prove_resident(ctx, pk, r1cs, z->scalars.p, r, s, proof_out, timings);
+        ops_for(pk->curve)->prove(ctx, pk, r1cs, nullptr, z->scalars.p, r, s, proof_out, timings);
     });
 }
 
