@@ -301,6 +301,94 @@ def test_key_image_carries_the_bound_tables(ctx, scheme):
         native.ProvingKey.from_image(ctx, 0, image[:-5], scheme=scheme)
 
 
+def _key_file_case(curve, scheme, n=14):
+    """(circuit, key file, assignment, prove(ctx, key, system) -> bytes, the oracle's proof) of one scheme at Circuit.synth(curve, n)."""
+    if scheme == "g16":
+        oc = cpu.Circuit.synth(curve.curve_id, n, 0x5EED0100)
+        tox = cpu.toxic_bytes(g16.Toxic.from_seed(curve))
+        z = oc.assignment()
+        return oc, cpu.ProvingKey.setup(oc, tox).serialize(), z, (lambda c, k, s: native.prove_g16(c, k, s, z, 51, 52)), cpu.trapdoor(oc, tox, z, 51, 52)
+    oc, tb17, opk, z = _gm17_case(curve, n)
+    return oc, opk.serialize(), z, (lambda c, k, s: native.prove_gm17(c, k, s, z, 51, 0, 52)), cpu.gm17_trapdoor(oc, tb17, z, 51, 52)
+
+
+def key_image_cases(ctx, curve, scheme):
+    """The whole key and shards 1 and 2 of 3, as loaded and bound (the whole key through `bind`, a shard through `bind_shard`):
+    (label, load() -> a fresh key in that state) for each of the six."""
+    oc, raw, _, _, _ = _key_file_case(curve, scheme)
+    cs = native.ConstraintSystem(ctx, curve.curve_id, oc.n, oc.l, oc.w, [oc.csr(k) for k in range(3)])
+    for rank, world in ((0, 1), (1, 3), (2, 3)):
+        for bound in (False, True):
+            def load(rank=rank, world=world, bound=bound):
+                pk = native.ProvingKey(ctx, curve.curve_id, raw, rank=rank, world=world, scheme=scheme)
+                if bound:
+                    pk.bind(cs) if world == 1 else pk.bind_shard(cs, raw)
+                    assert pk.is_bound(cs)
+                return pk
+            yield "%s %s %d/%d %s" % (scheme, curve.name, rank, world, "bound" if bound else "plain"), load
+
+
+@pytest.mark.parametrize("curve", CURVES, ids=lambda c: c.name)
+@pytest.mark.parametrize("scheme", ["g16", "gm17"])
+def test_key_image_round_trip(ctx, curve, scheme):
+    """An image is a function of the key file, the shard and the binding alone: two loads of the same file export the same bytes, and
+    an imported image exports itself — export(import(export(pk))) == export(pk), byte for byte (every resident base, the window
+    widths, the set counts, the index ranges, the bound tables and the fingerprint go through the header and back)."""
+    for label, load in key_image_cases(ctx, curve, scheme):
+        pk, again = load(), load()
+        image = pk.export_image().tobytes()
+        print(label, len(image))
+        assert again.export_image().tobytes() == image, label
+        back = native.ProvingKey.from_image(ctx, curve.curve_id, np.frombuffer(image, dtype=np.uint8), scheme=scheme)
+        assert back.export_image().tobytes() == image, label
+        for k in (pk, again, back):
+            k.close()
+
+
+def bad_key_files(curve, scheme, raw):
+    """Three files neither parser may take: a truncated key, the key of the other scheme, one trailing byte."""
+    other = _key_file_case(curve, "gm17" if scheme == "g16" else "g16")[1]
+    return {"truncated": raw[:len(raw) - 9], "other scheme": other, "trailing byte": np.concatenate([raw, np.zeros(1, dtype=np.uint8)])}
+
+
+@pytest.mark.parametrize("scheme", ["g16", "gm17"])
+def test_a_refused_key_file_leaves_the_binding(ctx, scheme):
+    key_file_refusal_checks(ctx, emu_library(), scheme)
+
+
+def key_file_refusal_checks(ctx, lib, scheme):
+    """The one parser per scheme, seen from outside: `bind_shard` and `multi.bind` given a file the parser refuses return an error
+    and leave what was there — an earlier binding still proves the oracle's bytes."""
+    curve = BN254
+    oc, raw, z, prove, want = _key_file_case(curve, scheme)
+    raw = np.asarray(raw, dtype=np.uint8)
+    mats = [oc.csr(k) for k in range(3)]
+    cs = native.ConstraintSystem(ctx, 0, oc.n, oc.l, oc.w, mats)
+    pk = native.ProvingKey(ctx, 0, raw, scheme=scheme)
+    pk.bind_shard(cs, raw)
+    assert pk.is_bound(cs) and prove(ctx, pk, cs) == want
+    for what, bad in bad_key_files(curve, scheme, raw).items():
+        with pytest.raises(native.ZkhipError):
+            pk.bind_shard(cs, bad)
+        assert pk.is_bound(cs), what
+        assert prove(ctx, pk, cs) == want, what
+    pk.close()
+    multi = native.Multi([0] * 3, lib)
+    try:
+        multi.load_constraint_system(0, oc.n, oc.l, oc.w, mats)
+        multi.load_proving_key(0, raw, scheme=scheme)
+        multi_prove = (lambda: multi.prove_g16(z, 51, 52)) if scheme == "g16" else (lambda: multi.prove_gm17(z, 51, 0, 52))
+        for bound in (False, True):      # the members as loaded, then bound: a refused file changes neither
+            if bound:
+                multi.bind(raw)
+            for what, bad in bad_key_files(curve, scheme, raw).items():
+                with pytest.raises(native.ZkhipError):
+                    multi.bind(bad)
+                assert multi_prove() == want, (what, bound)
+    finally:
+        multi.close()
+
+
 def test_multi_members_bind_together(ctx):
     """zkhip_multi_bind: one member computes the bound bases from the key file, every member installs its ranges; the members'
     proof is the unsharded one, for both schemes, with the host exchange and the gathered one."""

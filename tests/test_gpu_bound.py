@@ -34,6 +34,17 @@ def test_gpu_key_image_carries_the_bound_tables(gctx, scheme):
     T.test_key_image_carries_the_bound_tables(gctx, scheme)
 
 
+@pytest.mark.parametrize("curve", [BN254, BLS12_381], ids=lambda c: c.name)
+@pytest.mark.parametrize("scheme", ["g16", "gm17"])
+def test_gpu_key_image_round_trip(gctx, curve, scheme):
+    T.test_key_image_round_trip(gctx, curve, scheme)
+
+
+@pytest.mark.parametrize("scheme", ["g16", "gm17"])
+def test_gpu_a_refused_key_file_leaves_the_binding(gctx, scheme):
+    T.key_file_refusal_checks(gctx, native.default_library(), scheme)
+
+
 def test_gpu_multi_members_bind_together():
     T.multi_bind_checks(native.default_library(), gathered=False)      # members share the one GPU of the box: the host exchange
 

@@ -15,6 +15,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -841,6 +842,28 @@ struct zkhip_pk {
     bool inf_many_bound[2] = {true, true};   // (L', H'): as inf_many
 };
 
+// Device-layout image of a loaded key (zkhip_pk_export / _import; PkLoader<C>::export_image / import_image).  "ZKHIPPK" + layout
+// version; bump the version whenever the resident layout (packed points, sigma order, the extended base vectors, table levels)
+// changes: an image is only meaningful to the library build that wrote it.  An image holds level 0 of the five base tables; the
+// window multiples are recomputed on the device at import (~0.1 s for a 2^20 key — less than reading the 6 GiB they occupy from any
+// disk: measured in round 3, which is why the image that carried every level is gone).
+static const char PK_IMAGE_MAGIC[8] = {'Z', 'K', 'H', 'I', 'P', 'P', 'K', '5'};
+struct PkImageHeader {
+    char magic[8];
+    int32_t curve, scheme;
+    uint64_t m, w, l, hlen, N;
+    int32_t logN, c_z, c_h, sets;     // sets: s_z | s_h << 8 — which window multiples the tables hold (MsmShape::sets)
+    uint32_t rank, world;
+    int32_t ntt_split, reserved;      // the NTT split h_sigma is ordered for (zkhip_pk::ntt_log1 = NttPlan::split())
+    uint64_t z_lo, z_n, h_lo, h_n;
+    uint64_t len_delta, len_g2z2, len_buf[5];
+    // version 5: level 0 of the bound tables H' / L' (this key's index ranges) when the key was bound at export, and the fingerprint
+    // of the constraint system they were made for — zkhip_pk_bind_r1cs on the imported key attaches them when the system's
+    // fingerprint agrees and costs a checksum instead of the transforms (0 / 0: the key was not bound)
+    uint64_t len_bound[2];            // H', L'
+    uint64_t bound_fp[2];
+};
+
 // every constraint system of a process has a number of its own (a key remembers WHICH system it was bound to: an address can be
 // handed out again after zkhip_r1cs_free)
 static inline u64 zk_next_uid() {
@@ -936,6 +959,35 @@ struct SlotSums {
     }
 };
 
+// What a proving-key file of either scheme says a key is (PkLoader::parse_g16 / parse_gm17; pointers into the file's bytes, ark's
+// canonical encoding): four base tables over the extended variable range [0, m + 2), each a query vector at a shift, one extra point
+// at one index and optionally a constant folded into entry 0, in the resident order a, b1, l, b2 (b2: G2); the bases of the quotient
+// with their count before the padding; and the points the host formula for C needs.
+struct KeySources {
+    int scheme;                       // 0 = Groth16, 1 = GM17
+    u64 m, w, l, hlen, N;             // as zkhip_pk
+    struct Lane {
+        const uint8_t* src; u64 nsrc, shift;       // entry shift + j = src[j], j < nsrc
+        const uint8_t* extra; u64 extra_at;        // entry extra_at = *extra (if any); every other entry: the point at infinity
+        const uint8_t* add0;                       // added to entry 0 (if any)
+    } lane[4];
+    const uint8_t* h_src; u64 h_nsrc;
+    const uint8_t *delta_g1, *g_gamma2_z2;         // Groth16 / GM17: null in a key of the other scheme
+};
+// the square arithmetic program a GM17 key is made for (gm17.cuh): M variables, D0 rows padded to the radix-2 domain D
+struct SapShape {
+    u64 M, D0, D;
+    int logD;
+};
+static inline SapShape sap_shape(u64 n, u64 l, u64 w) {
+    SapShape s;
+    s.M = 1 + 2 * (l - 1) + w + n;
+    s.D0 = 2 * n + 2 * (l - 1) + 1;
+    s.logD = ilog2_ceil(s.D0);
+    s.D = (u64)1 << s.logD;
+    return s;
+}
+
 template <class C>
 struct PkLoader {
     typedef typename C::Fq Fq;
@@ -1002,73 +1054,147 @@ struct PkLoader {
         lo = std::min<u64>((u64)rank * nominal, total);
         n = std::min<u64>(nominal, total - lo);
     }
-    // the layout of ark's `serialize_unchecked` of ark_groth16::ProvingKey
-    struct Parsed {
-        const uint8_t *alpha_g1, *beta_g2, *delta_g2, *beta_g1, *delta_g1, *a_q, *b1_q, *b2_q, *h_q, *l_q;
-        u64 m, w, l, hl, N;
-    };
-    static Parsed parse(const uint8_t* bytes, size_t len) {
+    // ark's `serialize_unchecked` of ark_groth16::ProvingKey: vk{alpha_g1, beta_g2, gamma_g2, delta_g2,
+    // gamma_abc_g1[]}, beta_g1, delta_g1, a_query[], b_g1_query[], b_g2_query[] (G2), h_query[], l_query[].  The tables are extended by
+    // the (delta, r) and (delta, s) pairs — see prove() — and z_0 = 1, so alpha / beta ride on entry 0 of their query vectors:
+    //   lane 0  A_ext  = [a_query..., delta_1, inf]       + alpha_1      lane 2  L_ext  = [inf x l, l_query..., inf, inf]
+    //   lane 1  B1_ext = [b_g1_query..., inf, delta_1]    + beta_1       lane 3  B2_ext = [b_g2_query..., inf, delta_2]   + beta_2
+    static KeySources parse_g16(const uint8_t* bytes, size_t len) {
         Rd rd{bytes, bytes + len};
-        Parsed k;
-        k.alpha_g1 = rd.take(G1B);
-        k.beta_g2 = rd.take(G2B);
+        KeySources k{};
+        k.scheme = 0;
+        const uint8_t* alpha_g1 = rd.take(G1B);
+        const uint8_t* beta_g2 = rd.take(G2B);
         rd.take(G2B);                                  // gamma_g2 (verifier only)
-        k.delta_g2 = rd.take(G2B);
+        const uint8_t* delta_g2 = rd.take(G2B);
         const u64 n_abc = rd.len(G1B);
         rd.take(n_abc * G1B);                          // gamma_abc_g1 (verifier only)
-        k.beta_g1 = rd.take(G1B);
+        const uint8_t* beta_g1 = rd.take(G1B);
         k.delta_g1 = rd.take(G1B);
         k.m = rd.len(G1B);
-        k.a_q = rd.take(k.m * G1B);
+        const uint8_t* a_q = rd.take(k.m * G1B);
         const u64 mb1 = rd.len(G1B);
-        k.b1_q = rd.take(mb1 * G1B);
+        const uint8_t* b1_q = rd.take(mb1 * G1B);
         const u64 mb2 = rd.len(G2B);
-        k.b2_q = rd.take(mb2 * G2B);
-        k.hl = rd.len(G1B);
-        k.h_q = rd.take(k.hl * G1B);
+        const uint8_t* b2_q = rd.take(mb2 * G2B);
+        k.hlen = k.h_nsrc = rd.len(G1B);
+        k.h_src = rd.take(k.hlen * G1B);
         k.w = rd.len(G1B);
-        k.l_q = rd.take(k.w * G1B);
+        const uint8_t* l_q = rd.take(k.w * G1B);
         require(rd.p == rd.e, ZKHIP_ERR_PARSE, "trailing bytes after proving key");
         require(k.m >= 1 && mb1 == k.m && mb2 == k.m && k.w <= k.m, ZKHIP_ERR_PARSE, "inconsistent query lengths in proving key");
         k.l = k.m - k.w;
         require(n_abc == k.l, ZKHIP_ERR_PARSE, "gamma_abc length != number of instance variables");
-        k.N = k.hl + 1;
+        k.N = k.hlen + 1;
         require((k.N & (k.N - 1)) == 0, ZKHIP_ERR_PARSE, "h_query length + 1 is not a power of two");
         require(k.m + 2 < ((u64)1 << 31), ZKHIP_ERR_BAD_ARG, "too many variables");
+        k.lane[0] = {a_q, k.m, 0, k.delta_g1, k.m, alpha_g1};
+        k.lane[1] = {b1_q, k.m, 0, k.delta_g1, k.m + 1, beta_g1};
+        k.lane[2] = {l_q, k.w, k.l, nullptr, 0, nullptr};
+        k.lane[3] = {b2_q, k.m, 0, delta_g2, k.m + 1, beta_g2};
         return k;
     }
-    static void load(zkhip_ctx* ctx, const uint8_t* bytes, size_t len, zkhip_pk* pk) {
-        const Parsed k = parse(bytes, len);
-        const uint8_t *alpha_g1 = k.alpha_g1, *beta_g2 = k.beta_g2, *delta_g2 = k.delta_g2, *beta_g1 = k.beta_g1, *delta_g1 = k.delta_g1, *a_q = k.a_q,
-                      *b1_q = k.b1_q, *b2_q = k.b2_q, *h_q = k.h_q, *l_q = k.l_q;
-        const u64 m = k.m, w = k.w, l = k.l, hl = k.hl, N = k.N;
-        pk->m = m; pk->w = w; pk->l = l; pk->hlen = hl; pk->N = N; pk->logN = ilog2_floor(N);
+    // ark's `serialize_unchecked` of ark_gm17::ProvingKey: vk{h_g2, g_alpha_g1, h_beta_g2, g_gamma_g1, h_gamma_g2, query[]}, a_query[],
+    // b_query[] (G2), c_query_1[], c_query_2[], g_gamma_z, h_gamma_z (G2), g_ab_gamma_z, g_gamma2_z2, g_gamma2_z_t[].  The same five
+    // lanes with other bases (gm17.cuh has the algebra), extended by the (., rho) pair and one unused slot:
+    //   lane 0  [a_query, g_gamma_z, inf]                       lane 2  [inf x l, c_query_1, g_ab_gamma_z, inf]
+    //   lane 1  [c_query_2, inf, inf]                           lane 3  [b_query, h_gamma_z, inf]
+    // and over h g_gamma2_z_t[0 .. D) (entry D pairs with the d1^2 coefficient of ark's h, which the restructured prover does not produce)
+    static KeySources parse_gm17(const uint8_t* bytes, size_t len) {
+        Rd rd{bytes, bytes + len};
+        KeySources k{};
+        k.scheme = 1;
+        rd.take(G2B); rd.take(G1B); rd.take(G2B); rd.take(G1B); rd.take(G2B);   // vk points (verifier only)
+        k.l = rd.len(G1B);
+        rd.take(k.l * G1B);                                                      // vk.query (verifier only)
+        const u64 M = k.m = rd.len(G1B);
+        const uint8_t* a_q = rd.take(M * G1B);
+        const u64 Mb = rd.len(G2B);
+        const uint8_t* b_q = rd.take(Mb * G2B);
+        k.w = rd.len(G1B);
+        const uint8_t* c1_q = rd.take(k.w * G1B);
+        const u64 Mc2 = rd.len(G1B);
+        const uint8_t* c2_q = rd.take(Mc2 * G1B);
+        const uint8_t* g_gamma_z = rd.take(G1B);
+        const uint8_t* h_gamma_z = rd.take(G2B);
+        const uint8_t* g_ab_gamma_z = rd.take(G1B);
+        k.g_gamma2_z2 = rd.take(G1B);
+        k.hlen = rd.len(G1B);
+        k.h_src = rd.take(k.hlen * G1B);
+        require(rd.p == rd.e, ZKHIP_ERR_PARSE, "trailing bytes after proving key");
+        require(k.l >= 1 && M >= k.l && Mb == M && Mc2 == M && k.w == M - k.l, ZKHIP_ERR_PARSE, "inconsistent query lengths in GM17 proving key");
+        require(k.hlen >= 2 && ((k.hlen - 1) & (k.hlen - 2)) == 0, ZKHIP_ERR_PARSE, "g_gamma2_z_t length - 1 is not a power of two");
+        require(M + 2 < ((u64)1 << 31), ZKHIP_ERR_BAD_ARG, "too many variables");
+        k.N = k.h_nsrc = k.hlen - 1;
+        k.lane[0] = {a_q, M, 0, g_gamma_z, M, nullptr};
+        k.lane[1] = {c2_q, M, 0, nullptr, 0, nullptr};
+        k.lane[2] = {c1_q, k.w, k.l, g_ab_gamma_z, M, nullptr};
+        k.lane[3] = {b_q, M, 0, h_gamma_z, M, nullptr};
+        return k;
+    }
+    // THE list of a key's five resident tables, the four lanes over z and h: fn(k, buffer, Tag<field of the coordinates>, first index and
+    // count of this key's range [, the shape of the MSM the table serves: over z or over h])
+    template <class F> struct Tag { typedef F type; static constexpr int NC = std::is_same<F, Fq2>::value ? 4 : 2; };   // NC: base-field coordinates per point
+    template <class Fn>
+    static void for_each_table(zkhip_pk* pk, Fn&& fn) {
+        fn(0, pk->a_ext, Tag<Fq>{}, pk->z_lo, pk->z_n);
+        fn(1, pk->b1_ext, Tag<Fq>{}, pk->z_lo, pk->z_n);
+        fn(2, pk->l_ext, Tag<Fq>{}, pk->z_lo, pk->z_n);
+        fn(3, pk->b2_ext, Tag<Fq2>{}, pk->z_lo, pk->z_n);
+        fn(4, pk->h_sigma, Tag<Fq>{}, pk->h_lo, pk->h_n);
+    }
+    template <class Fn>
+    static void for_each_table(zkhip_pk* pk, const MsmShape& shz, const MsmShape& shh, Fn&& fn) {
+        for_each_table(pk, [&](int k, DBuf& b, auto f, u64 lo, u64 n) { fn(k, b, f, lo, n, &b == &pk->h_sigma ? shh : shz); });
+    }
+    static KeySources parse(int scheme, const uint8_t* bytes, size_t len) { return scheme == 0 ? parse_g16(bytes, len) : parse_gm17(bytes, len); }
+    template <int NC>
+    static void upload_lane(zkhip_ctx* ctx, DBuf& dst, u64 count, const KeySources::Lane& q) {
+        upload_decoded<NC>(ctx, dst, count, q.src, q.nsrc, q.shift, q.extra, q.extra_at);
+    }
+    // the h source in file order (affine), and from there in the sigma order the plan's NTT pipeline leaves h in, padded with infinity
+    static void upload_h(zkhip_ctx* ctx, const KeySources& k, DBuf& h_nat) {
+        upload_decoded<2>(ctx, h_nat, std::max<u64>(k.h_nsrc, 1), k.h_src, k.h_nsrc, 0, nullptr, 0);
+    }
+    static void sigma_order(zkhip_ctx* ctx, NttPlan<C>* plan, const KeySources& k, const DBuf& h_nat, DBuf& h_sigma) {
+        h_sigma.ensure(k.N * G1B);
+        ZK_LAUNCH((k_sigma_gather_points<Aff<Fq>>), dim3(blocks_for(k.N, 256)), dim3(256), 0, ctx->stream, ptr<Aff<Fq>>(h_nat), ptr<Aff<Fq>>(h_sigma), k.N, k.h_nsrc,
+                  plan->N1, plan->N2, plan->N3);
+    }
+    static void set_dims(zkhip_pk* pk, const KeySources& k) {
+        pk->scheme = k.scheme;
+        pk->m = k.m; pk->w = k.w; pk->l = k.l; pk->hlen = k.hlen; pk->N = k.N; pk->logN = ilog2_floor(k.N);
+    }
+    // a parsed key of either scheme, resident: the four lanes over z, the h table, the constants on entry 0, the window multiples
+    static void load(zkhip_ctx* ctx, const KeySources& k, zkhip_pk* pk) {
+        set_dims(pk, k);
         NttPlan<C>* plan = get_plan<C>(ctx, pk->logN);
         pk->ntt_log1 = plan->split();
-        pk->delta_g1_canon.assign(delta_g1, delta_g1 + G1B);
+        if (k.delta_g1) pk->delta_g1_canon.assign(k.delta_g1, k.delta_g1 + G1B);
+        if (k.g_gamma2_z2) pk->g_gamma2_z2_canon.assign(k.g_gamma2_z2, k.g_gamma2_z2 + G1B);
+        const u64 me = k.m + 2;
+        for_each_table(pk, [&](int j, DBuf& b, auto f, u64, u64) {
+            if (j < 4) upload_lane<decltype(f)::NC>(ctx, b, me, k.lane[j]);
+        });
+        {
+            DBuf h_nat;
+            upload_h(ctx, k, h_nat);
+            sigma_order(ctx, plan, k, h_nat, pk->h_sigma);
+            stream_sync(ctx->stream);
+        }
+        for_each_table(pk, [&](int j, DBuf& b, auto f, u64, u64) {
+            if (j < 4 && k.lane[j].add0) add_into<typename decltype(f)::type, decltype(f)::NC>(ctx, b, 0, k.lane[j].add0);
+        });
+        finish_tables(ctx, pk, me, k.N);
+    }
+    static void load_file(zkhip_ctx* ctx, int scheme, const uint8_t* bytes, size_t len, zkhip_pk* pk) { load(ctx, parse(scheme, bytes, len), pk); }
 
-        const u64 me = m + 2;   // extended by the (delta, r) and (delta, s) pairs — see prove()
-        // A_ext = [a_query..., delta_1, inf]          (+ alpha_1 folded into entry 0)
-        upload_decoded<2>(ctx, pk->a_ext, me, a_q, m, 0, delta_g1, m);
-        // B1_ext = [b_g1_query..., inf, delta_1]      (+ beta_1 folded into entry 0)
-        upload_decoded<2>(ctx, pk->b1_ext, me, b1_q, m, 0, delta_g1, m + 1);
-        // L_ext = [inf x l, l_query..., inf, inf]
-        upload_decoded<2>(ctx, pk->l_ext, me, l_q, w, l, nullptr, 0);
-        // B2_ext = [b_g2_query..., inf, delta_2]      (+ beta_2 folded into entry 0)
-        upload_decoded<4>(ctx, pk->b2_ext, me, b2_q, m, 0, delta_g2, m + 1);
-        // h_query, permuted into the sigma order the NTT pipeline leaves h in, padded with infinity
-        DBuf h_nat;
-        upload_decoded<2>(ctx, h_nat, std::max<u64>(hl, 1), h_q, hl, 0, nullptr, 0);
-        pk->h_sigma.ensure(N * G1B);
-        ZK_LAUNCH((k_sigma_gather_points<Aff<Fq>>), dim3(blocks_for(N, 256)), dim3(256), 0, ctx->stream, ptr<Aff<Fq>>(h_nat),
-                  ptr<Aff<Fq>>(pk->h_sigma), N, hl, plan->N1, plan->N2, plan->N3);
-        stream_sync(ctx->stream);
-        h_nat.release();
-        // constant terms: z_0 = 1, so alpha/beta ride on entry 0 of their query vectors
-        add_into<Fq, 2>(ctx, pk->a_ext, 0, alpha_g1);
-        add_into<Fq, 2>(ctx, pk->b1_ext, 0, beta_g1);
-        add_into<Fq2, 4>(ctx, pk->b2_ext, 0, beta_g2);
-        finish_tables(ctx, pk, me, N);
+    template <class F> static u64 table_bytes(u64 count, u32 levels) { return std::max<u64>(count, 1) * (u64)levels * packed_point_bytes<F>(); }
+    // bytes the five tables take at these shapes (an empty table still holds one point per level: what to_table allocates)
+    static u64 tables_need(zkhip_pk* pk, const MsmShape& shz, const MsmShape& shh) {
+        u64 t = 0;
+        for_each_table(pk, shz, shh, [&](int, DBuf&, auto f, u64, u64 n, const MsmShape& sh) { t += table_bytes<typename decltype(f)::type>(n, sh.levels); });
+        return t;
     }
     // this rank's share of the bases (everything for world = 1) as MSM tables: level 0 = the packed working form of the
     // range's points, levels 1 .. W-1 their window multiples 2^(c j) P (a 2^20 BN254 key: 16 levels, 6 GiB of the 288)
@@ -1076,44 +1202,36 @@ struct PkLoader {
         u64 nominal_z, nominal_h;
         range_of(me, pk->rank, pk->world, pk->z_lo, pk->z_n, nominal_z);
         range_of(hdom, pk->rank, pk->world, pk->h_lo, pk->h_n, nominal_h);
-        MsmShape shz = msm_shape(ctx, nominal_z, C::Fr::Params::BITS, true), shh = msm_shape(ctx, nominal_h, C::Fr::Params::BITS, true);
+        auto shape_z = [&](int sets) { return msm_shape(ctx, nominal_z, C::Fr::Params::BITS, true, 0, sets); };
+        auto shape_h = [&](int sets) { return msm_shape(ctx, nominal_h, C::Fr::Params::BITS, true, 0, sets); };
         // Every window multiple of every base (one bucket set, one fold per MSM) while that fits the device: a 2^20 key is 6 GiB,
         // 2^24 96 GiB.  Beyond — or when ZKHIP_TUNE_MSM_SETS says so — the tables keep every 2nd, 4th, ... multiple and the MSMs
         // fold as many bucket sets (the reference has no size limit below the field's two-adicity; this is how it is met).
         int sets = ctx->msm_sets;
         if (!sets) {
-            const u64 budget = msm_table_budget(ctx, pk->z_n, pk->h_n, hdom, shz.W, shz.K);
-            const u64 g1 = packed_point_bytes<Fq>(), g2 = packed_point_bytes<Fq2>();
+            const MsmShape one = shape_z(0);
+            const u64 budget = msm_table_budget(ctx, pk->z_n, pk->h_n, hdom, one.W, one.K);
             sets = 1;
             for (;;) {
-                const MsmShape a = msm_shape(ctx, nominal_z, C::Fr::Params::BITS, true, 0, sets), b = msm_shape(ctx, nominal_h, C::Fr::Params::BITS, true, 0, sets);
-                const u64 need = pk->z_n * (3 * g1 + g2) * a.levels + pk->h_n * g1 * b.levels;
-                if (need <= budget || (int)a.sets < sets) break;      // (a.sets < sets: already one bucket set per window)
+                const MsmShape a = shape_z(sets);
+                if (tables_need(pk, a, shape_h(sets)) <= budget || (int)a.sets < sets) break;      // (a.sets < sets: already one bucket set per window)
                 sets *= 2;
             }
         }
-        shz = msm_shape(ctx, nominal_z, C::Fr::Params::BITS, true, 0, sets);
-        shh = msm_shape(ctx, nominal_h, C::Fr::Params::BITS, true, 0, sets);
+        const MsmShape shz = shape_z(sets), shh = shape_h(sets);
         pk->c_z = shz.c;
         pk->c_h = shh.c;
         pk->s_z = (int)shz.sets;
         pk->s_h = (int)shh.sets;
-        to_table<Fq>(ctx, pk->a_ext, pk->z_lo, pk->z_n, shz);
-        to_table<Fq>(ctx, pk->b1_ext, pk->z_lo, pk->z_n, shz);
-        to_table<Fq>(ctx, pk->l_ext, pk->z_lo, pk->z_n, shz);
-        to_table<Fq2>(ctx, pk->b2_ext, pk->z_lo, pk->z_n, shz);
-        to_table<Fq>(ctx, pk->h_sigma, pk->h_lo, pk->h_n, shh);
+        for_each_table(pk, shz, shh, [&](int, DBuf& b, auto f, u64 lo, u64 n, const MsmShape& sh) { to_table<typename decltype(f)::type>(ctx, b, lo, n, sh); });
         count_points_at_infinity(ctx, pk);
     }
-    // levels 1 .. W-1 of the five tables of a key whose level 0 is in place (zkhip_pk_import of a compact image)
+    // levels 1 .. W-1 of the five tables of a key whose level 0 is in place (import of a compact image)
     static void table_levels(zkhip_ctx* ctx, zkhip_pk* pk) {
         const SlotSums<C> ly(ctx, pk);
-        const MsmShape &shz = ly.shz, &shh = ly.shh;
-        msm_table_levels<Fq>(ctx, pk->a_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
-        msm_table_levels<Fq>(ctx, pk->b1_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
-        msm_table_levels<Fq>(ctx, pk->l_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
-        msm_table_levels<Fq2>(ctx, pk->b2_ext.p, pk->z_n, shz.level_bits(), (int)shz.levels);
-        msm_table_levels<Fq>(ctx, pk->h_sigma.p, pk->h_n, shh.level_bits(), (int)shh.levels);
+        for_each_table(pk, ly.shz, ly.shh, [&](int, DBuf& b, auto f, u64, u64 n, const MsmShape& sh) {
+            msm_table_levels<typename decltype(f)::type>(ctx, b.p, n, sh.level_bits(), (int)sh.levels);
+        });
         count_points_at_infinity(ctx, pk);
     }
     // ---- zkhip_pk_bind_r1cs: H' and L' for ONE constraint system (bind.cuh has the algebra) ----
@@ -1159,18 +1277,25 @@ struct PkLoader {
         b.n_src = pk->scheme == 0 ? pk->hlen : pk->N;     // Groth16: h_query has N - 1 entries; GM17: g_gamma2_z_t[0 .. D)
         return b;
     }
-    // everything a refusal can depend on, BEFORE anything of the key is touched (zkhip_pk_bind_r1cs)
-    static void bind_check(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs) {
+    // THE test that a key belongs to a constraint system: curve, scheme (`want_scheme`: what the caller is about to run), dimensions
+    // (`min_N`: the smallest domain the caller can use)
+    static void check_match(const zkhip_pk* pk, const zkhip_r1cs* cs, int want_scheme, u64 min_N = 1) {
         require(pk->curve == C::ID && cs->curve == C::ID, ZKHIP_ERR_BAD_ARG, "curve mismatch between key and constraint system");
+        require(pk->scheme == want_scheme, ZKHIP_ERR_BAD_ARG,
+                want_scheme == 0 ? "this is a GM17 proving key: use zkhip_prove_gm17" : "this is a Groth16 proving key: use zkhip_prove_g16");
         if (pk->scheme == 0) {
             require(pk->m == cs->l + cs->w && pk->w == cs->w && pk->N == cs->N, ZKHIP_ERR_BAD_ARG,
                     "proving key does not match the constraint system (m, w or domain size)");
-            require(pk->N >= 2 && pk->hlen + 1 == pk->N, ZKHIP_ERR_BAD_ARG, "domain too small to bind");
         } else {
-            const u64 M = 1 + 2 * (cs->l - 1) + cs->w + cs->n, D0 = 2 * cs->n + 2 * (cs->l - 1) + 1;
-            require(pk->m == M && pk->l == cs->l && pk->N == ((u64)1 << ilog2_ceil(D0)) && pk->N >= 2, ZKHIP_ERR_BAD_ARG,
+            const SapShape sh = sap_shape(cs->n, cs->l, cs->w);
+            require(pk->m == sh.M && pk->l == cs->l && pk->N == sh.D && pk->N >= min_N, ZKHIP_ERR_BAD_ARG,
                     "GM17 proving key does not match the constraint system (SAP variables, instance size or domain)");
         }
+    }
+    // everything a refusal can depend on, BEFORE anything of the key is touched (zkhip_pk_bind_r1cs)
+    static void bind_check(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs) {
+        check_match(pk, cs, pk->scheme, 2);
+        if (pk->scheme == 0) require(pk->N >= 2 && pk->hlen + 1 == pk->N, ZKHIP_ERR_BAD_ARG, "domain too small to bind");
         NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
         require(pl->split() == pk->ntt_log1, ZKHIP_ERR_BAD_ARG, "the key's h bases were ordered for another NTT split (NTT_SINGLE_MAX_LOG changed): reload the key");
     }
@@ -1358,32 +1483,26 @@ struct PkLoader {
     // (zkhip_multi_bind: one member computes, all install; zkhip_pk_bind_r1cs_shard: a rank of a multi-process prover does both).
     static void bound_level0_from_file(zkhip_ctx* ctx, int scheme, const zkhip_r1cs* cs, const uint8_t* bytes, size_t len, std::vector<uint8_t>& h_host,
                                        std::vector<uint8_t>& l_host, u64 fp[2]) {
+        const KeySources k = parse(scheme, bytes, len);
         zkhip_pk tmp;                                   // dimensions and level 0 of the two tables only
-        tmp.curve = C::ID; tmp.scheme = scheme; tmp.ctx = ctx;
-        DBuf h_aff, l_aff;
-        if (scheme == 0) {
-            const Parsed k = parse(bytes, len);
-            tmp.m = k.m; tmp.w = k.w; tmp.l = k.l; tmp.hlen = k.hl; tmp.N = k.N; tmp.logN = ilog2_floor(k.N);
-            upload_decoded<2>(ctx, l_aff, k.m + 2, k.l_q, k.w, k.l, nullptr, 0);
-            upload_decoded<2>(ctx, h_aff, std::max<u64>(k.hl, 1), k.h_q, k.hl, 0, nullptr, 0);
-        } else {
-            gm17_level0_sources(ctx, bytes, len, &tmp, h_aff, l_aff);
-        }
+        tmp.curve = C::ID; tmp.ctx = ctx;
+        set_dims(&tmp, k);
+        DBuf l_aff, h_nat, h_sig;
+        upload_lane<2>(ctx, l_aff, k.m + 2, k.lane[2]);
+        upload_h(ctx, k, h_nat);
         NttPlan<C>* pl = get_plan<C>(ctx, tmp.logN);
         tmp.ntt_log1 = pl->split();
         bind_check(ctx, &tmp, cs);
         const BindShape b = bind_shape(&tmp);
         const u64 g1 = packed_point_bytes<Fq>();
-        DBuf h_sig, h0p, l0p;
-        h_sig.ensure(b.N * G1B);
-        ZK_LAUNCH((k_sigma_gather_points<Aff<Fq>>), dim3(blocks_for(b.N, 256)), dim3(256), 0, ctx->stream, ptr<Aff<Fq>>(h_aff), ptr<Aff<Fq>>(h_sig), b.N, b.n_src,
-                  pl->N1, pl->N2, pl->N3);
+        DBuf h0p, l0p;
+        sigma_order(ctx, pl, k, h_nat, h_sig);
         h0p.ensure(b.N * g1);
         l0p.ensure(b.me * g1);
         points_to_packed<Fq>(ctx, ptr<Aff<Fq>>(h_sig), h0p.p, b.N);
         points_to_packed<Fq>(ctx, ptr<Aff<Fq>>(l_aff), l0p.p, b.me);
         stream_sync(ctx->stream);
-        h_aff.release(); l_aff.release(); h_sig.release();
+        h_nat.release(); l_aff.release(); h_sig.release();
         WCols W;
         w_columns_for(ctx, scheme, cs, b.mcols, W);
         DBuf h0, l0;
@@ -1394,33 +1513,6 @@ struct PkLoader {
         dev_d2h(l_host.data(), l0.p, l_host.size(), ctx->stream);
         stream_sync(ctx->stream);
         r1cs_fingerprint(ctx, cs, fp);
-    }
-    // ark_gm17::ProvingKey: the quotient's bases g_gamma2_z_t[0 .. D) and the padded c_query_1 table (gm17.cuh Gm17::load's lane 2)
-    static void gm17_level0_sources(zkhip_ctx* ctx, const uint8_t* bytes, size_t len, zkhip_pk* dims, DBuf& h_aff, DBuf& l_aff) {
-        Rd rd{bytes, bytes + len};
-        rd.take(G2B); rd.take(G1B); rd.take(G2B); rd.take(G1B); rd.take(G2B);
-        const u64 l = rd.len(G1B);
-        rd.take(l * G1B);
-        const u64 M = rd.len(G1B);
-        rd.take(M * G1B);
-        const u64 Mb = rd.len(G2B);
-        rd.take(Mb * G2B);
-        const u64 n1 = rd.len(G1B);
-        const uint8_t* c1_q = rd.take(n1 * G1B);
-        const u64 Mc2 = rd.len(G1B);
-        rd.take(Mc2 * G1B);
-        rd.take(G1B); rd.take(G2B);
-        const uint8_t* g_ab_gamma_z = rd.take(G1B);
-        rd.take(G1B);
-        const u64 tl = rd.len(G1B);
-        const uint8_t* t_q = rd.take(tl * G1B);
-        require(rd.p == rd.e, ZKHIP_ERR_PARSE, "trailing bytes after proving key");
-        require(l >= 1 && M >= l && Mb == M && Mc2 == M && n1 == M - l && tl >= 2 && ((tl - 1) & (tl - 2)) == 0 && M + 2 < ((u64)1 << 31), ZKHIP_ERR_PARSE,
-                "inconsistent query lengths in GM17 proving key");
-        const u64 D = tl - 1;
-        dims->m = M; dims->w = n1; dims->l = l; dims->hlen = tl; dims->N = D; dims->logN = ilog2_floor(D);
-        upload_decoded<2>(ctx, l_aff, M + 2, c1_q, n1, l, g_ab_gamma_z, M);
-        upload_decoded<2>(ctx, h_aff, D, t_q, D, 0, nullptr, 0);
     }
     // a member's share of a binding computed elsewhere: its ranges of the whole-range level-0 arrays
     static void install_bound_ranges(zkhip_ctx* ctx, zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* h_full, size_t h_len, const uint8_t* l_full, size_t l_len,
@@ -1436,10 +1528,124 @@ struct PkLoader {
         install_bound(ctx, pk, h_full + pk->h_lo * g1, l_full + pk->z_lo * g1, false, fp);
         pk->bound_uid = cs->uid;
     }
+    // ---- device-layout image of a loaded key (PkImageHeader): level 0 of the five tables, and of H' / L' if the key was bound ----
+    static u64 export_size(const zkhip_pk* pk_) {
+        zkhip_pk* pk = const_cast<zkhip_pk*>(pk_);
+        u64 t = sizeof(PkImageHeader) + pk->delta_g1_canon.size() + pk->g_gamma2_z2_canon.size();
+        for_each_table(pk, [&](int, DBuf&, auto f, u64, u64 n) { t += table_bytes<typename decltype(f)::type>(n, 1); });
+        if (pk->h_bound.p && pk->l_bound.p) t += table_bytes<Fq>(pk->h_n, 1) + table_bytes<Fq>(pk->z_n, 1);
+        return t;
+    }
+    static void export_image(zkhip_pk* pk, uint8_t* out, u64 cap) {
+        zkhip_ctx* ctx = pk->ctx;
+        require(cap >= export_size(pk), ZKHIP_ERR_BAD_ARG, "output buffer too small (see zkhip_pk_export_size)");
+        PkImageHeader h;
+        memset(&h, 0, sizeof(h));
+        memcpy(h.magic, PK_IMAGE_MAGIC, 8);
+        h.curve = pk->curve; h.scheme = pk->scheme;
+        h.m = pk->m; h.w = pk->w; h.l = pk->l; h.hlen = pk->hlen; h.N = pk->N;
+        h.logN = pk->logN; h.c_z = pk->c_z; h.c_h = pk->c_h; h.sets = pk->s_z | (pk->s_h << 8);
+        h.rank = pk->rank; h.world = pk->world;
+        h.ntt_split = pk->ntt_log1;
+        h.z_lo = pk->z_lo; h.z_n = pk->z_n; h.h_lo = pk->h_lo; h.h_n = pk->h_n;
+        h.len_delta = pk->delta_g1_canon.size(); h.len_g2z2 = pk->g_gamma2_z2_canon.size();
+        const bool with_bound = pk->h_bound.p && pk->l_bound.p;
+        if (with_bound) {
+            h.len_bound[0] = table_bytes<Fq>(pk->h_n, 1);
+            h.len_bound[1] = table_bytes<Fq>(pk->z_n, 1);
+            h.bound_fp[0] = pk->bound_fp[0]; h.bound_fp[1] = pk->bound_fp[1];
+        }
+        uint8_t* p = out + sizeof(h);
+        memcpy(p, pk->delta_g1_canon.data(), h.len_delta); p += h.len_delta;
+        memcpy(p, pk->g_gamma2_z2_canon.data(), h.len_g2z2); p += h.len_g2z2;
+        for_each_table(pk, [&](int k, DBuf& b, auto f, u64, u64 n) {
+            h.len_buf[k] = table_bytes<typename decltype(f)::type>(n, 1);
+            dev_d2h(p, b.p, h.len_buf[k], ctx->stream);     // level 0 leads every table
+            p += h.len_buf[k];
+        });
+        memcpy(out, &h, sizeof(h));
+        if (with_bound) {
+            dev_d2h(p, pk->h_bound.p, h.len_bound[0], ctx->stream); p += h.len_bound[0];
+            dev_d2h(p, pk->l_bound.p, h.len_bound[1], ctx->stream); p += h.len_bound[1];
+        }
+        stream_sync(ctx->stream);
+    }
+    // `pk`: a fresh key of this curve and context; the caller has checked the length against the header's size, the magic and the curve id
+    static void import_image(zkhip_ctx* ctx, const uint8_t* bytes, size_t len, zkhip_pk* pk) {
+        PkImageHeader h;
+        memcpy(&h, bytes, sizeof(h));
+        require(h.scheme == 0 || h.scheme == 1, ZKHIP_ERR_PARSE, "key image: unknown scheme");
+        u64 total = sizeof(PkImageHeader), rest = len - sizeof(PkImageHeader);
+        const u64 parts[9] = {h.len_delta, h.len_g2z2, h.len_buf[0], h.len_buf[1], h.len_buf[2], h.len_buf[3], h.len_buf[4], h.len_bound[0], h.len_bound[1]};
+        for (u64 part : parts) {
+            require(part <= rest, ZKHIP_ERR_PARSE, "key image truncated");
+            rest -= part;
+            total += part;
+        }
+        require(total == len, ZKHIP_ERR_PARSE, "trailing bytes after key image");
+        int s_z = h.sets & 0xff, s_h = (h.sets >> 8) & 0xff;
+        require(h.world >= 1 && h.rank < h.world && h.logN >= 0 && h.logN <= 3 * NTT_MAX_SUBLOG && h.N == ((u64)1 << h.logN) && h.z_n <= h.m + 2 &&
+                    h.h_n <= h.N && h.c_z >= 2 && h.c_z <= MSM_MAX_C && h.c_h >= 2 && h.c_h <= MSM_MAX_C && s_z >= 1 && s_h >= 1 && (h.sets >> 16) == 0,
+                ZKHIP_ERR_PARSE, "key image: inconsistent header");
+        pk->scheme = h.scheme;
+        pk->m = h.m; pk->w = h.w; pk->l = h.l; pk->hlen = h.hlen; pk->N = h.N; pk->logN = h.logN;
+        pk->c_z = h.c_z; pk->c_h = h.c_h; pk->rank = h.rank; pk->world = h.world;
+        pk->z_lo = h.z_lo; pk->z_n = h.z_n; pk->h_lo = h.h_lo; pk->h_n = h.h_n;
+        pk->ntt_log1 = h.ntt_split;
+        auto shape_z = [&](int sets) { return msm_shape(ctx, h.z_n, C::Fr::Params::BITS, true, h.c_z, sets); };
+        auto shape_h = [&](int sets) { return msm_shape(ctx, h.h_n, C::Fr::Params::BITS, true, h.c_h, sets); };
+        // the index ranges must lie inside the key and the five base arrays must have exactly the size the ranges imply:
+        // the kernels trust these numbers
+        bool sizes_ok = h.m + 2 < ((u64)1 << 31) && h.z_lo <= h.m + 2 && h.z_n <= h.m + 2 - h.z_lo && h.h_lo <= h.N && h.h_n <= h.N - h.h_lo &&
+                        h.len_delta <= 4096 && h.len_g2z2 <= 4096;
+        for_each_table(pk, [&](int k, DBuf&, auto f, u64, u64 n) {
+            sizes_ok = sizes_ok && h.len_buf[k] == table_bytes<typename decltype(f)::type>(n, 1);
+        });
+        const bool with_bound = h.len_bound[0] || h.len_bound[1];
+        if (with_bound)
+            sizes_ok = sizes_ok && h.len_bound[0] == table_bytes<Fq>(h.h_n, 1) && h.len_bound[1] == table_bytes<Fq>(h.z_n, 1) && (h.bound_fp[0] | h.bound_fp[1]) != 0;
+        require(sizes_ok, ZKHIP_ERR_PARSE, "key image: array sizes do not match the header");
+        require(get_plan<C>(ctx, h.logN)->split() == h.ntt_split, ZKHIP_ERR_PARSE,
+                "key image: written under another NTT split (NTT_SINGLE_MAX_LOG / NTT_MAX_SUBLOG) than this context uses; re-import the proving key");
+        // The image carries level 0 only and the window multiples are recomputed here, so how many of them THIS device keeps is this
+        // context's decision, not the exporter's: ZKHIP_TUNE_MSM_SETS if set, else the header's count, doubled until the tables fit
+        // the budget of finish_tables (an image written on an empty 288 GB device must still load beside other tenants, with more
+        // bucket sets instead of an allocation failure) — each MSM clamped to its own number of windows
+        {
+            const int W_z = shape_z(1).W, W_h = shape_h(1).W;
+            if (ctx->msm_sets) s_z = std::min(ctx->msm_sets, W_z), s_h = std::min(ctx->msm_sets, W_h);
+            const u64 budget = msm_table_budget(ctx, h.z_n, h.h_n, h.N, W_z, shape_z(1).K);
+            while (!ctx->msm_sets) {
+                if (tables_need(pk, shape_z(s_z), shape_h(s_h)) <= budget || (s_z >= W_z && s_h >= W_h)) break;
+                s_z = std::min(2 * s_z, W_z);
+                s_h = std::min(2 * s_h, W_h);
+            }
+        }
+        // (c, sets) must be a shape this context's sort can run
+        const MsmShape shz = shape_z(s_z), shh = shape_h(s_h);
+        require(shz.c == h.c_z && (int)shz.sets == s_z && shh.c == h.c_h && (int)shh.sets == s_h, ZKHIP_ERR_PARSE,
+                "key image: window width / bucket sets not usable under this context's settings; re-import the proving key");
+        pk->s_z = s_z; pk->s_h = s_h;
+        const uint8_t* p = bytes + sizeof(h);
+        pk->delta_g1_canon.assign(p, p + h.len_delta); p += h.len_delta;
+        pk->g_gamma2_z2_canon.assign(p, p + h.len_g2z2); p += h.len_g2z2;
+        for_each_table(pk, shz, shh, [&](int k, DBuf& b, auto f, u64, u64 n, const MsmShape& sh) {
+            b.ensure(table_bytes<typename decltype(f)::type>(n, sh.levels));
+            const uint8_t* src = p;
+            dev_h2d_fill(b.p, h.len_buf[k], 64, ctx->stream, [src](char* out, size_t off, size_t len) { memcpy(out, src + off, len); });
+            p += h.len_buf[k];
+        });
+        stream_sync(ctx->stream);
+        table_levels(ctx, pk);                     // recompute the window multiples behind level 0
+        // ... and behind level 0 of H' / L'; attached to a system by zkhip_pk_bind_r1cs (fingerprint)
+        if (with_bound) install_bound(ctx, pk, p, p + h.len_bound[0], false, h.bound_fp);
+    }
     static void count_points_at_infinity(zkhip_ctx* ctx, zkhip_pk* pk) {
-        const u64 cnt[5] = {count_infinite<Fq>(ctx, pk->a_ext.p, pk->z_n), count_infinite<Fq>(ctx, pk->b1_ext.p, pk->z_n), count_infinite<Fq>(ctx, pk->l_ext.p, pk->z_n),
-                            count_infinite<Fq2>(ctx, pk->b2_ext.p, pk->z_n), count_infinite<Fq>(ctx, pk->h_sigma.p, pk->h_n)};
-        for (int k = 0; k < 5; ++k) pk->inf_many[k] = cnt[k] * 2048 > (k == 4 ? pk->h_n : pk->z_n);
+        u64 cnt[5];
+        for_each_table(pk, [&](int k, DBuf& b, auto f, u64, u64 n) {
+            cnt[k] = count_infinite<typename decltype(f)::type>(ctx, b.p, n);
+            pk->inf_many[k] = cnt[k] * 2048 > n;
+        });
         // the thinned list (zkhip_pk::thin_mask): ZKHIP_TUNE_B_SORT 0 = the tables a tenth of whose bases are at infinity, if leaving
         // out what they share drops a tenth of the list; 1 = the families the key formats predict, whatever the counts; 2 = never
         const bool gm17 = pk->scheme == 1;
@@ -1454,10 +1660,9 @@ struct PkLoader {
             const size_t words = (size_t)((pk->z_n + 31) / 32);
             pk->thin_keep.ensure(words * 4);
             dev_memset(pk->thin_keep.p, 0, words * 4, ctx->stream);
-            if (family & 1) mark_finite<Fq>(ctx, pk->a_ext.p, pk->z_n, ptr<u32>(pk->thin_keep));
-            if (family & 2) mark_finite<Fq>(ctx, pk->b1_ext.p, pk->z_n, ptr<u32>(pk->thin_keep));
-            if (family & 4) mark_finite<Fq>(ctx, pk->l_ext.p, pk->z_n, ptr<u32>(pk->thin_keep));
-            if (family & 8) mark_finite<Fq2>(ctx, pk->b2_ext.p, pk->z_n, ptr<u32>(pk->thin_keep));
+            for_each_table(pk, [&](int k, DBuf& b, auto f, u64, u64 n) {
+                if (family >> k & 1) mark_finite<typename decltype(f)::type>(ctx, b.p, n, ptr<u32>(pk->thin_keep));      // (bits 0 .. 3: the tables over z)
+            });
             std::vector<u32> host(words);
             dev_d2h(host.data(), pk->thin_keep.p, words * 4, ctx->stream);
             stream_sync(ctx->stream);
@@ -1475,7 +1680,7 @@ struct PkLoader {
     template <class F>
     static void to_table(zkhip_ctx* ctx, DBuf& buf, u64 lo, u64 count, const MsmShape& sh) {
         DBuf out;
-        out.ensure(std::max<u64>(count, 1) * (u64)sh.levels * packed_point_bytes<F>());
+        out.ensure(table_bytes<F>(count, sh.levels));
         if (count) points_to_packed<F>(ctx, ptr<Aff<F>>(buf) + lo, out.p, count);
         stream_sync(ctx->stream);
         buf.swap(out);
@@ -1692,10 +1897,7 @@ struct Prover {
     // sl.va + (1 - half) * N before enqueue_tail
     static void enqueue_head(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
                              const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1) {
-        require(pk->curve == C::ID && cs->curve == C::ID, ZKHIP_ERR_BAD_ARG, "curve mismatch between key and constraint system");
-        require(pk->scheme == 0, ZKHIP_ERR_BAD_ARG, "this is a GM17 proving key: use zkhip_prove_gm17");
-        require(pk->m == cs->l + cs->w && pk->w == cs->w && pk->N == cs->N, ZKHIP_ERR_BAD_ARG,
-                "proving key does not match the constraint system (m, w or domain size)");
+        PkLoader<C>::check_match(pk, cs, 0);
         const bool bound = is_bound(pk, cs);
         require(half < 0 || (bound && half <= 1), ZKHIP_ERR_BAD_ARG, "internal: only a proof over a bound key splits its witness map");
         Fr rr = fe_from_bytes_canon<Fr>(r), ss = fe_from_bytes_canon<Fr>(s_);
@@ -2350,13 +2552,15 @@ struct Prover {
 // ------------------------------------------------------------------ per-curve entry points
 namespace zk {
 struct CurveOps {
-    void (*pk_load)(zkhip_ctx*, const uint8_t*, size_t, zkhip_pk*);
-    void (*pk_table_levels)(zkhip_ctx*, zkhip_pk*);
+    void (*pk_load)(zkhip_ctx*, int scheme, const uint8_t*, size_t, zkhip_pk*);
+    u64 (*pk_export_size)(const zkhip_pk*);
+    void (*pk_export)(zkhip_pk*, uint8_t*, u64);
+    void (*pk_import)(zkhip_ctx*, const uint8_t*, size_t, zkhip_pk*);
     void (*pk_bind)(zkhip_ctx*, zkhip_pk*, const zkhip_r1cs*);
     void (*pk_bind_check)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*);
+    void (*pk_unbind)(zkhip_pk*);
     void (*bound_level0_from_file)(zkhip_ctx*, int scheme, const zkhip_r1cs*, const uint8_t*, size_t, std::vector<uint8_t>&, std::vector<uint8_t>&, u64 fp[2]);
     void (*install_bound_ranges)(zkhip_ctx*, zkhip_pk*, const zkhip_r1cs*, const uint8_t*, size_t, const uint8_t*, size_t, const u64 fp[2]);
-    void (*install_bound)(zkhip_ctx*, zkhip_pk*, const void*, const void*, bool on_device, const u64 fp[2]);
     void (*r1cs_fingerprint)(zkhip_ctx*, const zkhip_r1cs*, u64 fp[2]);
     bool (*can_split)(const zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*);
     void (*split_begin)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, const uint8_t*, int half);
@@ -2388,7 +2592,6 @@ struct CurveOps {
     void (*field_op)(zkhip_ctx*, int field, int op, u64, const uint8_t*, const uint8_t*, uint8_t*);
     void (*setup)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, u64);
     // GM17 (gm17.cuh)
-    void (*gm17_pk_load)(zkhip_ctx*, const uint8_t*, size_t, zkhip_pk*);
     void (*gm17_prove)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, uint8_t*, zkhip_timings*);
     void (*gm17_prove_batch)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, u32, const uint8_t*, void* const*, const uint8_t*, uint8_t*,
                              zkhip_timings*);
@@ -2396,10 +2599,6 @@ struct CurveOps {
     u64 (*gm17_key_bytes)(u64, u64, u64);
     void (*gm17_prove_partial)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, uint8_t*, zkhip_timings*);
     void (*gm17_combine)(const zkhip_pk*, u32, const uint8_t*, const uint8_t*, uint8_t*);
-    int (*ntt_log1)(zkhip_ctx*, int logN);   // the split of this context's NTT plan for a domain (what a key's h order depends on)
-    bool (*msm_shape_ok)(const zkhip_ctx*, u64 n, int c, int sets);   // (c, sets) of a key usable as they are under this context's settings
-    size_t packed_g1_bytes;  // size of one resident G1 base (G2: twice that): lets zkhip_pk_import validate an image's shape
-    int fr_bits;             // scalar width: the number of table levels follows from it and the window width
 };
 // fields of zkhip_field_op: 0 Fr, 1 Fq, 2 Fq2 in the saturated form; 3 Fq2, 4 Fr, 5 Fq in the unsaturated limbs of the MSM kernels
 // and the transform passes (k_field_op_fq2, k_field_op_unsat)
@@ -2417,24 +2616,17 @@ static void field_op_dispatch(zkhip_ctx* ctx, int field, int op, u64 count, cons
     else P::template field_op_api<Fq>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq* x, Fq* y) { ZK_LAUNCH((k_field_op_unsat<typename Fq::Params>), g, t, 0, s, x, y, x, count, op); });
 }
 template <class C>
-static int ntt_log1_of(zkhip_ctx* ctx, int logN) { return get_plan<C>(ctx, logN)->split(); }
-template <class C>
-static bool msm_shape_ok_of(const zkhip_ctx* ctx, u64 n, int c, int sets) {
-    const MsmShape sh = msm_shape(ctx, n, C::Fr::Params::BITS, true, c, sets);
-    return sh.c == c && (int)sh.sets == sets;
-}
-template <class C>
 static CurveOps make_curve_ops() {
     CurveOps o;
-    o.msm_shape_ok = &msm_shape_ok_of<C>;
-    o.ntt_log1 = &ntt_log1_of<C>;
-    o.pk_load = &PkLoader<C>::load;
-    o.pk_table_levels = &PkLoader<C>::table_levels;
+    o.pk_load = &PkLoader<C>::load_file;
+    o.pk_export_size = &PkLoader<C>::export_size;
+    o.pk_export = &PkLoader<C>::export_image;
+    o.pk_import = &PkLoader<C>::import_image;
     o.pk_bind = &PkLoader<C>::bind;
     o.pk_bind_check = &PkLoader<C>::bind_check;
+    o.pk_unbind = &PkLoader<C>::unbind;
     o.bound_level0_from_file = &PkLoader<C>::bound_level0_from_file;
     o.install_bound_ranges = &PkLoader<C>::install_bound_ranges;
-    o.install_bound = &PkLoader<C>::install_bound;
     o.r1cs_fingerprint = &PkLoader<C>::r1cs_fingerprint;
     o.can_split = &Prover<C>::can_split;
     o.split_begin = &Prover<C>::split_begin;
@@ -2461,15 +2653,12 @@ static CurveOps make_curve_ops() {
     o.msm_g2 = &Prover<C>::template msm_api<typename C::Fq2, 4>;
     o.field_op = &field_op_dispatch<C>;
     o.setup = &Setup<C>::run;
-    o.gm17_pk_load = &Gm17<C>::load;
     o.gm17_prove = &Gm17<C>::prove;
     o.gm17_prove_batch = &Gm17<C>::prove_batch;
     o.gm17_setup = &Gm17<C>::setup;
     o.gm17_key_bytes = &Gm17<C>::key_bytes;
     o.gm17_prove_partial = &Gm17<C>::prove_partial;
     o.gm17_combine = &Gm17<C>::combine;
-    o.packed_g1_bytes = packed_point_bytes<typename C::Fq>();
-    o.fr_bits = C::Fr::Params::BITS;
     return o;
 }
 const CurveOps* curve_ops_bn254();

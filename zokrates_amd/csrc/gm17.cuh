@@ -24,9 +24,10 @@
 // the Groth16 prover.  ark folds 2 d1 U + d1^2 Z - d2 into the quotient instead; the sums are the same group elements.
 //
 // The proof-slot driver is the Groth16 prover's (core.cuh, Prover<C>: open_slot, stage_z, start_z_lanes, lanes_after_h, collect,
-// run_batch, emit_partial, hand_out_sums, write_proof; the slot's layout is SlotSums<C>).  What this scheme supplies: the key
-// loader, the middle of `enqueue` (SAP rows and the extension on the main stream, the quotient's transforms on the context's NTT
-// stream) and the host formula for C (`assemble`).
+// run_batch, emit_partial, hand_out_sums, write_proof; the slot's layout is SlotSums<C>), and so is the key loader (PkLoader<C>:
+// parse_gm17 maps this scheme's key file to the lanes above, load and check_match serve both schemes).  What this scheme supplies:
+// the middle of `enqueue` (SAP rows and the extension on the main stream, the quotient's transforms on the context's NTT stream), the
+// host formula for C (`assemble`) and the setup.
 #pragma once
 
 namespace zk {
@@ -98,19 +99,6 @@ __global__ void k_gm17_coeffs(const F* __restrict__ a, const F* __restrict__ c, 
     vq[i] = fe_from_mont(v);
 }
 
-struct SapShape {
-    u64 M, D0, D;
-    int logD;
-};
-static inline SapShape sap_shape(u64 n, u64 l, u64 w) {
-    SapShape s;
-    s.M = 1 + 2 * (l - 1) + w + n;
-    s.D0 = 2 * n + 2 * (l - 1) + 1;
-    s.logD = ilog2_ceil(s.D0);
-    s.D = (u64)1 << s.logD;
-    return s;
-}
-
 template <class C>
 struct Gm17 {
     typedef typename C::Fr Fr;
@@ -121,65 +109,6 @@ struct Gm17 {
     static constexpr int FQB = Fq::BYTES;
     static constexpr int G1B = 2 * FQB, G2B = 4 * FQB;
 
-    // ------------------------------------------------------------ key load
-    // ark `serialize_unchecked` of ark_gm17::ProvingKey: vk{h_g2, g_alpha_g1, h_beta_g2, g_gamma_g1, h_gamma_g2, query[]},
-    // a_query[], b_query[] (G2), c_query_1[], c_query_2[], g_gamma_z, h_gamma_z (G2), g_ab_gamma_z, g_gamma2_z2,
-    // g_gamma2_z_t[]
-    static void load(zkhip_ctx* ctx, const uint8_t* bytes, size_t len, zkhip_pk* pk) {
-        typename L::Rd rd{bytes, bytes + len};
-        rd.take(G2B); rd.take(G1B); rd.take(G2B); rd.take(G1B); rd.take(G2B);   // vk points (verifier only)
-        const u64 l = rd.len(G1B);
-        rd.take(l * G1B);                                                        // vk.query (verifier only)
-        const u64 M = rd.len(G1B);
-        const uint8_t* a_q = rd.take(M * G1B);
-        const u64 Mb = rd.len(G2B);
-        const uint8_t* b_q = rd.take(Mb * G2B);
-        const u64 n1 = rd.len(G1B);
-        const uint8_t* c1_q = rd.take(n1 * G1B);
-        const u64 Mc2 = rd.len(G1B);
-        const uint8_t* c2_q = rd.take(Mc2 * G1B);
-        const uint8_t* g_gamma_z = rd.take(G1B);
-        const uint8_t* h_gamma_z = rd.take(G2B);
-        const uint8_t* g_ab_gamma_z = rd.take(G1B);
-        const uint8_t* g_gamma2_z2 = rd.take(G1B);
-        const u64 tl = rd.len(G1B);
-        const uint8_t* t_q = rd.take(tl * G1B);
-        require(rd.p == rd.e, ZKHIP_ERR_PARSE, "trailing bytes after proving key");
-        require(l >= 1 && M >= l && Mb == M && Mc2 == M && n1 == M - l, ZKHIP_ERR_PARSE, "inconsistent query lengths in GM17 proving key");
-        require(tl >= 2 && ((tl - 1) & (tl - 2)) == 0, ZKHIP_ERR_PARSE, "g_gamma2_z_t length - 1 is not a power of two");
-        require(M + 2 < ((u64)1 << 31), ZKHIP_ERR_BAD_ARG, "too many variables");
-        const u64 D = tl - 1;
-        pk->scheme = 1;
-        pk->m = M; pk->w = n1; pk->l = l; pk->hlen = tl; pk->N = D; pk->logN = ilog2_floor(D);
-        NttPlan<C>* plan = get_plan<C>(ctx, pk->logN);
-        pk->ntt_log1 = plan->split();
-        pk->g_gamma2_z2_canon.assign(g_gamma2_z2, g_gamma2_z2 + G1B);
-
-        const u64 me = M + 2;   // extended by the (., rho) pair and one unused slot (same shape as the Groth16 key)
-        L::template upload_decoded<2>(ctx, pk->a_ext, me, a_q, M, 0, g_gamma_z, M);
-        L::template upload_decoded<2>(ctx, pk->b1_ext, me, c2_q, M, 0, nullptr, 0);
-        L::template upload_decoded<2>(ctx, pk->l_ext, me, c1_q, n1, l, g_ab_gamma_z, M);
-        L::template upload_decoded<4>(ctx, pk->b2_ext, me, b_q, M, 0, h_gamma_z, M);
-        // g_gamma2_z_t[0..D), permuted into the sigma order the NTT pipeline leaves the quotient in (entry D pairs with
-        // the d1^2 coefficient of ark's h, which the restructured prover does not produce)
-        DBuf t_nat;
-        L::template upload_decoded<2>(ctx, t_nat, D, t_q, D, 0, nullptr, 0);
-        pk->h_sigma.ensure(D * G1B);
-        ZK_LAUNCH((k_sigma_gather_points<Aff<Fq>>), dim3(blocks_for(D, 256)), dim3(256), 0, ctx->stream, ptr<Aff<Fq>>(t_nat),
-                  ptr<Aff<Fq>>(pk->h_sigma), D, D, plan->N1, plan->N2, plan->N3);
-        stream_sync(ctx->stream);
-        t_nat.release();
-        L::finish_tables(ctx, pk, me, D);
-    }
-
-    static void check_match(const zkhip_pk* pk, const zkhip_r1cs* cs) {
-        require(pk->curve == C::ID && cs->curve == C::ID, ZKHIP_ERR_BAD_ARG, "curve mismatch between key and constraint system");
-        require(pk->scheme == 1, ZKHIP_ERR_BAD_ARG, "this is a Groth16 proving key: use zkhip_prove_g16");
-        const SapShape sh = sap_shape(cs->n, cs->l, cs->w);
-        require(pk->m == sh.M && pk->l == cs->l && pk->N == sh.D, ZKHIP_ERR_BAD_ARG,
-                "GM17 proving key does not match the constraint system (SAP variables, instance size or domain)");
-    }
-
     // ------------------------------------------------------------ prover
     static Fr add_mod(const Fr& a, const Fr& b) {   // canonical integers
         return fe_from_mont(fe_add(fe_to_mont(a), fe_to_mont(b)));
@@ -189,7 +118,7 @@ struct Gm17 {
     // context's NTT stream behind them
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
                         const uint8_t* d1, const uint8_t* r, int check_idx = -1) {
-        check_match(pk, cs);
+        L::check_match(pk, cs, 1);
         const u64 m = cs->l + cs->w, n = cs->n, l = cs->l, M = pk->m, D = pk->N;
         Fr dd = fe_from_bytes_canon<Fr>(d1), rr = fe_from_bytes_canon<Fr>(r);
         require(canon_lt_mod(dd) && canon_lt_mod(rr), ZKHIP_ERR_BAD_ARG, "d1 or r not a canonical field element");

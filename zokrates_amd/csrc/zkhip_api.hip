@@ -78,6 +78,41 @@ static __global__ void k_clock_probe(unsigned long long ticks, unsigned long lon
 }
 #endif
 
+// a proving-key file of either scheme, resident: the whole key (rank 0 of 1) or one shard
+static int32_t load_key(zkhip_ctx* ctx, int32_t curve, int scheme, const uint8_t* bytes, size_t len, uint32_t rank, uint32_t world, zkhip_pk** out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {
+        require(bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        require(world >= 1 && world <= 64 && rank < world, ZKHIP_ERR_BAD_ARG, "rank / world out of range (1 <= world <= 64)");
+        std::unique_ptr<zkhip_pk> pk(new zkhip_pk());
+        pk->curve = curve;
+        pk->ctx = ctx;
+        pk->rank = rank;
+        pk->world = world;
+        ops_for(curve)->pk_load(ctx, scheme, bytes, len, pk.get());
+        *out = pk.release();
+    });
+}
+// What zkhip_pk_bind_r1cs and zkhip_pk_bind_r1cs_shard share.  The argument checks come first and never touch the key: a call that is
+// refused leaves an earlier binding (seconds of work) as it was; only a failure INSIDE the rebuild — `rebuild(ops, started)` sets
+// `started` before it drops the old tables — leaves the key as loaded
+template <class Fn>
+static int32_t bind_key(zkhip_ctx* ctx, zkhip_pk* pk, const zkhip_r1cs* r1cs, bool args_ok, Fn&& rebuild) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    bool started = false;
+    const int32_t rc = guarded(ctx, [&] {
+        require(pk && r1cs && args_ok, ZKHIP_ERR_BAD_ARG, "null argument");
+        require(pk->ctx == ctx && r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "key / constraint system belong to another context");
+        for (auto& sl : ctx->slots) require(!sl.busy, ZKHIP_ERR_BAD_ARG, "a proof is in flight in this context");
+        const CurveOps* ops = ops_for(pk->curve);
+        ops->pk_bind_check(ctx, pk, r1cs);
+        rebuild(ops, started);
+    });
+    if (rc != ZKHIP_OK && pk && started) zkhip_pk_unbind(pk);   // whatever failed half-way: the key is as it was loaded
+    return rc;
+}
+
 extern "C" {
 
 int32_t zkhip_init(int32_t hw_queues) {
@@ -273,78 +308,35 @@ int32_t zkhip_describe(const zkhip_ctx* ctx, char* buf, size_t cap) {
     return ZKHIP_OK;
 }
 
-int32_t zkhip_pk_load_g16(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_pk** out) {
-    if (!ctx) return ZKHIP_ERR_BAD_ARG;
-    return guarded(ctx, [&] {
-        require(bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
-        *out = nullptr;
-        std::unique_ptr<zkhip_pk> pk(new zkhip_pk());
-        pk->curve = curve;
-        pk->ctx = ctx;
-        ops_for(curve)->pk_load(ctx, bytes, len, pk.get());
-        *out = pk.release();
-    });
-}
+int32_t zkhip_pk_load_g16(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_pk** out) { return load_key(ctx, curve, 0, bytes, len, 0, 1, out); }
 int32_t zkhip_pk_load_g16_shard(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, uint32_t rank, uint32_t world, zkhip_pk** out) {
-    if (!ctx) return ZKHIP_ERR_BAD_ARG;
-    return guarded(ctx, [&] {
-        require(bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
-        *out = nullptr;
-        require(world >= 1 && world <= 64 && rank < world, ZKHIP_ERR_BAD_ARG, "rank / world out of range (1 <= world <= 64)");
-        std::unique_ptr<zkhip_pk> pk(new zkhip_pk());
-        pk->curve = curve;
-        pk->ctx = ctx;
-        pk->rank = rank;
-        pk->world = world;
-        ops_for(curve)->pk_load(ctx, bytes, len, pk.get());
-        *out = pk.release();
-    });
+    return load_key(ctx, curve, 0, bytes, len, rank, world, out);
+}
+int32_t zkhip_pk_load_gm17(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_pk** out) { return load_key(ctx, curve, 1, bytes, len, 0, 1, out); }
+int32_t zkhip_pk_load_gm17_shard(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, uint32_t rank, uint32_t world, zkhip_pk** out) {
+    return load_key(ctx, curve, 1, bytes, len, rank, world, out);
 }
 void zkhip_pk_free(zkhip_pk* pk) { delete pk; }
 int32_t zkhip_pk_bind_r1cs(zkhip_ctx* ctx, zkhip_pk* pk, const zkhip_r1cs* r1cs) {
-    if (!ctx) return ZKHIP_ERR_BAD_ARG;
-    // the argument checks come first and never touch the key: a call that is refused leaves an earlier binding (seconds of work)
-    // as it was; only a failure INSIDE the rebuild — which starts by dropping the old tables — leaves the key as loaded
-    bool started = false;
-    const int32_t rc = guarded(ctx, [&] {
-        require(pk && r1cs, ZKHIP_ERR_BAD_ARG, "null argument");
-        require(pk->ctx == ctx && r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "key / constraint system belong to another context");
-        for (auto& sl : ctx->slots) require(!sl.busy, ZKHIP_ERR_BAD_ARG, "a proof is in flight in this context");
-        ops_for(pk->curve)->pk_bind_check(ctx, pk, r1cs);
+    return bind_key(ctx, pk, r1cs, true, [&](const CurveOps* ops, bool& started) {
         started = true;
-        ops_for(pk->curve)->pk_bind(ctx, pk, r1cs);
+        ops->pk_bind(ctx, pk, r1cs);
     });
-    if (rc != ZKHIP_OK && pk && started) zkhip_pk_unbind(pk);   // whatever failed half-way: the key is as it was loaded
-    return rc;
 }
 int32_t zkhip_pk_unbind(zkhip_pk* pk) {
     if (!pk) return ZKHIP_ERR_BAD_ARG;
-    return guarded(pk->ctx, [&] {
-        pk->bound_uid = 0;
-        pk->bound_fp[0] = pk->bound_fp[1] = 0;
-        pk->h_bound.release();
-        pk->l_bound.release();
-    });
+    return guarded(pk->ctx, [&] { ops_for(pk->curve)->pk_unbind(pk); });
 }
 // a shard of a multi-GPU key (or a whole key): the binding computed from the key FILE — the transforms need every base once — of
 // which this key keeps its own index ranges
 int32_t zkhip_pk_bind_r1cs_shard(zkhip_ctx* ctx, zkhip_pk* pk, const zkhip_r1cs* r1cs, const uint8_t* key_bytes, size_t len) {
-    if (!ctx) return ZKHIP_ERR_BAD_ARG;
-    bool started = false;
-    const int32_t rc = guarded(ctx, [&] {
-        require(pk && r1cs && key_bytes, ZKHIP_ERR_BAD_ARG, "null argument");
-        require(pk->ctx == ctx && r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "key / constraint system belong to another context");
-        for (auto& sl : ctx->slots) require(!sl.busy, ZKHIP_ERR_BAD_ARG, "a proof is in flight in this context");
-        const CurveOps* ops = ops_for(pk->curve);
-        ops->pk_bind_check(ctx, pk, r1cs);
+    return bind_key(ctx, pk, r1cs, key_bytes != nullptr, [&](const CurveOps* ops, bool& started) {
         std::vector<uint8_t> h_host, l_host;
         u64 fp[2];
         ops->bound_level0_from_file(ctx, pk->scheme, r1cs, key_bytes, len, h_host, l_host, fp);
         started = true;
         ops->install_bound_ranges(ctx, pk, r1cs, h_host.data(), h_host.size(), l_host.data(), l_host.size(), fp);
     });
-    if (rc != ZKHIP_OK && pk && started) zkhip_pk_unbind(pk);
-    return rc;
 }
 // One rank's share of a proof whose witness map is split between the ranks of a multi-PROCESS prover (one process per GPU): begin
 // computes this rank's half — `half` = 0: a, 1: b on the coset, N x 32 bytes (R'-form, packed) into `half_out` (host memory) — and
@@ -661,86 +653,15 @@ int32_t zkhip_prog_r1cs_load(zkhip_ctx* ctx, const zkhip_prog* prog, zkhip_r1cs*
                            prog->val[2].data(), out);
 }
 
-// ------------------------------------------------------------------ N2: device-layout image of a loaded key
-// "ZKHIPPK" + layout version; bump the version whenever the resident layout (packed points, sigma order, the extended base
-// vectors, table levels) changes: an image is only meaningful to the library build that wrote it.
-// An image holds level 0 of the five base tables; the window multiples are recomputed on the device at import (~0.1 s for a
-// 2^20 key — less than reading the 6 GiB they occupy from any disk: measured in round 3, which is why the image that carried
-// every level is gone).
-static const char PK_IMAGE_MAGIC[8] = {'Z', 'K', 'H', 'I', 'P', 'P', 'K', '5'};
-struct PkImageHeader {
-    char magic[8];
-    int32_t curve, scheme;
-    uint64_t m, w, l, hlen, N;
-    int32_t logN, c_z, c_h, sets;     // sets: s_z | s_h << 8 — which window multiples the tables hold (MsmShape::sets)
-    uint32_t rank, world;
-    int32_t ntt_split, reserved;      // the NTT split h_sigma is ordered for (zkhip_pk::ntt_log1 = NttPlan::split())
-    uint64_t z_lo, z_n, h_lo, h_n;
-    uint64_t len_delta, len_g2z2, len_buf[5];
-    // version 5: level 0 of the bound tables H' / L' (this key's index ranges) when the key was bound at export, and the fingerprint
-    // of the constraint system they were made for — zkhip_pk_bind_r1cs on the imported key attaches them when the system's
-    // fingerprint agrees and costs a checksum instead of the transforms (0 / 0: the key was not bound)
-    uint64_t len_bound[2];            // H', L'
-    uint64_t bound_fp[2];
-};
-static DBuf* pk_bufs(zkhip_pk* pk, int k) { DBuf* b[5] = {&pk->a_ext, &pk->b1_ext, &pk->l_ext, &pk->b2_ext, &pk->h_sigma}; return b[k]; }
-static int pk_levels(int curve, int c, int sets) {
-    const int bits = ops_for(curve)->fr_bits, W = (bits + 1 + c - 1) / c;
-    return (W + sets - 1) / sets;
-}
-// bytes of table k of this key: count x levels x point size (levels = 1: what an image holds)
-static uint64_t pk_table_bytes(int curve, int k, uint64_t z_n, uint64_t h_n, int levels) {
-    const uint64_t g1b = ops_for(curve)->packed_g1_bytes;
-    const uint64_t count = std::max<uint64_t>(k == 4 ? h_n : z_n, 1), pt = k == 3 ? 2 * g1b : g1b;
-    return count * pt * (uint64_t)levels;
-}
+// ------------------------------------------------------------------ N2: device-layout image of a loaded key (core.cuh PkImageHeader)
 int32_t zkhip_pk_export_size(const zkhip_pk* pk, uint64_t* bytes) {
     if (!pk || !bytes) return ZKHIP_ERR_BAD_ARG;
-    uint64_t t = sizeof(PkImageHeader) + pk->delta_g1_canon.size() + pk->g_gamma2_z2_canon.size();
-    for (int k = 0; k < 5; ++k) t += pk_table_bytes(pk->curve, k, pk->z_n, pk->h_n, 1);
-    if (pk->h_bound.p && pk->l_bound.p) t += pk_table_bytes(pk->curve, 4, pk->z_n, pk->h_n, 1) + pk_table_bytes(pk->curve, 2, pk->z_n, pk->h_n, 1);
-    *bytes = t;
+    *bytes = ops_for(pk->curve)->pk_export_size(pk);
     return ZKHIP_OK;
 }
-int32_t zkhip_pk_export(const zkhip_pk* pk_, uint8_t* out, uint64_t cap) {
-    if (!pk_ || !out) return ZKHIP_ERR_BAD_ARG;
-    zkhip_pk* pk = const_cast<zkhip_pk*>(pk_);
-    zkhip_ctx* ctx = pk->ctx;
-    return guarded(ctx, [&] {
-        uint64_t need = 0;
-        zkhip_pk_export_size(pk, &need);
-        require(cap >= need, ZKHIP_ERR_BAD_ARG, "output buffer too small (see zkhip_pk_export_size)");
-        PkImageHeader h;
-        memset(&h, 0, sizeof(h));
-        memcpy(h.magic, PK_IMAGE_MAGIC, 8);
-        h.curve = pk->curve; h.scheme = pk->scheme;
-        h.m = pk->m; h.w = pk->w; h.l = pk->l; h.hlen = pk->hlen; h.N = pk->N;
-        h.logN = pk->logN; h.c_z = pk->c_z; h.c_h = pk->c_h; h.sets = pk->s_z | (pk->s_h << 8);
-        h.rank = pk->rank; h.world = pk->world;
-        h.ntt_split = pk->ntt_log1;
-        h.z_lo = pk->z_lo; h.z_n = pk->z_n; h.h_lo = pk->h_lo; h.h_n = pk->h_n;
-        h.len_delta = pk->delta_g1_canon.size(); h.len_g2z2 = pk->g_gamma2_z2_canon.size();
-        for (int k = 0; k < 5; ++k) h.len_buf[k] = pk_table_bytes(pk->curve, k, pk->z_n, pk->h_n, 1);
-        const bool with_bound = pk->h_bound.p && pk->l_bound.p;
-        if (with_bound) {
-            h.len_bound[0] = pk_table_bytes(pk->curve, 4, pk->z_n, pk->h_n, 1);
-            h.len_bound[1] = pk_table_bytes(pk->curve, 2, pk->z_n, pk->h_n, 1);
-            h.bound_fp[0] = pk->bound_fp[0]; h.bound_fp[1] = pk->bound_fp[1];
-        }
-        uint8_t* p = out;
-        memcpy(p, &h, sizeof(h)); p += sizeof(h);
-        memcpy(p, pk->delta_g1_canon.data(), h.len_delta); p += h.len_delta;
-        memcpy(p, pk->g_gamma2_z2_canon.data(), h.len_g2z2); p += h.len_g2z2;
-        for (int k = 0; k < 5; ++k) {
-            dev_d2h(p, pk_bufs(pk, k)->p, h.len_buf[k], ctx->stream);     // level 0 leads every table
-            p += h.len_buf[k];
-        }
-        if (with_bound) {
-            dev_d2h(p, pk->h_bound.p, h.len_bound[0], ctx->stream); p += h.len_bound[0];
-            dev_d2h(p, pk->l_bound.p, h.len_bound[1], ctx->stream); p += h.len_bound[1];
-        }
-        stream_sync(ctx->stream);
-    });
+int32_t zkhip_pk_export(const zkhip_pk* pk, uint8_t* out, uint64_t cap) {
+    if (!pk || !out) return ZKHIP_ERR_BAD_ARG;
+    return guarded(pk->ctx, [&] { ops_for(pk->curve)->pk_export(const_cast<zkhip_pk*>(pk), out, cap); });
 }
 int32_t zkhip_pk_import(zkhip_ctx* ctx, const uint8_t* bytes, size_t len, zkhip_pk** out) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
@@ -752,72 +673,10 @@ int32_t zkhip_pk_import(zkhip_ctx* ctx, const uint8_t* bytes, size_t len, zkhip_
         memcpy(&h, bytes, sizeof(h));
         require(!memcmp(h.magic, PK_IMAGE_MAGIC, 8), ZKHIP_ERR_PARSE, "not a key image of this library version (re-import the proving key)");
         const CurveOps* ops = ops_for(h.curve);   // (validates the curve id)
-        require(h.scheme == 0 || h.scheme == 1, ZKHIP_ERR_PARSE, "key image: unknown scheme");
-        uint64_t total = sizeof(PkImageHeader), rest = len - sizeof(PkImageHeader);
-        const uint64_t parts[9] = {h.len_delta, h.len_g2z2, h.len_buf[0], h.len_buf[1], h.len_buf[2], h.len_buf[3], h.len_buf[4], h.len_bound[0], h.len_bound[1]};
-        for (uint64_t part : parts) {
-            require(part <= rest, ZKHIP_ERR_PARSE, "key image truncated");
-            rest -= part;
-            total += part;
-        }
-        require(total == len, ZKHIP_ERR_PARSE, "trailing bytes after key image");
-        int s_z = h.sets & 0xff, s_h = (h.sets >> 8) & 0xff;
-        require(h.world >= 1 && h.rank < h.world && h.logN >= 0 && h.logN <= 3 * NTT_MAX_SUBLOG && h.N == ((uint64_t)1 << h.logN) && h.z_n <= h.m + 2 &&
-                    h.h_n <= h.N && h.c_z >= 2 && h.c_z <= MSM_MAX_C && h.c_h >= 2 && h.c_h <= MSM_MAX_C && s_z >= 1 && s_h >= 1 && (h.sets >> 16) == 0,
-                ZKHIP_ERR_PARSE, "key image: inconsistent header");
-        // the index ranges must lie inside the key and the five base arrays must have exactly the size the ranges imply:
-        // the kernels trust these numbers
-        bool sizes_ok = h.m + 2 < ((uint64_t)1 << 31) && h.z_lo <= h.m + 2 && h.z_n <= h.m + 2 - h.z_lo && h.h_lo <= h.N && h.h_n <= h.N - h.h_lo &&
-                        h.len_delta <= 4096 && h.len_g2z2 <= 4096;
-        for (int k = 0; k < 5 && sizes_ok; ++k) sizes_ok = h.len_buf[k] == pk_table_bytes(h.curve, k, h.z_n, h.h_n, 1);
-        const bool with_bound = h.len_bound[0] || h.len_bound[1];
-        if (with_bound)
-            sizes_ok = sizes_ok && h.len_bound[0] == pk_table_bytes(h.curve, 4, h.z_n, h.h_n, 1) && h.len_bound[1] == pk_table_bytes(h.curve, 2, h.z_n, h.h_n, 1) &&
-                       (h.bound_fp[0] | h.bound_fp[1]) != 0;
-        require(sizes_ok, ZKHIP_ERR_PARSE, "key image: array sizes do not match the header");
-        require(ops->ntt_log1(ctx, h.logN) == h.ntt_split, ZKHIP_ERR_PARSE,
-                "key image: written under another NTT split (NTT_SINGLE_MAX_LOG / NTT_MAX_SUBLOG) than this context uses; re-import the proving key");
-        // The image carries level 0 only and the window multiples are recomputed here, so how many of them THIS device keeps is this
-        // context's decision, not the exporter's: ZKHIP_TUNE_MSM_SETS if set, else the header's count, doubled until the tables fit
-        // 60 % of the free device memory (PkLoader::finish_tables' rule: an image written on an empty 288 GB device must still load
-        // beside other tenants, with more bucket sets instead of an allocation failure).
-        {
-            const int W_z = (ops->fr_bits + 1 + h.c_z - 1) / h.c_z, W_h = (ops->fr_bits + 1 + h.c_h - 1) / h.c_h;
-            if (ctx->msm_sets) s_z = std::min(ctx->msm_sets, W_z), s_h = std::min(ctx->msm_sets, W_h);
-            const uint64_t budget = msm_table_budget(ctx, h.z_n, h.h_n, h.N, W_z, 1u << (h.c_z - 1));
-            while (!ctx->msm_sets) {
-                uint64_t need = 0;
-                for (int k = 0; k < 5; ++k) need += pk_table_bytes(h.curve, k, h.z_n, h.h_n, k == 4 ? pk_levels(h.curve, h.c_h, s_h) : pk_levels(h.curve, h.c_z, s_z));
-                if (need <= budget || (s_z >= W_z && s_h >= W_h)) break;
-                s_z = std::min(2 * s_z, W_z);
-                s_h = std::min(2 * s_h, W_h);
-            }
-        }
-        // (c, sets) must be a shape this context's sort can run
-        require(ops->msm_shape_ok(ctx, h.z_n, h.c_z, s_z) && ops->msm_shape_ok(ctx, h.h_n, h.c_h, s_h), ZKHIP_ERR_PARSE,
-                "key image: window width / bucket sets not usable under this context's settings; re-import the proving key");
         std::unique_ptr<zkhip_pk> pk(new zkhip_pk());
-        pk->curve = h.curve; pk->scheme = h.scheme; pk->ctx = ctx;
-        pk->m = h.m; pk->w = h.w; pk->l = h.l; pk->hlen = h.hlen; pk->N = h.N; pk->logN = h.logN;
-        pk->c_z = h.c_z; pk->c_h = h.c_h; pk->s_z = s_z; pk->s_h = s_h; pk->rank = h.rank; pk->world = h.world;
-        pk->z_lo = h.z_lo; pk->z_n = h.z_n; pk->h_lo = h.h_lo; pk->h_n = h.h_n;
-        pk->ntt_log1 = h.ntt_split;
-        const uint8_t* p = bytes + sizeof(h);
-        pk->delta_g1_canon.assign(p, p + h.len_delta); p += h.len_delta;
-        pk->g_gamma2_z2_canon.assign(p, p + h.len_g2z2); p += h.len_g2z2;
-        for (int k = 0; k < 5; ++k) {
-            DBuf* b = pk_bufs(pk.get(), k);
-            b->ensure(pk_table_bytes(h.curve, k, h.z_n, h.h_n, k == 4 ? pk_levels(h.curve, h.c_h, s_h) : pk_levels(h.curve, h.c_z, s_z)));
-            const uint8_t* src = p;
-            dev_h2d_fill(b->p, h.len_buf[k], 64, ctx->stream, [src](char* out, size_t off, size_t len) { memcpy(out, src + off, len); });
-            p += h.len_buf[k];
-        }
-        stream_sync(ctx->stream);
-        ops->pk_table_levels(ctx, pk.get());       // recompute the window multiples behind level 0
-        if (with_bound) {                          // ... and behind level 0 of H' / L'; attached to a system by zkhip_pk_bind_r1cs (fingerprint)
-            ops->install_bound(ctx, pk.get(), p, p + h.len_bound[0], false, h.bound_fp);
-            p += h.len_bound[0] + h.len_bound[1];
-        }
+        pk->curve = h.curve;
+        pk->ctx = ctx;
+        ops->pk_import(ctx, bytes, len, pk.get());
         *out = pk.release();
     });
 }
@@ -1054,22 +913,19 @@ int32_t zkhip_multi_r1cs_load(zkhip_multi* m, int32_t curve, uint64_t n, uint64_
     if (rc != ZKHIP_OK) drop();      // all members or none: a partly loaded group must not reach the provers
     return rc;
 }
-int32_t zkhip_multi_pk_load_g16(zkhip_multi* m, int32_t curve, const uint8_t* bytes, size_t len) {
+// member k: shard k of n of the key, or — `replicas` — the whole key
+static int32_t multi_load(zkhip_multi* m, int32_t curve, int scheme, bool replicas, const uint8_t* bytes, size_t len) {
     if (!m) return ZKHIP_ERR_BAD_ARG;
     multi_drop_keys(m);
-    const uint32_t world = (uint32_t)m->ctx.size();
-    const int32_t rc = multi_each(m, [&](size_t k) { return zkhip_pk_load_g16_shard(m->ctx[k], curve, bytes, len, (uint32_t)k, world, &m->pk[k]); });
-    if (rc == ZKHIP_OK) m->scheme = 0; else multi_drop_keys(m);
+    const uint32_t world = replicas ? 1 : (uint32_t)m->ctx.size();
+    const int32_t rc = multi_each(m, [&](size_t k) { return load_key(m->ctx[k], curve, scheme, bytes, len, replicas ? 0 : (uint32_t)k, world, &m->pk[k]); });
+    if (rc == ZKHIP_OK) { m->scheme = scheme; m->replicas = replicas; } else multi_drop_keys(m);
     return rc;
 }
-int32_t zkhip_multi_pk_load_gm17(zkhip_multi* m, int32_t curve, const uint8_t* bytes, size_t len) {
-    if (!m) return ZKHIP_ERR_BAD_ARG;
-    multi_drop_keys(m);
-    const uint32_t world = (uint32_t)m->ctx.size();
-    const int32_t rc = multi_each(m, [&](size_t k) { return zkhip_pk_load_gm17_shard(m->ctx[k], curve, bytes, len, (uint32_t)k, world, &m->pk[k]); });
-    if (rc == ZKHIP_OK) m->scheme = 1; else multi_drop_keys(m);
-    return rc;
-}
+int32_t zkhip_multi_pk_load_g16(zkhip_multi* m, int32_t curve, const uint8_t* bytes, size_t len) { return multi_load(m, curve, 0, false, bytes, len); }
+int32_t zkhip_multi_pk_load_gm17(zkhip_multi* m, int32_t curve, const uint8_t* bytes, size_t len) { return multi_load(m, curve, 1, false, bytes, len); }
+// throughput mode: the whole key on every member; zkhip_prove_g16_multi_batch deals independent proofs round-robin
+int32_t zkhip_multi_pk_load_g16_replicas(zkhip_multi* m, int32_t curve, const uint8_t* bytes, size_t len) { return multi_load(m, curve, 0, true, bytes, len); }
 // The members' keys bound to the members' constraint system: member 0 computes level 0 of H' / L' over the whole index range from
 // the key file (the same bytes the key was loaded from), every member installs its own ranges (replicas: all of it).
 int32_t zkhip_multi_bind(zkhip_multi* m, const uint8_t* key_bytes, size_t len) {
@@ -1104,14 +960,6 @@ int32_t zkhip_multi_unbind(zkhip_multi* m) {
     if (!m) return ZKHIP_ERR_BAD_ARG;
     for (auto* p : m->pk) if (p) zkhip_pk_unbind(p);
     return ZKHIP_OK;
-}
-// throughput mode: the whole key on every member; zkhip_prove_g16_multi_batch deals independent proofs round-robin
-int32_t zkhip_multi_pk_load_g16_replicas(zkhip_multi* m, int32_t curve, const uint8_t* bytes, size_t len) {
-    if (!m) return ZKHIP_ERR_BAD_ARG;
-    multi_drop_keys(m);
-    const int32_t rc = multi_each(m, [&](size_t k) { return zkhip_pk_load_g16(m->ctx[k], curve, bytes, len, &m->pk[k]); });
-    if (rc == ZKHIP_OK) { m->scheme = 0; m->replicas = true; } else multi_drop_keys(m);
-    return rc;
 }
 int32_t zkhip_prove_g16_multi_batch(zkhip_multi* m, uint32_t count, const uint8_t* z, const uint8_t* rs, uint8_t* proofs_out, zkhip_timings* timings) {
     if (!m) return ZKHIP_ERR_BAD_ARG;
@@ -1259,33 +1107,6 @@ int32_t zkhip_prove_gm17_multi(zkhip_multi* m, const uint8_t* z, const uint8_t* 
 }
 
 // ------------------------------------------------------------------ GM17 (config 5)
-int32_t zkhip_pk_load_gm17(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_pk** out) {
-    if (!ctx) return ZKHIP_ERR_BAD_ARG;
-    return guarded(ctx, [&] {
-        require(bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
-        *out = nullptr;
-        std::unique_ptr<zkhip_pk> pk(new zkhip_pk());
-        pk->curve = curve;
-        pk->ctx = ctx;
-        ops_for(curve)->gm17_pk_load(ctx, bytes, len, pk.get());
-        *out = pk.release();
-    });
-}
-int32_t zkhip_pk_load_gm17_shard(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, uint32_t rank, uint32_t world, zkhip_pk** out) {
-    if (!ctx) return ZKHIP_ERR_BAD_ARG;
-    return guarded(ctx, [&] {
-        require(bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
-        *out = nullptr;
-        require(world >= 1 && world <= 64 && rank < world, ZKHIP_ERR_BAD_ARG, "rank / world out of range (1 <= world <= 64)");
-        std::unique_ptr<zkhip_pk> pk(new zkhip_pk());
-        pk->curve = curve;
-        pk->ctx = ctx;
-        pk->rank = rank;
-        pk->world = world;
-        ops_for(curve)->gm17_pk_load(ctx, bytes, len, pk.get());
-        *out = pk.release();
-    });
-}
 int32_t zkhip_prove_gm17_partial(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, const uint8_t* z, zkhip_assignment* z_resident,
                                  const uint8_t* d1_d2_r, uint8_t* partial_out, zkhip_timings* timings) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
