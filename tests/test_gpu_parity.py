@@ -116,24 +116,41 @@ def test_msm_skewed_scalars(ctx):
 
 
 def test_msm_edge_points(ctx):
-    curve = BN254
-    G1, G2 = groups(curve)
-    rnd = random.Random(3)
-    n = 64
-    p1 = [G1.amul(G1.gen, rnd.randrange(1, curve.r)) for _ in range(n)]
-    ks = [rnd.randrange(curve.r) for _ in range(n)]
-    p1[3] = None
-    p1[5] = p1[6]; ks[5] = ks[6]
-    p1[7] = G1.aneg(p1[8]); ks[7] = ks[8]
-    b1 = np.frombuffer(b"".join(formats.ser_g1(curve, P) for P in p1), dtype=np.uint8)
-    assert ctx.msm(0, 1, b1, le(ks)) == cpu.msm(0, 1, b1, le(ks))
-    assert ctx.msm(0, 1, b1, np.zeros(n * 32, dtype=np.uint8))[-1] == 1
-    for c in (2, 7, 11, 16):
-        ctx.tune("msm_c", c)
-        try:
-            assert ctx.msm(0, 1, b1, le(ks)) == cpu.msm(0, 1, b1, le(ks)), c
-        finally:
-            ctx.tune("msm_c", 0)
+    """A repeated base, an opposite pair and a base at infinity among 64 points, under several window widths: G1 and G2 of both
+    curves (the G2 accumulator keeps part of its sum in LDS and prefetches differently: other code than G1's)."""
+    for curve in CURVES:
+        cid = curve.curve_id
+        G1, G2 = groups(curve)
+        rnd = random.Random(3)
+        n = 64
+        p1 = [G1.amul(G1.gen, rnd.randrange(1, curve.r)) for _ in range(n)]
+        ks = [rnd.randrange(curve.r) for _ in range(n)]
+        p1[3] = None
+        p1[5] = p1[6]; ks[5] = ks[6]
+        p1[7] = G1.aneg(p1[8]); ks[7] = ks[8]
+        b1 = np.frombuffer(b"".join(formats.ser_g1(curve, P) for P in p1), dtype=np.uint8)
+        # G2: a walk of additions from two multiples of the generator (64 scalar multiplications in Fq2 cost seconds), same pattern
+        at, step = G2.amul(G2.gen, rnd.randrange(1, curve.r)), G2.amul(G2.gen, rnd.randrange(1, curve.r))
+        p2 = []
+        for _ in range(n):
+            at = G2.aadd(at, step)
+            p2.append(at)
+        p2[3] = None
+        p2[5] = p2[6]
+        p2[7] = G2.aneg(p2[8])
+        b2 = np.frombuffer(b"".join(formats.ser_g2(curve, P) for P in p2), dtype=np.uint8)
+        want1, want2 = cpu.msm(cid, 1, b1, le(ks)), cpu.msm(cid, 2, b2, le(ks))
+        assert ctx.msm(cid, 1, b1, le(ks)) == want1
+        assert ctx.msm(cid, 2, b2, le(ks)) == want2
+        assert ctx.msm(cid, 1, b1, np.zeros(n * 32, dtype=np.uint8))[-1] == 1
+        assert ctx.msm(cid, 2, b2, np.zeros(n * 32, dtype=np.uint8))[-1] == 1
+        for c in (2, 7, 11, 16):
+            ctx.tune("msm_c", c)
+            try:
+                assert ctx.msm(cid, 1, b1, le(ks)) == want1, (curve.name, c)
+                assert ctx.msm(cid, 2, b2, le(ks)) == want2, (curve.name, c)
+            finally:
+                ctx.tune("msm_c", 0)
 
 
 @pytest.mark.parametrize("curve,logn,kind", [

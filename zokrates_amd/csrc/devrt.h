@@ -548,7 +548,7 @@ inline JitterState& jitter_state() { static JitterState st; return st; }
     emu::launch(dim3(grid), dim3(block), (size_t)(smem), [&]() { kernel(__VA_ARGS__); })
 #define ZK_DYN_SMEM(name) unsigned char* name = emu::dyn_smem()
 #define ZK_PRIO_HIGH() ((void)0)
-#define ZK_WAVE_ANY(pred) (pred)      /* (the fibres of the emulator decide one by one: both sides compute the same result) */
+#define ZK_WAVE_ANY(pred) (emu::wave_ballot(pred) != 0)      /* a real vote of the wave's 64 fibres: a lane is taken along by its neighbours as on the device */
 #define ZK_WAVE_BALLOT(pred) emu::wave_ballot(pred)
 #ifdef ZK_CHECKED
 #define ZK_ASSERT_IDX(cond) do { if (!(cond)) { fprintf(stderr, "ZK_ASSERT_IDX failed: %s (%s:%d)\n", #cond, __FILE__, __LINE__); abort(); } } while (0)

@@ -205,7 +205,9 @@ inline T wave_exchange(T v, int src_lane) {
     return out;
 }
 
-// wave ballot: every lane of the wave (none may have exited) must call it
+// wave ballot: every LIVE lane of the wave must call it.  Lanes that have left the kernel (an early return, a loop with fewer
+// trips) take no part, as inactive lanes of a wavefront do: the rendezvous releases the wave when its live fibres wait, and the
+// word an exited lane left in its exchange slot is not counted.
 inline unsigned long long wave_ballot(bool pred) {
     Global& g = G();
     const unsigned flat = g.cur->flat, w = flat / 64;
@@ -214,7 +216,7 @@ inline unsigned long long wave_ballot(bool pred) {
     sync_wave();
     unsigned long long m = 0;
     for (unsigned l = 0; l < 64 && w * 64 + l < nt; ++l)
-        if (g.xchg[w * 64 + l]) m |= (unsigned long long)1 << l;
+        if (g.fibers[w * 64 + l].state != DONE && g.xchg[w * 64 + l]) m |= (unsigned long long)1 << l;
     sync_wave();
     return m;
 }
