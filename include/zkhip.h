@@ -21,6 +21,16 @@
  *    paired create/free.  No callbacks.
  *  - A context is bound to one GPU and is not re-entrant (one call at a time per context);
  *    distinct contexts may be used from distinct threads.
+ *  - One pair of calls leaves a proof in flight ACROSS calls: zkhip_prove_g16_split_begin .. zkhip_prove_g16_split_end.  Between
+ *    them the proof is PENDING in its context, and the context accepts zkhip_prove_g16_split_end, zkhip_prove_g16_split_abort and
+ *    the calls that neither enqueue device work nor change a handle (zkhip_last_error, zkhip_describe, zkhip_pk_dims,
+ *    zkhip_pk_is_bound, zkhip_pk_export_size, zkhip_partial_size, zkhip_combine_*, zkhip_ctx_set_checked(ctx, -1),
+ *    zkhip_ctx_unsatisfied, zkhip_setup_*_size, the zkhip_prog_* family).  Every other call on that context or on one of its keys —
+ *    the prove calls, zkhip_r1cs_check, a second begin, zkhip_pk_bind_r1cs / _shard / zkhip_pk_unbind, zkhip_ctx_tune,
+ *    zkhip_ctx_set_checked(ctx, 0 / 1), key loads, imports and exports, setups, uploads and the primitives (they work in the
+ *    pending proof's buffers and on its streams) — returns ZKHIP_ERR_BAD_ARG with a message that names the pending split proof,
+ *    before anything is enqueued, and leaves the pending proof as it is.  Freeing a handle a pending proof uses is the caller's
+ *    error, as it is during any call.
  *  - There is no CPU fallback: without a usable gfx950 device zkhip_ctx_create fails with
  *    ZKHIP_ERR_DEVICE.
  */
@@ -234,7 +244,8 @@ int32_t zkhip_r1cs_check(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* 
  * every proof's assignment on the device (one pointwise pass over the three row-product vectors; over a bound key C's mat-vec
  * as well) with no further synchronisation.  If any fails, the call returns ZKHIP_ERR_UNSATISFIED, zkhip_last_error names the
  * first failing proof and its constraint, the output slot of every failing proof is zero-filled, the slot of every other proof
- * of the call holds the bytes the unchecked call writes, and the context stays usable.  With checked mode off nothing changes:
+ * of the call holds the bytes the unchecked call writes, and the context stays usable.  (on >= 0 while a split proof is pending:
+ * ZKHIP_ERR_BAD_ARG, nothing changed.)  With checked mode off nothing changes:
  * the same launches, bytes and return codes as without this section.
  * The multi-GPU entry points — zkhip_prove_*_partial, zkhip_prove_g16_split_*, zkhip_prove_*_multi* — IGNORE checked mode (the
  * members of a zkhip_multi are created with it off): their callers use zkhip_r1cs_check. */
@@ -443,11 +454,19 @@ int32_t zkhip_pk_bind_r1cs_shard(zkhip_ctx* ctx, zkhip_pk* pk, const zkhip_r1cs*
  * assignment, starts this rank's MSMs over it and transforms ITS half of the witness map — half = 0: a, 1: b on the coset — into
  * `half_out` (N x 32 bytes of host memory; N = the key's domain); the caller exchanges halves with a rank of the other parity;
  * `end` takes the partner's half and leaves the rank's partial record (as zkhip_prove_g16_partial).  The key must be bound
- * (zkhip_pk_bind_r1cs_shard).  zokrates_amd/parallel.py prove_sharded does exactly this over RCCL / gloo. */
+ * (zkhip_pk_bind_r1cs_shard).  zokrates_amd/parallel.py prove_sharded does exactly this over RCCL / gloo.
+ * After a successful `begin` the proof is pending (see Conventions): the context remembers the key, the constraint system and that
+ * the key was bound, and `end` finishes THAT proof — it wants the same `pk` and `r1cs` (ZKHIP_ERR_BAD_ARG otherwise, the proof stays
+ * pending), and is refused the same way when nothing is pending: without a `begin`, or a second time for a proof already collected.
+ * A `begin` that returns an error leaves nothing pending; so does an `end` that fails after its argument checks.  A `begin` that
+ * is refused because its key is not bound, its `half` is not 0 or 1, or r / s is not canonical has enqueued nothing.
+ * zkhip_prove_g16_split_abort is for the caller that gives the exchange up after `begin` (its partner failed): it waits for what the
+ * head enqueued, drops the pending proof and leaves the context as before `begin`; ZKHIP_OK also when nothing is pending. */
 int32_t zkhip_prove_g16_split_begin(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, const uint8_t* z, zkhip_assignment* z_resident,
                                     const uint8_t* r, const uint8_t* s, int32_t half, uint8_t* half_out);
 int32_t zkhip_prove_g16_split_end(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, const uint8_t* other_half, uint8_t* partial_out,
                                   zkhip_timings* timings);
+int32_t zkhip_prove_g16_split_abort(zkhip_ctx* ctx);
 int32_t zkhip_r1cs_fingerprint(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, uint64_t out[2]);
 int32_t zkhip_pk_is_bound(const zkhip_pk* pk, const zkhip_r1cs* r1cs);
 

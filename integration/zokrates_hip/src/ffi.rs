@@ -60,6 +60,14 @@ extern "C" {
         count: *mut u32) -> i32;
     /// a shard of a multi-GPU key (or a whole key, Groth16 or GM17) bound from the key FILE: the transforms need every base once
     pub fn zkhip_pk_bind_r1cs_shard(ctx: *mut zkhip_ctx, pk: *mut zkhip_pk, r1cs: *const zkhip_r1cs, key_bytes: *const u8, len: usize) -> i32;
+    // ranks that are separate processes: the witness map of one proof split between two of them.  Between
+    // `begin` and `end` the proof is PENDING in its context, which refuses everything but `end`, `abort` and host-only calls
+    pub fn zkhip_prove_g16_split_begin(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, r1cs: *const zkhip_r1cs, z: *const u8,
+        z_resident: *mut zkhip_assignment, r: *const u8, s: *const u8, half: i32, half_out: *mut u8) -> i32;
+    pub fn zkhip_prove_g16_split_end(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, r1cs: *const zkhip_r1cs, other_half: *const u8,
+        partial_out: *mut u8, timings: *mut zkhip_timings) -> i32;
+    /// the exchange was given up after `begin`: drops the pending proof (ZKHIP_OK also when none is pending)
+    pub fn zkhip_prove_g16_split_abort(ctx: *mut zkhip_ctx) -> i32;
     // one proof across several GPUs of this process
     pub fn zkhip_ctx_create_multi(devices: *const i32, n: i32, out: *mut *mut zkhip_multi) -> i32;
     pub fn zkhip_multi_free(m: *mut zkhip_multi);

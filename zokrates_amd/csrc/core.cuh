@@ -142,6 +142,13 @@ struct ProofSlot {
     Event half_ready = nullptr;                           // a member of a multi-GPU proof: its half of the witness map (a or b on the coset) is in va
     int half = -1;                                        // which half this proof's head computed (-1: the whole witness map)
     bool lone = false;                                    // (enqueue_head -> enqueue_tail)
+    // a split proof between its head and its tail (zkhip_prove_g16_split_begin .. _end, or the two phases of zkhip_prove_g16_multi):
+    // PENDING.  The slot remembers the handles the head was enqueued with and whether the key was bound then; the tail takes these,
+    // and until it is collected (or zkhip_prove_g16_split_abort) the context refuses every call that could touch them (split_refuse)
+    bool split_pending = false;
+    const zkhip_pk* split_pk = nullptr;
+    const zkhip_r1cs* split_cs = nullptr;
+    bool split_bound = false;
     bool ready = false;        // streams and events exist (slot_init)
     // the proof currently in flight in this slot
     bool busy = false;
@@ -1925,7 +1932,13 @@ struct Prover {
         ctx->ws = wn;
         witness_map(ctx, cs, pl, bound, half, sl.check_idx >= 0);
         ctx->ws = ctx->stream;
-        if (half >= 0) event_record(sl.half_ready, wn);
+        if (half >= 0) {
+            event_record(sl.half_ready, wn);
+            sl.split_pk = pk;
+            sl.split_cs = cs;
+            sl.split_bound = bound;
+            sl.split_pending = true;
+        }
     }
     // ... and the rest: (the product of the two halves,) the G1 lanes over z, the h sort and the H MSM, the copies out
     static void enqueue_tail(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs) {
@@ -1940,7 +1953,8 @@ struct Prover {
             Fr* a = ptr<Fr>(sl.va);
             ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, wn, a, a + N, fe_from_mont(get_plan<C>(ctx, pk->logN)->zinv), a + 2 * N, N);
         }
-        lanes_after_h(ctx, sl, pk, Lay(ctx, pk), is_bound(pk, cs), sl.lone, h_scalars, wn);
+        // (a split proof: what the head saw — the product above pairs with the bound tables whatever has happened to the key since)
+        lanes_after_h(ctx, sl, pk, Lay(ctx, pk), sl.half >= 0 ? sl.split_bound : is_bound(pk, cs), sl.lone, h_scalars, wn);
     }
 
     // ---- the z lanes' start: the digits of S sorted once on the main stream — and once more without the variables a family of
@@ -2084,6 +2098,7 @@ struct Prover {
         require(sl.busy, ZKHIP_ERR_DEVICE, "internal: no proof in flight in this slot");
         event_sync(sl.ev[3]);
         sl.busy = false;
+        split_clear(sl);
         const Lay ly(ctx, pk);
         require_canonical(ly.zflag_word(sl));
         // five independent Horner chains (W x c doublings each): one host thread per MSM, the G2 chain on this one
@@ -2242,36 +2257,49 @@ struct Prover {
         enqueue_head(ctx, ctx->slots[0], pk, cs, z_host, z_dev, r, s_, false, half);
     }
     static const void* split_half_ptr(zkhip_ctx* ctx, const zkhip_pk* pk, int half) { return ptr<Fr>(ctx->slots[0].va) + (u64)half * pk->N; }
-    // the slot of the split proof in flight, and the stream its halves travel on
-    static ProofSlot& split_slot(zkhip_ctx* ctx, Stream* wn = nullptr) {
-        require(ctx->slots[0].half >= 0, ZKHIP_ERR_BAD_ARG, "internal: no split proof in flight");
+    // a collected (or abandoned) split proof: the slot is an ordinary free slot again
+    static void split_clear(ProofSlot& sl) {
+        sl.split_pending = false;
+        sl.split_pk = nullptr;
+        sl.split_cs = nullptr;
+        sl.half = -1;
+    }
+    // the slot of the pending split proof — which must be the proof of these handles —, and the stream its halves travel on
+    static ProofSlot& split_slot(zkhip_ctx* ctx, const zkhip_pk* pk, Stream* wn = nullptr) {
+        ProofSlot& s0 = ctx->slots[0];
+        require(s0.split_pending && s0.half >= 0, ZKHIP_ERR_BAD_ARG, "no split proof pending in this context");
+        require(s0.split_pk == pk, ZKHIP_ERR_BAD_ARG, "the split proof pending in this context was begun with another proving key");
         if (wn) *wn = ctx->serial ? ctx->stream : ctx_ntt_stream(ctx);
         return ctx->slots[0];
     }
     static void split_fetch(zkhip_ctx* ctx, const zkhip_pk* pk, const void* src, int src_device, Event src_ready) {
         Stream wn;
-        ProofSlot& sl = split_slot(ctx, &wn);
+        ProofSlot& sl = split_slot(ctx, pk, &wn);
         if (src_ready) event_sync(src_ready);           // (the partner's stream, possibly on another device: waited for on the host)
         dev_copy_between(ptr<Fr>(sl.va) + (u64)(1 - sl.half) * pk->N, ctx->device, src, src_device, pk->N * sizeof(Fr), wn);
     }
     static void split_fetch_host(zkhip_ctx* ctx, const zkhip_pk* pk, const uint8_t* other_half) {
         Stream wn;
-        ProofSlot& sl = split_slot(ctx, &wn);
+        ProofSlot& sl = split_slot(ctx, pk, &wn);
         dev_h2d(ptr<Fr>(sl.va) + (u64)(1 - sl.half) * pk->N, other_half, pk->N * sizeof(Fr), wn);
     }
     static void split_half_out(zkhip_ctx* ctx, const zkhip_pk* pk, uint8_t* out) {
         Stream wn;
-        ProofSlot& sl = split_slot(ctx, &wn);
+        ProofSlot& sl = split_slot(ctx, pk, &wn);
         dev_d2h(out, ptr<Fr>(sl.va) + (u64)sl.half * pk->N, pk->N * sizeof(Fr), wn);
         stream_sync(wn);
     }
     static void split_end_partial(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, uint8_t* partial_out, zkhip_timings* tm) {
-        enqueue_tail(ctx, split_slot(ctx), pk, cs);
+        ProofSlot& sl = split_slot(ctx, pk);
+        require(sl.split_cs == cs, ZKHIP_ERR_BAD_ARG, "the split proof pending in this context was begun with another constraint system");
+        enqueue_tail(ctx, sl, pk, cs);
         emit_partial(ctx, ctx->slots[0], pk, partial_out, tm);
     }
     static void split_end_device_sums(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2,
                                       zkhip_timings* tm) {
-        enqueue_tail(ctx, split_slot(ctx), pk, cs);
+        ProofSlot& sl = split_slot(ctx, pk);
+        require(sl.split_cs == cs, ZKHIP_ERR_BAD_ARG, "the split proof pending in this context was begun with another constraint system");
+        enqueue_tail(ctx, sl, pk, cs);
         hand_out_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2, tm);
     }
     // one rank's share of a proof, left ON THE DEVICE: the raw bucket-set sums of its five MSMs (ws1: 4 G1 MSMs x Wmax XYZZ
@@ -2288,6 +2316,7 @@ struct Prover {
         require(sl.busy, ZKHIP_ERR_DEVICE, "internal: no proof in flight in this slot");
         event_sync(sl.ev[3]);
         sl.busy = false;
+        split_clear(sl);
         const Lay ly(ctx, pk);
         *b1 = ly.b1();
         *b2 = ly.b2();

@@ -25,8 +25,31 @@ static void release_slots(zkhip_ctx* ctx) {
     dev_sync_all();
     for (auto& sl : ctx->slots) sl.busy = false;
 }
+// Between zkhip_prove_g16_split_begin and _end a proof is PENDING in slot 0: its vectors, sorted lists and lanes hold the head's work,
+// and its tail will take the tables and the streams the head saw.  Every entry point that enqueues on the context's streams, writes
+// its workspaces, or changes a key, the streams or the mode — all of them but the ones that pass `while_pending` — is refused here,
+// on the host, before anything is enqueued, and the pending proof stays as it is (no release_slots: nothing of this call is in flight)
+static const char* const SPLIT_PENDING_MSG =
+    "a split proof is pending in this context (zkhip_prove_g16_split_begin): finish it with zkhip_prove_g16_split_end or drop it with "
+    "zkhip_prove_g16_split_abort first";
+static bool split_pending(const zkhip_ctx* ctx) { return ctx->slots[0].split_pending; }
+// an abandoned or failed split proof: what is enqueued drains, the slot is free again
+static void split_drop(zkhip_ctx* ctx) {
+    ProofSlot& sl = ctx->slots[0];
+    if (!sl.split_pending && !sl.busy) return;
+    try { dev_set(ctx->device); dev_sync_all(); } catch (...) {}
+    sl.busy = false;
+    sl.split_pending = false;
+    sl.split_pk = nullptr;
+    sl.split_cs = nullptr;
+    sl.half = -1;
+}
 template <class Fn>
-static int32_t guarded(zkhip_ctx* ctx, Fn&& fn) {
+static int32_t guarded(zkhip_ctx* ctx, Fn&& fn, bool while_pending = false) {
+    if (ctx && !while_pending && split_pending(ctx)) {
+        ctx->err = SPLIT_PENDING_MSG;
+        return ZKHIP_ERR_BAD_ARG;
+    }
     try {
         if (ctx) dev_set(ctx->device);
         fn();
@@ -351,8 +374,13 @@ int32_t zkhip_prove_g16_split_begin(zkhip_ctx* ctx, const zkhip_pk* pk, const zk
                         "assignment does not match the constraint system");
         for (auto& sl : ctx->slots) require(!sl.busy, ZKHIP_ERR_BAD_ARG, "a proof is in flight in this context");
         const CurveOps* ops = ops_for(pk->curve);
-        ops->split_begin(ctx, pk, r1cs, z, z ? nullptr : z_resident->scalars.p, r, s, half);
-        ops->split_half_out(ctx, pk, half_out);
+        try {
+            ops->split_begin(ctx, pk, r1cs, z, z ? nullptr : z_resident->scalars.p, r, s, half);
+            ops->split_half_out(ctx, pk, half_out);
+        } catch (...) {
+            split_drop(ctx);      // (a begin that fails leaves nothing pending)
+            throw;
+        }
     });
 }
 int32_t zkhip_prove_g16_split_end(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, const uint8_t* other_half, uint8_t* partial_out, zkhip_timings* timings) {
@@ -360,10 +388,24 @@ int32_t zkhip_prove_g16_split_end(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhi
     return guarded(ctx, [&] {
         require(pk && r1cs && other_half && partial_out, ZKHIP_ERR_BAD_ARG, "null argument");
         require(pk->ctx == ctx && r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "handles belong to another context");
+        // the state and the handles first, on the host: a call that is refused for them leaves the pending proof as it is
+        const ProofSlot& sl = ctx->slots[0];
+        require(sl.split_pending, ZKHIP_ERR_BAD_ARG, "no split proof pending in this context: zkhip_prove_g16_split_begin comes first, and a proof is collected once");
+        require(sl.split_pk == pk && sl.split_cs == r1cs, ZKHIP_ERR_BAD_ARG,
+                "the split proof pending in this context was begun with another proving key or constraint system");
         const CurveOps* ops = ops_for(pk->curve);
-        ops->split_fetch_host(ctx, pk, other_half);
-        ops->split_end_partial(ctx, pk, r1cs, partial_out, timings);
-    });
+        try {
+            ops->split_fetch_host(ctx, pk, other_half);
+            ops->split_end_partial(ctx, pk, r1cs, partial_out, timings);
+        } catch (...) {
+            split_drop(ctx);      // (an end that fails leaves nothing pending either)
+            throw;
+        }
+    }, true);
+}
+int32_t zkhip_prove_g16_split_abort(zkhip_ctx* ctx) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] { split_drop(ctx); }, true);
 }
 int32_t zkhip_r1cs_fingerprint(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, uint64_t out[2]) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
@@ -471,7 +513,7 @@ int32_t zkhip_combine_g16(zkhip_ctx* ctx, const zkhip_pk* pk, uint32_t count, co
         require(pk && partials && r && s && proof_out && count >= 1, ZKHIP_ERR_BAD_ARG, "null argument");
         require(pk->scheme == 0, ZKHIP_ERR_BAD_ARG, "this is a GM17 proving key");
         ops_for(pk->curve)->combine(pk, count, partials, r, s, proof_out);
-    });
+    }, true);      // (host arithmetic only: legal beside a pending split proof)
 }
 
 int32_t zkhip_prove_g16_batch(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, uint32_t count, const uint8_t* z, const uint8_t* rs,
@@ -524,6 +566,10 @@ int32_t zkhip_r1cs_check(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* 
 int32_t zkhip_ctx_set_checked(zkhip_ctx* ctx, int32_t on) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
     const int32_t was = ctx->checked ? 1 : 0;
+    if (on >= 0 && split_pending(ctx)) {
+        ctx->err = SPLIT_PENDING_MSG;
+        return ZKHIP_ERR_BAD_ARG;
+    }
     if (on >= 0) ctx->checked = on != 0;
     return was;
 }
@@ -991,6 +1037,9 @@ int32_t zkhip_prove_g16_multi_batch(zkhip_multi* m, uint32_t count, const uint8_
     }
     return ZKHIP_OK;
 }
+static void multi_split_drop(zkhip_multi* m) {
+    for (auto* c : m->ctx) split_drop(c);
+}
 static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const uint8_t* rnd, const uint8_t* s_, uint8_t* proof_out, zkhip_timings* timings) {
     if (!m) return ZKHIP_ERR_BAD_ARG;
     if (!z || !rnd || !proof_out || (scheme == 0 && !s_)) { m->err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
@@ -1026,7 +1075,7 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
                 sops->split_begin(m->ctx[k], m->pk[k], m->cs[k], z, nullptr, rnd, s_, half_of(k));
             });
         });
-        if (rc != ZKHIP_OK) { for (auto* c : m->ctx) { try { dev_set(c->device); dev_sync_all(); } catch (...) {} } return rc; }
+        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }      // (no member stays pending behind another member's failure)
     }
     if (m->rccl) {
         // every member leaves the bucket-set sums of its five partial MSMs on its device and all-gathers them (RCCL over
@@ -1043,11 +1092,11 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
                 else ops->gm17_prove_device_sums(c, m->pk[k], m->cs[k], z, rnd, &d1[k], &b1[k], &d2[k], &b2[k], &tm[k]);
                 m->gather1[k].ensure(n * b1[k]);
                 m->gather2[k].ensure(n * b2[k]);
-            });
+            }, split);
         };
 #ifdef ZK_EMU
         rc = multi_each(m, share);
-        if (rc != ZKHIP_OK) return rc;
+        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }
         for (size_t k = 0; k < n; ++k) {
             dev_d2d((uint8_t*)m->gather1[0].p + k * b1[0], d1[k], b1[0], m->ctx[0]->stream);
             dev_d2d((uint8_t*)m->gather2[0].p + k * b2[0], d2[k], b2[0], m->ctx[0]->stream);
@@ -1056,7 +1105,7 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
         // two phases: a member enters the collective only when EVERY member has its share (one that failed alone would
         // leave the others waiting in ncclAllGather for ever)
         rc = multi_each(m, share);
-        if (rc != ZKHIP_OK) return rc;
+        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }
         rc = multi_each(m, [&](size_t k) {
             return guarded(m->ctx[k], [&] {
                 Rccl& R = rccl();
@@ -1080,11 +1129,11 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
         if (rc != ZKHIP_OK) { m->err = std::string("gather: ") + zkhip_last_error(m->ctx[0]); return rc; }
     } else {
         rc = multi_each(m, [&](size_t k) {
-            if (split) return guarded(m->ctx[k], [&] { fetch(k); sops->split_end_partial(m->ctx[k], m->pk[k], m->cs[k], &records[k * rec], &tm[k]); });
+            if (split) return guarded(m->ctx[k], [&] { fetch(k); sops->split_end_partial(m->ctx[k], m->pk[k], m->cs[k], &records[k * rec], &tm[k]); }, true);
             return scheme == 0 ? zkhip_prove_g16_partial(m->ctx[k], m->pk[k], m->cs[k], z, nullptr, rnd, s_, &records[k * rec], &tm[k])
                                : zkhip_prove_gm17_partial(m->ctx[k], m->pk[k], m->cs[k], z, nullptr, rnd, &records[k * rec], &tm[k]);
         });
-        if (rc != ZKHIP_OK) return rc;
+        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }
     }
     rc = scheme == 0 ? zkhip_combine_g16(m->ctx[0], m->pk[0], (uint32_t)n, records.data(), rnd, s_, proof_out)
                      : zkhip_combine_gm17(m->ctx[0], m->pk[0], (uint32_t)n, records.data(), rnd, proof_out);
@@ -1124,7 +1173,7 @@ int32_t zkhip_combine_gm17(zkhip_ctx* ctx, const zkhip_pk* pk, uint32_t count, c
         require(pk && partials && d1_d2_r && proof_out && count >= 1, ZKHIP_ERR_BAD_ARG, "null argument");
         require(pk->scheme == 1, ZKHIP_ERR_BAD_ARG, "this is a Groth16 proving key");
         ops_for(pk->curve)->gm17_combine(pk, count, partials, d1_d2_r, proof_out);
-    });
+    }, true);
 }
 int32_t zkhip_prove_gm17(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, const uint8_t* z, const uint8_t* d1_d2_r,
                          uint8_t* proof_out, zkhip_timings* timings) {

@@ -67,7 +67,7 @@ class Library:
         "zkhip_pk_export_size", "zkhip_pk_export", "zkhip_pk_import",
         "zkhip_pk_bind_r1cs", "zkhip_pk_unbind", "zkhip_pk_is_bound", "zkhip_pk_bind_r1cs_shard", "zkhip_r1cs_fingerprint",
         "zkhip_ctx_tune", "zkhip_init", "zkhip_ctx_clock_probe", "zkhip_multi_bind", "zkhip_multi_unbind",
-        "zkhip_multi_transform_split", "zkhip_multi_last_split", "zkhip_prove_g16_split_begin", "zkhip_prove_g16_split_end",
+        "zkhip_multi_transform_split", "zkhip_multi_last_split", "zkhip_prove_g16_split_begin", "zkhip_prove_g16_split_end", "zkhip_prove_g16_split_abort",
         "zkhip_ctx_create_multi", "zkhip_multi_free", "zkhip_multi_size", "zkhip_multi_ctx", "zkhip_multi_last_error", "zkhip_multi_r1cs_load",
         "zkhip_multi_pk_load_g16", "zkhip_multi_pk_load_gm17", "zkhip_prove_g16_multi", "zkhip_prove_gm17_multi",
         "zkhip_multi_pk_load_g16_replicas", "zkhip_prove_g16_multi_batch", "zkhip_multi_use_rccl", "zkhip_multi_exchange",
@@ -150,6 +150,7 @@ class Library:
         L.zkhip_multi_last_split.restype = i32; L.zkhip_multi_last_split.argtypes = [vp]
         L.zkhip_prove_g16_split_begin.restype = i32; L.zkhip_prove_g16_split_begin.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
         L.zkhip_prove_g16_split_end.restype = i32; L.zkhip_prove_g16_split_end.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.zkhip_prove_g16_split_abort.restype = i32; L.zkhip_prove_g16_split_abort.argtypes = [vp]
         L.zkhip_prog_parse.restype = i32; L.zkhip_prog_parse.argtypes = [vp, sz, pp]
         L.zkhip_prog_free.restype = None; L.zkhip_prog_free.argtypes = [vp]
         L.zkhip_prog_dims.restype = i32; L.zkhip_prog_dims.argtypes = [vp, vp]
@@ -213,7 +214,10 @@ class Context:
     def set_checked(self, on=True):
         """`zkhip_ctx_set_checked`: the single-GPU prove calls of this context test Az o Bz == Cz on the device and refuse (ZkhipError
         code -5, `unsatisfied`) an assignment that fails.  None only reports.  Returns the previous setting."""
-        return bool(self.lib.L.zkhip_ctx_set_checked(self.h, -1 if on is None else int(bool(on))))
+        was = self.lib.L.zkhip_ctx_set_checked(self.h, -1 if on is None else int(bool(on)))
+        if was < 0:       # (refused: a split proof is pending)
+            self._check(was)
+        return bool(was)
 
     def unsatisfied(self):
         """`zkhip_ctx_unsatisfied`: [(proof index, first failing row, failing rows)] of the last checked prove call that failed."""
@@ -476,6 +480,11 @@ def prove_g16_split_end(ctx, pk_shard, cs, other_half):
     tm = Timings()
     ctx._check(ctx.lib.L.zkhip_prove_g16_split_end(ctx.h, pk_shard.h, cs.h, _ptr(other), _ptr(out), C.byref(tm)))
     return out
+
+
+def prove_g16_split_abort(ctx):
+    """`zkhip_prove_g16_split_abort`: drop the split proof pending in `ctx` (the exchange was given up); nothing pending: no-op."""
+    ctx._check(ctx.lib.L.zkhip_prove_g16_split_abort(ctx.h))
 
 
 def partial_size(ctx, curve_id):

@@ -76,6 +76,15 @@ class Ranks:
         self._dist.all_reduce(t, op=self._dist.ReduceOp.MAX)
         return float(t.item())
 
+    def min_over_ranks(self, values):
+        """Element-wise MIN of a short list of numbers over the ranks (one all-reduce): how the ranks agree on a yes / no."""
+        if self._dist is None:
+            return [float(v) for v in values]
+        dev = "cuda" if self.backend == "nccl" else "cpu"
+        t = self._torch.tensor([float(v) for v in values], dtype=self._torch.float64, device=dev)
+        self._dist.all_reduce(t, op=self._dist.ReduceOp.MIN)
+        return [float(v) for v in t.tolist()]
+
     def sum_over_ranks(self, value):
         if self._dist is None:
             return float(value)
@@ -140,25 +149,45 @@ SPLIT_MIN_LOG = int(os.environ.get("ZKHIP_SPLIT_MIN_LOG", "18"))     # the libra
 def prove_sharded(ranks, ctx, pk_shard, cs, z, r, s, d1_d2=None, transform_split=None):
     """One proof across all ranks.  `pk_shard` = native.ProvingKey(..., rank=ranks.rank, world=ranks.world); z and the
     blinding scalars are the same on every rank (Groth16: r, s; GM17: d1_d2 = (d1, d2) and r, `s` ignored).  Every rank
-    returns the (identical) proof bytes."""
+    returns the (identical) proof bytes.
+
+    The ranks AGREE before they prove (one MIN all-reduce of two flags).  (1) Bound or not: the partial sums of a bound shard pair
+    other scalars with other bases than those of a shard as loaded (H' with the quotient's evaluations, L' with c's share folded in),
+    so records of the two kinds do not add up to the proof — and a rank may legally be unbound where the others are bound
+    (zkhip_pk_bind_r1cs_shard, ZKHIP_ERR_NOMEM: "the key stays usable, unbound").  If any rank is unbound, the bound ranks unbind:
+    all or none, as zkhip_multi_bind has it.  (2) Split or not (Groth16, transform_split=None): a rank that decided alone to prove
+    the whole witness map would go to the all-gather while its partner waits in the exchange for a half that never comes.
+    transform_split=True with a rank that cannot split raises — on every rank, after the same collective."""
     from . import native
-    if getattr(pk_shard, "scheme", "g16") == "gm17":
+    mine_bound = bool(pk_shard.is_bound(cs))
+    gm17 = getattr(pk_shard, "scheme", "g16") == "gm17"
+    wants = (not gm17) and ranks.world >= 2 and mine_bound and (transform_split if transform_split is not None else (pk_shard.hlen + 1) >= (1 << SPLIT_MIN_LOG))
+    all_bound, all_want = ranks.min_over_ranks([1.0 if mine_bound else 0.0, 1.0 if wants else 0.0]) if ranks.world >= 2 else (float(mine_bound), 0.0)
+    if mine_bound and all_bound < 1.0:
+        pk_shard.unbind()
+    if gm17:
         d1, d2 = d1_d2
         parts = ranks.all_gather_bytes(native.prove_gm17_partial(ctx, pk_shard, cs, z, d1, d2, r))
         return native.combine_gm17(ctx, pk_shard, parts, d1, d2, r)
-    split = transform_split if transform_split is not None else (ranks.world >= 2 and pk_shard.is_bound(cs) and (pk_shard.hlen + 1) >= (1 << SPLIT_MIN_LOG))
-    if split and ranks.world >= 2:
+    if transform_split and ranks.world >= 2 and all_bound < 1.0:
+        raise RuntimeError("transform_split=True, but the key shard of at least one rank is not bound to the constraint system "
+                           + ("(this rank's was: unbound now)" if mine_bound else "(this rank's is not)"))
+    if all_want >= 1.0:
         # the witness map split between the ranks (bound shards: a and b on the coset are all a proof needs of it): even ranks
         # transform a, odd ranks b, partners swap their halves
         half = ranks.rank & 1
         partner = ranks.rank ^ 1 if (ranks.rank ^ 1) < ranks.world else ranks.rank - 1
         mine = native.prove_g16_split_begin(ctx, pk_shard, cs, z, r, s, half)
-        if (ranks.rank ^ 1) < ranks.world:
-            theirs = ranks.exchange_bytes(partner, mine)
-        else:      # the odd rank out (world is odd): it only receives — its partner has a partner of its own
-            theirs = ranks.recv_bytes(partner, mine.size)
-        if ranks.world % 2 == 1 and ranks.rank == ranks.world - 2:
-            ranks.send_bytes(ranks.world - 1, mine)          # ... which also serves the rank without one
+        try:
+            if (ranks.rank ^ 1) < ranks.world:
+                theirs = ranks.exchange_bytes(partner, mine)
+            else:      # the odd rank out (world is odd): it only receives — its partner has a partner of its own
+                theirs = ranks.recv_bytes(partner, mine.size)
+            if ranks.world % 2 == 1 and ranks.rank == ranks.world - 2:
+                ranks.send_bytes(ranks.world - 1, mine)          # ... which also serves the rank without one
+        except BaseException:
+            native.prove_g16_split_abort(ctx)      # the exchange failed: the context is not left with a proof pending
+            raise
         part = native.prove_g16_split_end(ctx, pk_shard, cs, theirs)
     else:
         part = native.prove_g16_partial(ctx, pk_shard, cs, z, r, s)
