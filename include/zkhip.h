@@ -62,6 +62,7 @@ typedef struct zkhip_ctx zkhip_ctx;
 typedef struct zkhip_pk zkhip_pk;
 typedef struct zkhip_r1cs zkhip_r1cs;
 typedef struct zkhip_assignment zkhip_assignment;
+typedef struct zkhip_prog zkhip_prog;         /* a parsed ZoKrates program (the zkhip_prog_* family below) */
 
 /* Per-proof phase timings in milliseconds (HIP events on the library's own streams).  The MSMs run on their own
  * streams concurrently with each other and with the NTT pipeline, so the phase intervals overlap: they do not
@@ -216,6 +217,54 @@ int32_t zkhip_assignment_upload(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const ui
 void zkhip_assignment_free(zkhip_assignment* z);
 int32_t zkhip_prove_g16_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_assignment* z,
                                  const uint8_t* r, const uint8_t* s, uint8_t* proof_out, zkhip_timings* timings);
+
+/* ---- compact assignments ----
+ * An assignment of a program over bool / u8 / u32 / u64 is mostly zeros and ones (bit decompositions), and m x 32 B of it cross the
+ * bus for every proof.  The packed form keeps the low bytes a value needs and is widened on the device: the upload below returns the
+ * same resident assignment as zkhip_assignment_upload, bit for bit, so every *_resident entry point gives the same proof bytes.
+ * All integers little-endian; every section starts on a 16-byte boundary of the buffer:
+ *
+ *   0    8 B   magic "ZKHIPZ1\0"
+ *   8    u64   m                      number of elements
+ *   16   u64   payload_bytes          multiple of 16
+ *   24   u32   block = 1024           elements per block (the only value accepted)
+ *   28   u32   flags = 0
+ *   32   tags     2 bits per element: element i in bits 2(i%4)..2(i%4)+1 of byte i/4; ceil(m/4) bytes, zero-padded to a
+ *                 multiple of 16
+ *   ..   index    nblocks + 1 entries of u64, nblocks = ceil(m/1024): index[b] = offset of block b's values inside the payload,
+ *                 index[0] = 0, index[nblocks] = payload_bytes, every entry a multiple of 16; one zero entry appended if needed
+ *                 to make the count even
+ *   ..   payload  per block, in element order: the value's low bytes, width by tag - 0: none (value 0), 1: 1 byte, 2: 8 bytes,
+ *                 3: 32 bytes; zero bytes up to the next multiple of 16 at the end of every block (a block: at most 32 KiB)
+ *
+ * zkhip_assignment_pack is deterministic and minimal (the smallest class that holds the value, all padding zero): two packings of
+ * one assignment are the same bytes.  The decoders accept a wider class than needed and decode it to the same value.  A dense
+ * witness (field elements: Poseidon) packs to *len >= 32 m, and its caller keeps the plain upload.
+ *
+ * The packer has no curve: it refuses a z entry that is canonical in NO supported field (>= the largest r, BLS12-381's), and a
+ * `cap` that is too small (*len is the length needed either way; nothing is written past cap).  Whether a 32-byte value is below
+ * the r of the constraint system's curve is tested where the curve is known: by zkhip_prog_assignment_packed on the host, and by
+ * zkhip_assignment_upload_packed on the device, with the error zkhip_assignment_upload gives.
+ *
+ * zkhip_assignment_unpack and zkhip_assignment_upload_packed validate the whole structure on the host before anything else
+ * happens (ZKHIP_ERR_PARSE, the message names the rule): magic, block, flags; len == header + tags + index + payload; the index
+ * monotone and 16-aligned; every index span the 16-rounded sum of its block's widths; unused tag bits and padding zero.  The upload
+ * then wants m == l + w of `r1cs` and element 0 == 1 (ZKHIP_ERR_BAD_ARG), and is refused like every upload while a split proof is
+ * pending.  The context keeps one device buffer for the packed bytes, as large as the largest packed buffer it has uploaded
+ * (about 32 m bytes after a dense one), until zkhip_ctx_free.
+ * zkhip_assignment_pack is therefore NOT a test that z is canonical for a given curve: only the upload and
+ * zkhip_prog_assignment_packed are. */
+/* host only: no context, no device work (like the zkhip_prog_* family) */
+int32_t zkhip_assignment_pack_bound(uint64_t m, uint64_t* bytes);                 /* worst case: every element 32 bytes wide */
+int32_t zkhip_assignment_pack(const uint8_t* z, uint64_t m, uint8_t* out, uint64_t cap, uint64_t* len);
+int32_t zkhip_assignment_unpack(const uint8_t* packed, size_t len, uint8_t* z_out, uint64_t m_cap, uint64_t* m);
+/* zkhip_prog_assignment, with z in the packed form; the same bytes as zkhip_assignment_pack of its z_out */
+int32_t zkhip_prog_assignment_packed(const zkhip_prog* prog, const uint8_t* witness, size_t len, uint8_t* packed_out,
+                                     uint64_t cap, uint64_t* packed_len, uint8_t* inputs_out, uint64_t inputs_cap,
+                                     uint64_t* n_inputs);
+/* zkhip_assignment_upload from the packed form: the same resident assignment, bit for bit */
+int32_t zkhip_assignment_upload_packed(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* packed, size_t len,
+                                       zkhip_assignment** out);
 
 /* Steady-state variant for proofs/sec: `count` assignments (each m x 32 B, contiguous), `count`
  * (r, s) pairs (64 B each) and `count` proof slots (8*sz(Fq)+3 B each).  Same results as `count`
@@ -488,7 +537,6 @@ int32_t zkhip_pk_is_bound(const zkhip_pk* pk, const zkhip_r1cs* r1cs);
  * inputs_cap elements of 32 B) receives `public_inputs_values` (/root/reference/zokrates_ast/src/ir/mod.rs:278-288:
  * public arguments in argument order, then ~out_0, ~out_1, ...: the `inputs` of proof.json); a variable without a value
  * gives ZKHIP_ERR_UNSATISFIED (the reference panics with AssignmentMissing). */
-typedef struct zkhip_prog zkhip_prog;
 int32_t zkhip_prog_parse(const uint8_t* bytes, size_t len, zkhip_prog** out);
 void zkhip_prog_free(zkhip_prog* prog);
 int32_t zkhip_prog_dims(const zkhip_prog* prog, uint64_t out[8]);

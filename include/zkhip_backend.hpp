@@ -216,10 +216,17 @@ class Hip {
     bool check(const System& system, const uint8_t* witness, size_t witness_len, uint64_t* first_row = nullptr, uint64_t* n_bad = nullptr);
     bool set_checked(bool on);
     bool checked() const;
+    // Compact witnesses (zkhip.h "compact assignments"): prove() reads the witness straight into the packed form
+    // (zkhip_prog_assignment_packed) and, when that is less than half of the m x 32 B (a witness of bits and small integers), uploads
+    // it packed and proves through the resident entry point; a dense witness takes the usual path.  The same proof either way;
+    // off by default.  Returns the previous setting; last_witness_packed() says which way the last prove() went.
+    bool set_compact_witness(bool on) { const bool was = compact_; compact_ = on; return was; }
+    bool last_witness_packed() const { return last_packed_; }
     std::string describe() const;
 
   private:
     zkhip_ctx* ctx_ = nullptr;
+    bool compact_ = false, last_packed_ = false;
     void check(int32_t rc) const;
 };
 

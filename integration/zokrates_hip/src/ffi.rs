@@ -44,6 +44,18 @@ extern "C" {
     pub fn zkhip_prog_r1cs_load(ctx: *mut zkhip_ctx, prog: *const zkhip_prog, out: *mut *mut zkhip_r1cs) -> i32;
     pub fn zkhip_prog_assignment(prog: *const zkhip_prog, witness: *const u8, len: usize, z_out: *mut u8,
         inputs_out: *mut u8, inputs_cap: u64, n_inputs: *mut u64) -> i32;
+    // compact assignments: a witness of bits packed on the host (no context), widened on the device into an ordinary resident
+    // assignment; `len` of zkhip_assignment_pack >= 32 m says "dense: keep the plain path"
+    pub fn zkhip_assignment_pack_bound(m: u64, bytes: *mut u64) -> i32;
+    pub fn zkhip_assignment_pack(z: *const u8, m: u64, out: *mut u8, cap: u64, len: *mut u64) -> i32;
+    pub fn zkhip_assignment_unpack(packed: *const u8, len: usize, z_out: *mut u8, m_cap: u64, m: *mut u64) -> i32;
+    pub fn zkhip_prog_assignment_packed(prog: *const zkhip_prog, witness: *const u8, len: usize, packed_out: *mut u8,
+        cap: u64, packed_len: *mut u64, inputs_out: *mut u8, inputs_cap: u64, n_inputs: *mut u64) -> i32;
+    pub fn zkhip_assignment_upload_packed(ctx: *mut zkhip_ctx, r1cs: *const zkhip_r1cs, packed: *const u8, len: usize,
+        out: *mut *mut zkhip_assignment) -> i32;
+    pub fn zkhip_assignment_free(z: *mut zkhip_assignment);
+    pub fn zkhip_prove_g16_resident(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, cs: *const zkhip_r1cs, z: *mut zkhip_assignment,
+        r: *const u8, s: *const u8, proof_out: *mut u8, timings: *mut zkhip_timings) -> i32;
     // key cache: the resident form of a loaded key as one image
     pub fn zkhip_pk_export_size(pk: *const zkhip_pk, bytes: *mut u64) -> i32;
     pub fn zkhip_pk_export(pk: *const zkhip_pk, out: *mut u8, cap: u64) -> i32;

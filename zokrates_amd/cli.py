@@ -128,7 +128,14 @@ def cmd_generate_proof(args):
             host["prog"] = prog
             lap("parse_program_ms", t0)
             t0 = time.perf_counter()
-            host["z"], inp = prog.assignment(wdata)    # ark order; inputs = public_inputs_values
+            if args.compact_witness:                   # straight into the packed form; widened here only when it is dense
+                packed, inp = prog.assignment_packed(wdata)
+                if 2 * packed.size < 32 * prog.m:
+                    host["packed"], host["z"] = packed, None
+                else:
+                    host["z"] = native.unpack_assignment(packed)
+            else:
+                host["z"], inp = prog.assignment(wdata)    # ark order; inputs = public_inputs_values
             host["inputs"] = [int.from_bytes(inp[32 * i:32 * i + 32].tobytes(), "little") for i in range(inp.size // 32)]
             lap("witness_to_assignment_ms", t0)
         else:
@@ -176,7 +183,17 @@ def cmd_generate_proof(args):
         if curve_w != cs.curve_id or z.size != 32 * cs.m:
             sys.exit("witness does not match the constraint system")
         inputs = [int.from_bytes(z[32 * i:32 * i + 32].tobytes(), "little") for i in range(1, cs.l)]
+        if args.compact_witness:                       # a .wtns holds the plain m x 32 B: packed here, by the same rule
+            packed = native.pack_assignment(z)
+            if 2 * packed.size < z.size:
+                host["packed"] = packed
     lap("r1cs_upload_ms", t0)
+    resident = None
+    if host.get("packed") is not None:                 # --compact-witness, a witness of bits: widened on the device, proved resident
+        resident = z = native.Assignment.from_packed(ctx, cs, host["packed"])
+        print("compact witness: uploaded packed")
+    elif args.compact_witness:
+        print("compact witness: dense, uploaded plain")
     if args.check:
         # Az o Bz == Cz on the device before proving (zkhip_r1cs_check): a failing witness is refused with its first failing constraint
         t0 = time.perf_counter()
@@ -197,10 +214,10 @@ def cmd_generate_proof(args):
     gen = rng.rng_from_entropy(args.entropy) if args.entropy is not None else rng.StdRng(os.urandom(32))
     if args.proving_scheme == "gm17":
         d1, d2, r = (rng.fr_rand(gen, cs.curve_id) for _ in range(3))
-        raw = native.prove_gm17(ctx, pk, cs, z, d1, d2, r)
+        raw = native.prove_gm17(ctx, pk, cs, z, d1, d2, r)         # (z: host bytes or the resident assignment)
     else:
         r, s = (rng.fr_rand(gen, cs.curve_id) for _ in range(2))
-        raw = native.prove_g16(ctx, pk, cs, z, r, s)
+        raw = native.prove_g16_resident(ctx, pk, cs, resident, r, s) if resident else native.prove_g16(ctx, pk, cs, z, r, s)
     lap("prove_ms", t0)
     t0 = time.perf_counter()
     with open(args.proof_path, "w") as f:
@@ -250,6 +267,7 @@ def main(argv=None):
     g.add_argument("--entropy")
     g.add_argument("--device", type=int, default=0)
     g.add_argument("--check", action="store_true", help="test the witness against the constraints on the GPU first; refuse one that fails, naming the constraint")
+    g.add_argument("--compact-witness", action="store_true", help="read the witness into the packed form and, when that halves it, widen it on the GPU (the same proof.json)")
     g.set_defaults(fn=cmd_generate_proof)
     args = ap.parse_args(argv)
     args.fn(args)

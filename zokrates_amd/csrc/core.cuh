@@ -24,6 +24,7 @@
 #include "ec.cuh"
 #include "kernels_msm.cuh"
 #include "kernels_ntt.cuh"
+#include "zpack.cuh"
 
 namespace zk {
 
@@ -74,6 +75,8 @@ struct ApiError {
 static inline void require(bool ok, int32_t code, const char* msg) {
     if (!ok) throw ApiError{code, msg};
 }
+// what both uploads of an assignment say of a first element that is not the constant
+static const char* const Z0_NOT_ONE_MSG = "z[0] must be 1 (ark instance variable 0 is the constant ONE)";
 
 // ------------------------------------------------------------------ device buffers
 struct DBuf {
@@ -207,6 +210,7 @@ struct zkhip_ctx {
     ProofSlot slots[ZK_NSLOTS];
     ProofSlot* cur = &slots[0];   // the slot the primitives (ntt, msm, ...) and the next enqueue work in
     DBuf tmp;
+    DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed); kept between calls
     std::vector<std::unique_ptr<NttPlanBase>> plans;
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
     // process would leave the second GPU of a process at the 64 KiB default)
@@ -1831,7 +1835,7 @@ struct Prover {
     static void upload_z(zkhip_ctx* ctx, DBuf& dst, u64 m, u64 cap, const uint8_t* z, DBuf& flag) {
         Fr z0 = fe_from_bytes_canon<Fr>(z);
         Fr one = Fr::zero(); one.v[0] = 1;
-        require(z0.equals(one), ZKHIP_ERR_BAD_ARG, "z[0] must be 1 (ark instance variable 0 is the constant ONE)");
+        require(z0.equals(one), ZKHIP_ERR_BAD_ARG, Z0_NOT_ONE_MSG);
         dst.ensure(cap * 32);
         dev_h2d(dst.p, z, m * 32, ctx->stream);
         // every entry must be a canonical field element (checked on the device; the verdict is read with the results)
@@ -2420,6 +2424,25 @@ struct Prover {
         stream_sync(ctx->stream);
         require_canonical(verdict);
     }
+    // the same resident assignment from its packed form (validated on the host: zkhip_api.hip): one copy of the packed bytes, one
+    // launch that widens them and tests the 32-byte values against r, the same verdict word
+    static void assignment_upload_packed(zkhip_ctx* ctx, zkhip_assignment* a, const uint8_t* packed, size_t len, u64 tags_off, u64 index_off,
+                                         u64 payload_off) {
+        Stream s = ctx->stream;
+        DBuf flag;
+        a->scalars.ensure((a->m + 2) * 32);
+        ctx->zpack.ensure(len);
+        dev_h2d(ctx->zpack.p, packed, len, s);
+        flag.ensure(4);
+        dev_memset(flag.p, 0, 4, s);
+        const uint8_t* d = ptr<uint8_t>(ctx->zpack);
+        ZK_LAUNCH((k_unpack_assignment<Fr>), dim3(blocks_for(a->m, ZPACK_BLOCK_ELEMS)), dim3(256), 0, s, d + tags_off, (const u64*)(d + index_off),
+                  d + payload_off, ptr<Fr>(a->scalars), a->m, ptr<u32>(flag));
+        u32 verdict = 0;
+        dev_d2h(&verdict, flag.p, 4, s);
+        stream_sync(s);
+        require_canonical(verdict);
+    }
 
     // generic MSM primitive (bases in ark encoding)
     template <class F, int NC>
@@ -2613,6 +2636,7 @@ struct CurveOps {
                                    size_t*, zkhip_timings*);
     void (*record_from_sums)(zkhip_ctx*, const zkhip_pk*, const uint8_t*, const uint8_t*, uint8_t*);
     void (*assignment_upload)(zkhip_ctx*, zkhip_assignment*, const uint8_t*);
+    void (*assignment_upload_packed)(zkhip_ctx*, zkhip_assignment*, const uint8_t*, size_t, u64, u64, u64);
     void (*r1cs_check)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const void*, u64 out[2]);
     void (*ntt)(zkhip_ctx*, u32, int, uint8_t*);
     void (*witness_map)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, uint8_t*);
@@ -2675,6 +2699,7 @@ static CurveOps make_curve_ops() {
     o.gm17_prove_device_sums = &Gm17<C>::prove_device_sums;
     o.record_from_sums = &Prover<C>::record_from_sums;
     o.assignment_upload = &Prover<C>::assignment_upload;
+    o.assignment_upload_packed = &Prover<C>::assignment_upload_packed;
     o.r1cs_check = &Prover<C>::r1cs_check;
     o.ntt = &Prover<C>::ntt_api;
     o.witness_map = &Prover<C>::witness_map_api;

@@ -332,12 +332,32 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     const size_t fq = curve == ZKHIP_CURVE_BN128 ? 32 : 48;
     // (1) the assignment in ark order and the public inputs as the ark backend computes them (groth16.rs:33-38)
     auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint8_t> z(program.variables() * 32);
+    const uint64_t m = program.variables();
+    std::vector<uint8_t> z, packed;
     const uint64_t cap = witness_len / 40 + 2;
     std::vector<uint8_t> inputs(cap * 32);
-    uint64_t n_inputs = 0;
-    int32_t rc = zkhip_prog_assignment(program.get(), witness, witness_len, z.data(), inputs.data(), cap, &n_inputs);
-    if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
+    uint64_t n_inputs = 0, packed_len = 0;
+    int32_t rc;
+    last_packed_ = false;
+    if (compact_) {
+        // the witness straight into the packed form; packed when that is less than half of the plain bytes, else widened on the host
+        uint64_t bound = 0;
+        zkhip_assignment_pack_bound(m, &bound);
+        packed.resize(bound);
+        rc = zkhip_prog_assignment_packed(program.get(), witness, witness_len, packed.data(), bound, &packed_len, inputs.data(), cap, &n_inputs);
+        if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
+        last_packed_ = 2 * packed_len < 32 * m;
+        if (!last_packed_) {
+            z.resize(m * 32);
+            uint64_t got = 0;
+            rc = zkhip_assignment_unpack(packed.data(), packed_len, z.data(), m, &got);
+            if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
+        }
+    } else {
+        z.resize(m * 32);
+        rc = zkhip_prog_assignment(program.get(), witness, witness_len, z.data(), inputs.data(), cap, &n_inputs);
+        if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
+    }
     if (tm) tm->witness_to_assignment = ms_since(t0);
     // (2) the constraint system: resident
     zkhip_r1cs* cs = system.get();
@@ -345,13 +365,20 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     // (3) the blinding scalars: the first draws ark makes from the caller's RNG; (4) the GPU
     t0 = std::chrono::steady_clock::now();
     std::vector<uint8_t> raw(8 * fq + 3);
+    struct Resident {      // the packed witness widened on the device (zkhip_assignment_upload_packed)
+        zkhip_assignment* a = nullptr;
+        ~Resident() { if (a) zkhip_assignment_free(a); }
+    } resident;
+    if (last_packed_) check(zkhip_assignment_upload_packed(ctx_, cs, packed.data(), packed_len, &resident.a));
     if (scheme == Scheme::GM17) {
         uint8_t rnd[96];
         for (int i = 0; i < 3; ++i) memcpy(rnd + 32 * i, fr_rand(rng, curve).data(), 32);      // d1, d2, r
-        rc = zkhip_prove_gm17(ctx_, key.get(), cs, z.data(), rnd, raw.data(), nullptr);
+        rc = last_packed_ ? zkhip_prove_gm17_resident(ctx_, key.get(), cs, resident.a, rnd, raw.data(), nullptr)
+                          : zkhip_prove_gm17(ctx_, key.get(), cs, z.data(), rnd, raw.data(), nullptr);
     } else {
         const std::array<uint8_t, 32> r = fr_rand(rng, curve), s = fr_rand(rng, curve);
-        rc = zkhip_prove_g16(ctx_, key.get(), cs, z.data(), r.data(), s.data(), raw.data(), nullptr);
+        rc = last_packed_ ? zkhip_prove_g16_resident(ctx_, key.get(), cs, resident.a, r.data(), s.data(), raw.data(), nullptr)
+                          : zkhip_prove_g16(ctx_, key.get(), cs, z.data(), r.data(), s.data(), raw.data(), nullptr);
     }
     check(rc);
     if (tm) tm->prove = ms_since(t0);

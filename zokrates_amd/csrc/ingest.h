@@ -42,4 +42,22 @@ uint64_t prog_write_bound(uint64_t n, uint64_t nnz, uint64_t n_args);
 uint64_t prog_write(int curve, uint64_t n, uint64_t m, const uint64_t* const rp[3], const uint32_t* const col[3], const uint8_t* const val[3],
                     const int64_t* ids, const int64_t* arg_ids, const uint8_t* arg_private, uint64_t n_args, uint32_t return_count, uint8_t* out,
                     uint64_t cap);
+
+// ---- compact assignments (the "ZKHIPZ1" form of include/zkhip.h): 2-bit width classes, a block index, the values' low bytes
+static constexpr uint64_t ZPACK_BLOCK = 1024;      // elements per block (one workgroup of k_unpack_assignment)
+// where the sections of a packed buffer of m elements are; `total` = the whole length (payload_bytes as given)
+struct PackedLayout {
+    uint64_t m = 0, payload_bytes = 0, nblocks = 0, tags_off = 0, index_off = 0, payload_off = 0, total = 0;
+};
+PackedLayout packed_layout(uint64_t m, uint64_t payload_bytes);
+// the length a packing of z takes (written to *need even when `cap` is too small, which is refused before anything is written);
+// throws IngestError for a z entry that is canonical in no supported field
+void assignment_pack(const uint8_t* z, uint64_t m, uint8_t* out, uint64_t cap, uint64_t* need);
+// every rule of the format, on the host; throws IngestError (ZKHIP_ERR_PARSE) naming the one that fails
+PackedLayout assignment_packed_validate(const uint8_t* packed, size_t len);
+void assignment_unpack(const uint8_t* packed, const PackedLayout& ly, uint8_t* z_out);      // (a validated buffer)
+// whether element 0 of a validated buffer is the value 1
+bool packed_first_is_one(const uint8_t* packed, const PackedLayout& ly);
+void prog_assignment_packed(const zkhip_prog* prog, const uint8_t* wit, size_t len, uint8_t* packed_out, uint64_t cap, uint64_t* packed_len,
+                            uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs);
 }  // namespace zk

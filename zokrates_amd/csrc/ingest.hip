@@ -750,4 +750,149 @@ void prog_assignment(const zkhip_prog* prog, const uint8_t* wit, size_t len, uin
     }
 }
 
+// ------------------------------------------------------------------ compact assignments ("ZKHIPZ1", include/zkhip.h)
+namespace {
+const uint8_t ZPACK_MAGIC[8] = {'Z', 'K', 'H', 'I', 'P', 'Z', '1', 0};
+const uint32_t ZPACK_WIDTH[4] = {0, 1, 8, 32};
+inline uint64_t round16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
+// the smallest class that holds a 32-byte little-endian value
+inline int zpack_class(const uint8_t* v) {
+    uint64_t q[4];
+    memcpy(q, v, 32);
+    if (q[1] | q[2] | q[3]) return 3;
+    return q[0] == 0 ? 0 : q[0] < 256 ? 1 : 2;
+}
+// payload bytes of the four elements of one tag byte
+struct TagWidths {
+    uint8_t sum[256];
+    TagWidths() {
+        for (int t = 0; t < 256; ++t) sum[t] = (uint8_t)(ZPACK_WIDTH[t & 3] + ZPACK_WIDTH[(t >> 2) & 3] + ZPACK_WIDTH[(t >> 4) & 3] + ZPACK_WIDTH[t >> 6]);
+    }
+};
+const TagWidths TAG_WIDTHS;
+}  // namespace
+
+PackedLayout packed_layout(uint64_t m, uint64_t payload_bytes) {
+    PackedLayout ly;
+    ly.m = m;
+    ly.payload_bytes = payload_bytes;
+    ly.nblocks = (m + ZPACK_BLOCK - 1) / ZPACK_BLOCK;
+    ly.tags_off = 32;
+    ly.index_off = ly.tags_off + round16((m + 3) / 4);
+    ly.payload_off = ly.index_off + 8 * ((ly.nblocks + 2) & ~(uint64_t)1);      // nblocks + 1 entries, made even
+    ly.total = ly.payload_off + payload_bytes;
+    return ly;
+}
+
+void assignment_pack(const uint8_t* z, uint64_t m, uint8_t* out, uint64_t cap, uint64_t* need) {
+    if (m >= (uint64_t)1 << 56) fail(ZKHIP_ERR_BAD_ARG, "assignment too large to pack");
+    // classes and block sizes first: the length is known, and `cap` tested, before a byte is written
+    PackedLayout ly = packed_layout(m, 0);
+    std::vector<uint8_t> tags(ly.index_off - ly.tags_off, 0);
+    std::vector<uint64_t> index((ly.payload_off - ly.index_off) / 8, 0);
+    for (uint64_t b = 0; b < ly.nblocks; ++b) {
+        uint64_t bytes = 0;
+        const uint64_t hi = std::min(m, (b + 1) * ZPACK_BLOCK);
+        for (uint64_t i = b * ZPACK_BLOCK; i < hi; ++i) {
+            const int c = zpack_class(z + 32 * i);
+            // (wider than every supported scalar field: canonical nowhere.  Between a smaller field's r and this bound only the
+            // upload can tell, on the device: it knows the curve)
+            if (c == 3 && !canonical32<Bls381Fr>(z + 32 * i)) fail(ZKHIP_ERR_BAD_ARG, "assignment entry " + std::to_string(i) + " is not a canonical field element of any supported curve");
+            tags[i / 4] |= (uint8_t)(c << (2 * (i % 4)));
+            bytes += ZPACK_WIDTH[c];
+        }
+        index[b + 1] = index[b] + round16(bytes);
+    }
+    ly = packed_layout(m, index[ly.nblocks]);
+    if (need) *need = ly.total;
+    if (cap < ly.total) fail(ZKHIP_ERR_BAD_ARG, "packed buffer too small: " + std::to_string(ly.total) + " bytes needed (zkhip_assignment_pack_bound)");
+    memset(out, 0, ly.total);
+    memcpy(out, ZPACK_MAGIC, 8);
+    memcpy(out + 8, &ly.m, 8);
+    memcpy(out + 16, &ly.payload_bytes, 8);
+    const uint32_t block = (uint32_t)ZPACK_BLOCK;
+    memcpy(out + 24, &block, 4);
+    if (!tags.empty()) memcpy(out + ly.tags_off, tags.data(), tags.size());
+    memcpy(out + ly.index_off, index.data(), index.size() * 8);
+    uint8_t* pay = out + ly.payload_off;
+    for (uint64_t b = 0; b < ly.nblocks; ++b) {
+        uint8_t* p = pay + index[b];
+        const uint64_t hi = std::min(m, (b + 1) * ZPACK_BLOCK);
+        for (uint64_t i = b * ZPACK_BLOCK; i < hi; ++i) {
+            const uint32_t w = ZPACK_WIDTH[(tags[i / 4] >> (2 * (i % 4))) & 3];
+            memcpy(p, z + 32 * i, w);
+            p += w;
+        }
+    }
+}
+
+PackedLayout assignment_packed_validate(const uint8_t* packed, size_t len) {
+    if (len < 32) fail(ZKHIP_ERR_PARSE, "packed assignment truncated (shorter than its header)");
+    if (memcmp(packed, ZPACK_MAGIC, 8)) fail(ZKHIP_ERR_PARSE, "not a packed assignment (magic is not \"ZKHIPZ1\")");
+    uint32_t block, flags;
+    memcpy(&block, packed + 24, 4);
+    memcpy(&flags, packed + 28, 4);
+    if (block != ZPACK_BLOCK) fail(ZKHIP_ERR_PARSE, "packed assignment: block is " + std::to_string(block) + ", only 1024 is accepted");
+    if (flags != 0) fail(ZKHIP_ERR_PARSE, "packed assignment: flags must be 0");
+    const uint64_t m = rd64(packed + 8), payload_bytes = rd64(packed + 16);
+    if (m / 4 > len || payload_bytes > len) fail(ZKHIP_ERR_PARSE, "packed assignment: length does not match header + tags + index + payload");
+    const PackedLayout ly = packed_layout(m, payload_bytes);
+    if (ly.total != len) fail(ZKHIP_ERR_PARSE, "packed assignment: length does not match header + tags + index + payload (" + std::to_string(ly.total) + " expected)");
+    if (payload_bytes % 16) fail(ZKHIP_ERR_PARSE, "packed assignment: payload_bytes is not a multiple of 16");
+    // the index: 0 .. payload_bytes, monotone, 16-aligned, its padding entry zero
+    const uint8_t* ix = packed + ly.index_off;
+    const uint64_t entries = (ly.payload_off - ly.index_off) / 8;
+    if (rd64(ix) != 0) fail(ZKHIP_ERR_PARSE, "packed assignment: index[0] is not 0");
+    if (rd64(ix + 8 * ly.nblocks) != payload_bytes) fail(ZKHIP_ERR_PARSE, "packed assignment: the last index entry is not payload_bytes");
+    if (entries > ly.nblocks + 1 && rd64(ix + 8 * (ly.nblocks + 1)) != 0) fail(ZKHIP_ERR_PARSE, "packed assignment: the index's padding entry is not zero");
+    // the tags: the span of every block is the 16-rounded sum of its widths; unused bits and padding bytes are zero
+    const uint8_t* tags = packed + ly.tags_off;
+    const uint64_t ntag = (m + 3) / 4;
+    for (uint64_t b = 0; b < ly.nblocks; ++b) {
+        const uint64_t lo = rd64(ix + 8 * b), hi = rd64(ix + 8 * (b + 1));
+        if (lo % 16 || hi % 16) fail(ZKHIP_ERR_PARSE, "packed assignment: index entry of block " + std::to_string(b) + " is not a multiple of 16");
+        if (hi < lo) fail(ZKHIP_ERR_PARSE, "packed assignment: index not monotone at block " + std::to_string(b));
+        uint64_t bytes = 0;
+        const uint64_t t1 = std::min(ntag, (b + 1) * (ZPACK_BLOCK / 4));
+        for (uint64_t t = b * (ZPACK_BLOCK / 4); t < t1; ++t) bytes += TAG_WIDTHS.sum[tags[t]];
+        if (hi - lo != round16(bytes)) fail(ZKHIP_ERR_PARSE, "packed assignment: the index span of block " + std::to_string(b) + " does not match the widths of its tags");
+    }
+    if (m % 4 && (tags[ntag - 1] >> (2 * (m % 4)))) fail(ZKHIP_ERR_PARSE, "packed assignment: tag bits past the last element are not zero");
+    for (uint64_t t = ntag; t < ly.index_off - ly.tags_off; ++t)
+        if (tags[t]) fail(ZKHIP_ERR_PARSE, "packed assignment: the tags' padding is not zero");
+    return ly;
+}
+
+void assignment_unpack(const uint8_t* packed, const PackedLayout& ly, uint8_t* z_out) {
+    const uint8_t* tags = packed + ly.tags_off;
+    if (ly.m) memset(z_out, 0, ly.m * 32);
+    for (uint64_t b = 0; b < ly.nblocks; ++b) {
+        const uint8_t* p = packed + ly.payload_off + rd64(packed + ly.index_off + 8 * b);
+        const uint64_t hi = std::min(ly.m, (b + 1) * ZPACK_BLOCK);
+        for (uint64_t i = b * ZPACK_BLOCK; i < hi; ++i) {
+            const uint32_t w = ZPACK_WIDTH[(tags[i / 4] >> (2 * (i % 4))) & 3];
+            memcpy(z_out + 32 * i, p, w);
+            p += w;
+        }
+    }
+}
+
+bool packed_first_is_one(const uint8_t* packed, const PackedLayout& ly) {
+    if (ly.m == 0) return false;
+    const uint32_t w = ZPACK_WIDTH[packed[ly.tags_off] & 3];
+    uint8_t v[32] = {0};
+    memcpy(v, packed + ly.payload_off, w);
+    if (v[0] != 1) return false;
+    for (int i = 1; i < 32; ++i) if (v[i]) return false;
+    return true;
+}
+
+void prog_assignment_packed(const zkhip_prog* prog, const uint8_t* wit, size_t len, uint8_t* packed_out, uint64_t cap, uint64_t* packed_len,
+                            uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs) {
+    const uint64_t m = prog->l + prog->w;
+    zkhip_raw_vector<uint8_t> z(m * 32);
+    prog_assignment(prog, wit, len, z.data(), inputs_out, inputs_cap, n_inputs);
+    assignment_pack(z.data(), m, packed_out, cap, packed_len);
+}
+
 }  // namespace zk

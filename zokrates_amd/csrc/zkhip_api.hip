@@ -474,6 +474,55 @@ int32_t zkhip_assignment_upload(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const ui
 }
 void zkhip_assignment_free(zkhip_assignment* a) { delete a; }
 
+// ---- compact assignments: the host-only packer / unpacker (no context), and the upload from the packed form
+// (the kernel clamps nothing: what the host validates per block must be what one workgroup takes)
+static_assert(ZPACK_BLOCK == ZPACK_BLOCK_ELEMS, "the host validates blocks of the size the kernel widens");
+int32_t zkhip_assignment_pack_bound(uint64_t m, uint64_t* bytes) {
+    if (!bytes || m >= (uint64_t)1 << 56) { g_create_err = "bad argument"; return ZKHIP_ERR_BAD_ARG; }
+    *bytes = packed_layout(m, 32 * m).total;      // every element 32 bytes wide: no block needs padding
+    return ZKHIP_OK;
+}
+int32_t zkhip_assignment_pack(const uint8_t* z, uint64_t m, uint8_t* out, uint64_t cap, uint64_t* len) {
+    if ((!z && m) || !out || !len) { g_create_err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
+    return guarded_host([&] { assignment_pack(z, m, out, cap, len); });
+}
+int32_t zkhip_assignment_unpack(const uint8_t* packed, size_t len, uint8_t* z_out, uint64_t m_cap, uint64_t* m) {
+    if (!packed || !m) { g_create_err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
+    return guarded_host([&] {
+        const PackedLayout ly = assignment_packed_validate(packed, len);
+        *m = ly.m;
+        if (ly.m > m_cap || (!z_out && ly.m)) throw IngestError{ZKHIP_ERR_BAD_ARG, "z_out holds " + std::to_string(m_cap) + " elements, the packed assignment has " + std::to_string(ly.m)};
+        assignment_unpack(packed, ly, z_out);
+    });
+}
+int32_t zkhip_prog_assignment_packed(const zkhip_prog* prog, const uint8_t* witness, size_t len, uint8_t* packed_out, uint64_t cap,
+                                     uint64_t* packed_len, uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs) {
+    if (!prog || !witness || !packed_out || !packed_len) { g_create_err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
+    return guarded_host([&] { prog_assignment_packed(prog, witness, len, packed_out, cap, packed_len, inputs_out, inputs_cap, n_inputs); });
+}
+int32_t zkhip_assignment_upload_packed(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* packed, size_t len, zkhip_assignment** out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {
+        require(r1cs && packed && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        require(r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "constraint system belongs to another context");
+        // the whole structure on the host, before anything is enqueued: the kernel never sees an inconsistent buffer
+        PackedLayout ly;
+        try {
+            ly = assignment_packed_validate(packed, len);
+        } catch (const IngestError& e) {
+            throw ApiError{e.code, e.msg};
+        }
+        const std::string dims = "the packed assignment has " + std::to_string(ly.m) + " elements, the constraint system " + std::to_string(r1cs->l + r1cs->w) + " variables (l + w)";
+        require(ly.m == r1cs->l + r1cs->w, ZKHIP_ERR_BAD_ARG, dims.c_str());
+        require(packed_first_is_one(packed, ly), ZKHIP_ERR_BAD_ARG, Z0_NOT_ONE_MSG);
+        std::unique_ptr<zkhip_assignment> a(new zkhip_assignment());
+        a->curve = r1cs->curve; a->ctx = ctx; a->m = ly.m;
+        ops_for(r1cs->curve)->assignment_upload_packed(ctx, a.get(), packed, len, ly.tags_off, ly.index_off, ly.payload_off);
+        *out = a.release();
+    });
+}
+
 int32_t zkhip_prove_g16_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_assignment* z, const uint8_t* r,
                                  const uint8_t* s, uint8_t* proof_out, zkhip_timings* timings) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;

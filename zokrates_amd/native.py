@@ -72,6 +72,8 @@ class Library:
         "zkhip_multi_pk_load_g16", "zkhip_multi_pk_load_gm17", "zkhip_prove_g16_multi", "zkhip_prove_gm17_multi",
         "zkhip_multi_pk_load_g16_replicas", "zkhip_prove_g16_multi_batch", "zkhip_multi_use_rccl", "zkhip_multi_exchange",
         "zkhip_r1cs_check", "zkhip_ctx_set_checked", "zkhip_ctx_unsatisfied",
+        "zkhip_assignment_pack_bound", "zkhip_assignment_pack", "zkhip_assignment_unpack", "zkhip_prog_assignment_packed",
+        "zkhip_assignment_upload_packed",
     ]
 
     def __init__(self, path=None):
@@ -163,6 +165,11 @@ class Library:
         L.zkhip_r1cs_check.restype = i32; L.zkhip_r1cs_check.argtypes = [vp] * 6
         L.zkhip_ctx_set_checked.restype = i32; L.zkhip_ctx_set_checked.argtypes = [vp, i32]
         L.zkhip_ctx_unsatisfied.restype = i32; L.zkhip_ctx_unsatisfied.argtypes = [vp, u32, vp, vp, vp, vp]
+        L.zkhip_assignment_pack_bound.restype = i32; L.zkhip_assignment_pack_bound.argtypes = [u64, vp]
+        L.zkhip_assignment_pack.restype = i32; L.zkhip_assignment_pack.argtypes = [vp, u64, vp, u64, vp]
+        L.zkhip_assignment_unpack.restype = i32; L.zkhip_assignment_unpack.argtypes = [vp, sz, vp, u64, vp]
+        L.zkhip_prog_assignment_packed.restype = i32; L.zkhip_prog_assignment_packed.argtypes = [vp, vp, sz, vp, u64, vp, vp, u64, vp]
+        L.zkhip_assignment_upload_packed.restype = i32; L.zkhip_assignment_upload_packed.argtypes = [vp, vp, vp, sz, pp]
         self.L = L
 
     def init(self, hw_queues):
@@ -436,6 +443,17 @@ class Assignment:
         self.h = C.c_void_p()
         ctx._check(ctx.lib.L.zkhip_assignment_upload(ctx.h, cs.h, _ptr(z), C.byref(self.h)))
 
+    @classmethod
+    def from_packed(cls, ctx, cs, packed):
+        """`zkhip_assignment_upload_packed`: the same resident assignment from its packed form (`pack_assignment`,
+        `Program.assignment_packed`), widened on the device."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        packed = _u8(packed)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.L.zkhip_assignment_upload_packed(ctx.h, cs.h, _ptr(packed), packed.size, C.byref(self.h)))
+        return self
+
     def close(self):
         if self.h:
             self.ctx.lib.L.zkhip_assignment_free(self.h)
@@ -446,6 +464,48 @@ class Assignment:
             self.close()
         except Exception:
             pass
+
+
+def pack_bound(m, library=None):
+    """`zkhip_assignment_pack_bound`: the length of a packing of m elements that are all 32 bytes wide."""
+    lib = library or default_library()
+    out = C.c_uint64()
+    rc = lib.L.zkhip_assignment_pack_bound(int(m), C.byref(out))
+    if rc != 0:
+        raise ZkhipError(rc, lib.L.zkhip_last_error(None).decode())
+    return int(out.value)
+
+
+def pack_assignment(z, library=None, cap=None):
+    """`zkhip_assignment_pack` (host only): uint8[m*32] -> the packed form as uint8[len].  len >= 32 m says the witness is dense
+    and the plain upload is the one to use.  `cap`: the size of the output buffer (default: the bound)."""
+    lib = library or default_library()
+    z = _u8(z)
+    if z.size % 32:
+        raise ValueError("an assignment is m x 32 bytes")
+    m = z.size // 32
+    cap = pack_bound(m, lib) if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_uint64()
+    rc = lib.L.zkhip_assignment_pack(_ptr(z), m, _ptr(out), cap, C.byref(n))
+    if rc != 0:
+        raise ZkhipError(rc, lib.L.zkhip_last_error(None).decode())
+    return out[:n.value].copy()
+
+
+def unpack_assignment(packed, library=None, m_cap=None):
+    """`zkhip_assignment_unpack` (host only): the packed form -> uint8[m*32].  `m_cap`: the elements the output may hold
+    (default: the count the header names, within what a buffer of that length can hold)."""
+    lib = library or default_library()
+    packed = _u8(packed)
+    if m_cap is None:
+        m_cap = min(int.from_bytes(packed[8:16].tobytes(), "little"), 4 * packed.size) if packed.size >= 16 else 0
+    z = np.zeros(max(int(m_cap), 1) * 32, dtype=np.uint8)
+    m = C.c_uint64()
+    rc = lib.L.zkhip_assignment_unpack(_ptr(packed), packed.size, _ptr(z), int(m_cap), C.byref(m))
+    if rc != 0:
+        raise ZkhipError(rc, lib.L.zkhip_last_error(None).decode())
+    return z[:32 * m.value].copy()
 
 
 def prove_g16_resident(ctx, pk, cs, assignment, r, s, want_timings=False):
@@ -695,6 +755,20 @@ class Program:
         if rc != 0:
             raise ZkhipError(rc, self.lib.L.zkhip_last_error(None).decode())
         return z, inputs[:32 * n_in.value].copy()
+
+    def assignment_packed(self, witness_bytes):
+        """`zkhip_prog_assignment_packed`: (the packed form of z, inputs) — `pack_assignment(self.assignment(w)[0])` without the
+        caller holding the m x 32 B in between."""
+        wit = _u8(witness_bytes)
+        pcap = pack_bound(self.m, self.lib)
+        packed = np.zeros(pcap, dtype=np.uint8)
+        cap = self.n_public_args + wit.size // 40 + 1
+        inputs = np.zeros(cap * 32, dtype=np.uint8)
+        n_in, n_packed = C.c_uint64(), C.c_uint64()
+        rc = self.lib.L.zkhip_prog_assignment_packed(self.h, _ptr(wit), wit.size, _ptr(packed), pcap, C.byref(n_packed), _ptr(inputs), cap, C.byref(n_in))
+        if rc != 0:
+            raise ZkhipError(rc, self.lib.L.zkhip_last_error(None).decode())
+        return packed[:n_packed.value].copy(), inputs[:32 * n_in.value].copy()
 
     def close(self):
         if self.h:
