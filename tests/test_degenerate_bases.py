@@ -29,6 +29,7 @@ from oracle.fields import BN254, BLS12_381
 from zokrates_amd import native
 
 from emu_util import emu_library
+from size_ladder import adhoc_window, table_window      # the shape model: the widths msm_shape picks, without and with tables
 
 CURVES = {0: BN254, 1: BLS12_381, 2: ref.CURVE}
 RUN = 40                                   # length of the runs of equal and of alternating bases
@@ -65,22 +66,6 @@ def scalar_bits(curve):
 
 def windows(curve, c):
     return (scalar_bits(curve) + 1 + c - 1) // c
-
-
-def adhoc_window(n, bits):
-    """The window width an ad-hoc MSM of n points picks by itself (msm_shape without a table): about log2(n) - 5, moved to the
-    nearest width whose top window is full or whose top buckets stay below 4096 points each."""
-    lg = max(n, 1).bit_length() - 1
-    want = max(2, min(16, lg - 5))
-    for d in range(15):
-        for cand in (want + d, want - d):
-            if cand < 2 or cand > 16:
-                continue
-            W = (bits + 1 + cand - 1) // cand
-            top_bits = bits + 1 - (W - 1) * cand
-            if top_bits >= cand or (n >> (top_bits - 1)) <= 4096:
-                return cand
-    return want
 
 
 def recode(k, c, W):
@@ -328,17 +313,6 @@ def test_gpu_msm_structured_groups(gpu_ctx, shape):
 
 
 # ------------------------------------------------------------------ proofs over circuits with twin variables (honest keys)
-def table_window(m, bits):
-    """The window width of a resident key of m variables (msm_shape with tables): the fewest windows the widest admissible width
-    gives, and of the widths with that many windows the narrowest."""
-    cmax = max(2, min(17, max(m, 1).bit_length()))
-    wmin = (bits + 1 + cmax - 1) // cmax
-    c = cmax
-    while c > 2 and (bits + 1 + (c - 1) - 1) // (c - 1) == wmin:
-        c -= 1
-    return c
-
-
 def witness_values(curve, rnd, m_about, extra=6):
     """The common witness values of the groups, drawn like the scalars of the MSM cases: the edge lists of the key's own window
     width and of the widest one, and full-width random values."""
