@@ -31,6 +31,31 @@
  *    pending proof's buffers and on its streams) — returns ZKHIP_ERR_BAD_ARG with a message that names the pending split proof,
  *    before anything is enqueued, and leaves the pending proof as it is.  Freeing a handle a pending proof uses is the caller's
  *    error, as it is during any call.
+ *  - A proof queue (zkhip_queue_open .. zkhip_queue_close, below) keeps up to its capacity of proofs in flight across calls — the
+ *    pipeline of the *_batch calls with the caller as the loop.  Order and capacity: capacity is the context's ZKHIP_TUNE_SLOTS when
+ *    the queue is opened; tickets count from 0 per queue; collect is first in, first out; a submit at capacity returns ZKHIP_ERR_BUSY and
+ *    a collect on an empty queue ZKHIP_ERR_BAD_ARG, and neither changes anything; proofs are enqueued exactly as the batch calls enqueue
+ *    theirs, slots round-robin, so submit, submit, submit, collect, submit, collect ... is the batch calls' own schedule.  Bytes: every
+ *    collected proof is byte-identical to what zkhip_prove_g16 / zkhip_prove_gm17 returns for the same inputs, for any order of calls,
+ *    a bound or an unbound key, and each of the three witness sources.  Buffers: z, packed and rnd belong to the caller again as soon as
+ *    submit returns (the library copies host memory through its own pinned ring; the measurement switch ZKHIP_COPY_MODE=0, which
+ *    hands the caller's pointer to the runtime instead, gives that up); a resident assignment must stay alive until its ticket is
+ *    collected.  Failures of ONE proof fail that ticket only
+ *    and leave every other proof in flight as it is: an entry that is not canonical (found on the device; ZKHIP_ERR_BAD_ARG at collect,
+ *    the message of zkhip_prove_g16), an assignment that does not satisfy the system in checked mode (ZKHIP_ERR_UNSATISFIED at collect,
+ *    the output zero-filled, the message names the ticket and the constraint, zkhip_ctx_unsatisfied reports one triple with proof index
+ *    0), and a submit refused for its arguments — null or both sources, z[0] != 1, a blinding scalar that is not canonical, an assignment
+ *    of another system, a malformed packed buffer (ZKHIP_ERR_PARSE, the messages of zkhip_assignment_upload_packed) — which consumes no
+ *    ticket.  Only a device error breaks the queue: it is kept, every ticket still in flight collects with ZKHIP_ERR_DEVICE and its text,
+ *    further submits answer the same, and zkhip_queue_close still works.  Pending: an open queue makes its context pending in the sense
+ *    of the split-proof paragraph above — every call that paragraph refuses is refused, on the host and before anything is enqueued,
+ *    with ZKHIP_ERR_BAD_ARG and a message that names the open queue (zkhip_prove_g16_split_begin and a second zkhip_queue_open among
+ *    them; zkhip_queue_open while a split proof is pending gets that paragraph's message); the calls it lets through stay allowed
+ *    (zkhip_prove_g16_split_end finds nothing pending, zkhip_prove_g16_split_abort has nothing to drop).  Checked mode is read when the
+ *    queue is opened.  Freeing the key, the constraint system or the context under an open queue is the caller's error.  Resources:
+ *    opening, submitting and collecting create no stream and no event beyond the ones the proof slots own, and allocate nothing once
+ *    every slot has been used (a packed buffer longer than any before grows the context's one buffer for packed bytes): a process near
+ *    the hardware-queue budget of INTEGRATION.md section 4 stays where it is.
  *  - There is no CPU fallback: without a usable gfx950 device zkhip_ctx_create fails with
  *    ZKHIP_ERR_DEVICE.
  */
@@ -52,6 +77,7 @@ extern "C" {
 #define ZKHIP_ERR_UNSATISFIED (-5)  /* the assignment does not satisfy the R1CS: zkhip_r1cs_check, and the single-GPU prove calls of a
                                      * context in checked mode (zkhip_ctx_set_checked); also zkhip_prog_assignment for a variable
                                      * the witness file gives no value                                                            */
+#define ZKHIP_ERR_BUSY (-6)         /* zkhip_queue_submit*: as many proofs in flight as the queue holds; collect one first        */
 
 /* curve ids; names are zokrates_common::constants (/root/reference/zokrates_common/src/constants.rs:5-9) */
 #define ZKHIP_CURVE_BN128 0
@@ -303,6 +329,30 @@ int32_t zkhip_ctx_set_checked(zkhip_ctx* ctx, int32_t on);
  * row, failing rows) triples, in proof order; *count = how many proofs of the call failed. */
 int32_t zkhip_ctx_unsatisfied(const zkhip_ctx* ctx, uint32_t cap, uint32_t* proof_idx, uint64_t* first_row,
                               uint64_t* n_bad, uint32_t* count);
+
+/* ---- proof queue: proofs in flight across calls ----
+ * The *_batch calls reach their rate by keeping ZKHIP_TUNE_SLOTS proofs in flight, and drain that pipeline before they return.  A
+ * prover service receives its witnesses one at a time: a queue over one (context, key, constraint system) lets it submit each as
+ * it arrives and collect the oldest when it wants it — the same pipeline, kept full by the caller.  The scheme is the key's (Groth16
+ * or GM17); whole keys only (a shard is refused); one queue per context.  The contract is in Conventions above.
+ *   submit        : exactly one of z (m x 32 B, host memory) and z_resident; rnd = r | s (64 B, Groth16) or d1 | d2 | r (96 B, GM17);
+ *                   *ticket (may be NULL) = the proof's number.  No host synchronisation.
+ *   submit_packed : the assignment in the packed form of zkhip_assignment_pack, validated on the host like
+ *                   zkhip_assignment_upload_packed and widened on the device into the proof's own buffer; unlike that upload it does not
+ *                   wait for the device: whether every 32-byte value is below r is read when the ticket is collected
+ *   ready         : never blocks.  *ready = 1 if the OLDEST proof in flight is done on the device (collect will not wait), 0 if it is
+ *                   not or the queue is empty
+ *   collect       : the oldest proof; blocks until it is done.  *ticket (may be NULL) = its number, proof_out as zkhip_prove_g16,
+ *                   timings optional (total_ms: from submit to the end of collect)
+ *   close         : waits for what is in flight, discards it, frees q.  The context is an ordinary context again. */
+typedef struct zkhip_queue zkhip_queue;
+int32_t zkhip_queue_open(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_queue** out);
+int32_t zkhip_queue_state(const zkhip_queue* q, uint32_t* capacity, uint32_t* in_flight);
+int32_t zkhip_queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* z_resident, const uint8_t* rnd, uint64_t* ticket);
+int32_t zkhip_queue_submit_packed(zkhip_queue* q, const uint8_t* packed, size_t len, const uint8_t* rnd, uint64_t* ticket);
+int32_t zkhip_queue_ready(zkhip_queue* q, int32_t* ready);
+int32_t zkhip_queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, zkhip_timings* timings);
+int32_t zkhip_queue_close(zkhip_queue* q);
 
 /* ---- one proof across several GPUs ----
  * Every MSM is a sum over independent (scalar, base) pairs, so rank k of `world` loads only its index range of

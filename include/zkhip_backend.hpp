@@ -165,6 +165,42 @@ struct Timings {
     double witness_to_assignment = 0, r1cs_upload = 0, prove = 0;
 };
 
+class Hip;
+// Witnesses that arrive ONE AT A TIME, proved at the rate of a batch (zkhip.h "proof queue"): up to capacity() proofs of one resident
+// (System, Key) in flight across calls.  submit() reads the witness, draws the blinding scalars from the caller's RNG in the order
+// Hip::prove draws them (so equal seeds give equal proofs, whatever the order of submit and collect) and returns without waiting for
+// the device; collect() returns the OLDEST proof.  It honours Hip::set_compact_witness with prove()'s rule — a witness whose packed form
+// is less than half of the m x 32 B goes to the device packed (zkhip_queue_submit_packed).  While a Queue is open its Hip refuses
+// every other proving call (zkhip.h, Conventions); close() — or the destructor — drops what is uncollected.  The Hip, the System and
+// the Key must outlive it.  An Error from collect() concerns that one proof (its ticket is spent); the others stay in flight.
+class Queue {
+  public:
+    Queue() = default;
+    ~Queue();
+    Queue(Queue&& o) noexcept;
+    Queue& operator=(Queue&& o) noexcept;
+    Queue(const Queue&) = delete;
+    Queue& operator=(const Queue&) = delete;
+    uint32_t capacity() const;
+    uint32_t in_flight() const;
+    bool full() const { return in_flight() >= capacity(); }
+    uint64_t submit(const uint8_t* witness, size_t witness_len, StdRng& rng);      // the ticket; Error(ZKHIP_ERR_BUSY) when full
+    bool ready();                                                                  // would collect() return without waiting?  Never blocks
+    Proof collect(uint64_t* ticket = nullptr);
+    bool last_witness_packed() const { return last_packed_; }
+    void close();
+    explicit operator bool() const { return q_ != nullptr; }
+
+  private:
+    friend class Hip;
+    zkhip_queue* q_ = nullptr;
+    const Hip* hip_ = nullptr;
+    const Program* prog_ = nullptr;
+    Scheme scheme_ = Scheme::G16;
+    bool last_packed_ = false;
+    std::vector<std::vector<uint8_t>> inputs_;      // public_inputs_values of the tickets in flight, oldest first
+};
+
 // One GPU.  (The reference's backends are unit structs — `pub struct Ark;` — because they own nothing; this one owns a
 // zkhip_ctx, so it is an object.  Not re-entrant, like the context.)
 class Hip {
@@ -222,9 +258,12 @@ class Hip {
     // off by default.  Returns the previous setting; last_witness_packed() says which way the last prove() went.
     bool set_compact_witness(bool on) { const bool was = compact_; compact_ = on; return was; }
     bool last_witness_packed() const { return last_packed_; }
+    // a long-lived prover fed one witness at a time: a proof queue over a resident system and key (see Queue above)
+    Queue open_queue(Scheme scheme, const System& system, const Key& key);
     std::string describe() const;
 
   private:
+    friend class Queue;
     zkhip_ctx* ctx_ = nullptr;
     bool compact_ = false, last_packed_ = false;
     void check(int32_t rc) const;

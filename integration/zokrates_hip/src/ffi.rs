@@ -8,6 +8,9 @@ use std::os::raw::c_char;
 #[repr(C)] pub struct zkhip_multi { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_prog { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_assignment { _p: [u8; 0] }
+#[repr(C)] pub struct zkhip_queue { _p: [u8; 0] }
+/// zkhip_queue_submit*: as many proofs in flight as the queue holds; collect one first
+pub const ZKHIP_ERR_BUSY: i32 = -6;
 /// 16 floats: h2d, matvec, ntt, msm_h, msm_z, finish, total, accum_g1, accum_g2, kernel_ntt, 6 reserved (milliseconds)
 #[repr(C)] #[derive(Default, Clone, Copy)] pub struct zkhip_timings { pub ms: [f32; 16] }
 
@@ -70,6 +73,16 @@ extern "C" {
     pub fn zkhip_ctx_set_checked(ctx: *mut zkhip_ctx, on: i32) -> i32;
     pub fn zkhip_ctx_unsatisfied(ctx: *const zkhip_ctx, cap: u32, proof_idx: *mut u32, first_row: *mut u64, n_bad: *mut u64,
         count: *mut u32) -> i32;
+    // proof queue: up to ZKHIP_TUNE_SLOTS proofs of one (ctx, pk, r1cs) in flight ACROSS calls — a prover that receives its witnesses one
+    // at a time reaches the rate of the batch calls.  While a queue is open its context is pending, as between
+    // `split_begin` and `split_end`.  rnd = r | s (64 B, Groth16) or d1 | d2 | r (96 B, GM17); collect is first in, first out
+    pub fn zkhip_queue_open(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, r1cs: *const zkhip_r1cs, out: *mut *mut zkhip_queue) -> i32;
+    pub fn zkhip_queue_state(q: *const zkhip_queue, capacity: *mut u32, in_flight: *mut u32) -> i32;
+    pub fn zkhip_queue_submit(q: *mut zkhip_queue, z: *const u8, z_resident: *mut zkhip_assignment, rnd: *const u8, ticket: *mut u64) -> i32;
+    pub fn zkhip_queue_submit_packed(q: *mut zkhip_queue, packed: *const u8, len: usize, rnd: *const u8, ticket: *mut u64) -> i32;
+    pub fn zkhip_queue_ready(q: *mut zkhip_queue, ready: *mut i32) -> i32;
+    pub fn zkhip_queue_collect(q: *mut zkhip_queue, ticket: *mut u64, proof_out: *mut u8, timings: *mut zkhip_timings) -> i32;
+    pub fn zkhip_queue_close(q: *mut zkhip_queue) -> i32;
     /// a shard of a multi-GPU key (or a whole key, Groth16 or GM17) bound from the key FILE: the transforms need every base once
     pub fn zkhip_pk_bind_r1cs_shard(ctx: *mut zkhip_ctx, pk: *mut zkhip_pk, r1cs: *const zkhip_r1cs, key_bytes: *const u8, len: usize) -> i32;
     // ranks that are separate processes: the witness map of one proof split between two of them.  Between

@@ -158,6 +158,25 @@ struct ProofSlot {
     uint8_t r[32], s[32];
     std::chrono::steady_clock::time_point t_start;
 };
+// an assignment in the packed form of zkhip_assignment_pack, validated on the host (assignment_packed_validate): where its sections start
+struct PackedZ {
+    const uint8_t* bytes;
+    size_t len;
+    u64 tags_off, index_off, payload_off;
+};
+// zkhip_queue: the loop of Prover::run_batch — "enqueue i, finish i - (NS - 1)" — with the CALLER as the loop (zkhip_api.hip).  Ticket t
+// is in flight in slot t % cap, the slot run_batch gives proof t; head .. next - 1 are in flight, so a submit finds its slot free
+// because at most `cap` are.  While it is open its context is pending (`zkhip_ctx::queue`), as under a split proof.
+struct zkhip_queue {
+    zkhip_ctx* ctx = nullptr;
+    const zkhip_pk* pk = nullptr;
+    const zkhip_r1cs* cs = nullptr;
+    u32 cap = 0;              // ctx->nslots at open
+    u64 head = 0, next = 0;   // the oldest ticket in flight, the next ticket handed out
+    bool checked = false;     // the context's checked mode at open
+    bool broken = false;      // a device error: nothing is in flight any more, every remaining ticket collects with `dev_err`
+    std::string dev_err;
+};
 struct zkhip_ctx {
     int device = 0;
     Stream stream = 0;        // main stream: staging, sort, mat-vec, NTTs (high priority: short kernels the H MSM waits for)
@@ -209,8 +228,9 @@ struct zkhip_ctx {
     std::string desc;
     ProofSlot slots[ZK_NSLOTS];
     ProofSlot* cur = &slots[0];   // the slot the primitives (ntt, msm, ...) and the next enqueue work in
+    zkhip_queue* queue = nullptr; // the open proof queue of this context (zkhip_queue_open .. zkhip_queue_close): the context is pending
     DBuf tmp;
-    DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed); kept between calls
+    DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed, zkhip_queue_submit_packed); kept between calls
     std::vector<std::unique_ptr<NttPlanBase>> plans;
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
     // process would leave the second GPU of a process at the 64 KiB default)
@@ -1843,11 +1863,35 @@ struct Prover {
         dev_memset(flag.p, 0, 4, ctx->stream);
         ZK_LAUNCH((k_check_canonical<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, ctx->stream, ptr<Fr>(dst), m, ptr<u32>(flag));
     }
+    // the same from the packed form (validated on the host: zkhip_api.hip) into a buffer of `cap` entries: one copy of the packed bytes
+    // into the context's buffer, one launch that widens them and tests the 32-byte values against r, the same verdict word.
+    // ctx->zpack stays ONE buffer however many packed proofs are in flight: the copy in, the widening kernel and the next proof's copy in
+    // are all enqueued on ctx->stream, so the kernel has read the bytes of proof t before the copy of proof t + 1 overwrites them, and
+    // nothing else ever reads them (every later stage works from the slot's scalars).  Growing it frees the old buffer, which waits
+    // for the device: a larger packed buffer than any before costs that once.
+    static void unpack_z(zkhip_ctx* ctx, DBuf& dst, u64 m, u64 cap, const PackedZ& zp, DBuf& flag) {
+        Stream s = ctx->stream;
+        dst.ensure(cap * 32);
+        ctx->zpack.ensure(zp.len);
+        dev_h2d(ctx->zpack.p, zp.bytes, zp.len, s);
+        flag.ensure(4);
+        dev_memset(flag.p, 0, 4, s);
+        const uint8_t* d = ptr<uint8_t>(ctx->zpack);
+        ZK_LAUNCH((k_unpack_assignment<Fr>), dim3(blocks_for(m, ZPACK_BLOCK_ELEMS)), dim3(256), 0, s, d + zp.tags_off, (const u64*)(d + zp.index_off),
+                  d + zp.payload_off, ptr<Fr>(dst), m, ptr<u32>(flag));
+    }
     // the assignment into the slot, from host memory or from a resident one (checked when it was uploaded: a clean zflag word), and
     // the verdict of a checked proof reset behind it.  Returns where it is: a resident one stays where it was if the caller only
     // reads it (`in_place`; the provers append to theirs)
-    static const Fr* stage_z(zkhip_ctx* ctx, ProofSlot& sl, u64 m, u64 cap, const uint8_t* z_host, const void* z_dev, bool checked, bool in_place = false) {
+    // (`zp`: the assignment comes packed — zkhip_queue_submit_packed — and is widened into the slot; its verdict word is the slot's)
+    static const Fr* stage_z(zkhip_ctx* ctx, ProofSlot& sl, u64 m, u64 cap, const uint8_t* z_host, const void* z_dev, bool checked, bool in_place = false,
+                             const PackedZ* zp = nullptr) {
         Stream st = ctx->stream;
+        if (zp) {
+            unpack_z(ctx, sl.scalars, m, cap, *zp, sl.zflag);
+            if (checked) verdict_reset(sl, st);
+            return ptr<Fr>(sl.scalars);
+        }
         if (z_host) {
             upload_z(ctx, sl.scalars, m, cap, z_host, sl.zflag);
         } else {
@@ -1881,8 +1925,8 @@ struct Prover {
     // z_dev != nullptr: the assignment is already in HBM (copied device-to-device into the slot); else z is a host buffer
     // `lone`: nothing else of this context is in flight beside this proof (the single-proof entry points; a batch pipelines)
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
-                        const uint8_t* r, const uint8_t* s_, bool lone = false, int check_idx = -1) {
-        enqueue_head(ctx, sl, pk, cs, z_host, z_dev, r, s_, lone, -1, check_idx);
+                        const uint8_t* r, const uint8_t* s_, bool lone = false, int check_idx = -1, const PackedZ* zp = nullptr) {
+        enqueue_head(ctx, sl, pk, cs, z_host, z_dev, r, s_, lone, -1, check_idx, zp);
         enqueue_tail(ctx, sl, pk, cs);
     }
     // whether a proof over (pk, cs) may be split between members: a bound key (its proof needs a and b on the coset and nothing else
@@ -1907,7 +1951,7 @@ struct Prover {
     // (0: a, 1: b) of a bound key's, after which sl.half_ready is recorded and the caller brings the other vector into
     // sl.va + (1 - half) * N before enqueue_tail
     static void enqueue_head(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
-                             const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1) {
+                             const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1, const PackedZ* zp = nullptr) {
         PkLoader<C>::check_match(pk, cs, 0);
         const bool bound = is_bound(pk, cs);
         require(half < 0 || (bound && half <= 1), ZKHIP_ERR_BAD_ARG, "internal: only a proof over a bound key splits its witness map");
@@ -1920,7 +1964,7 @@ struct Prover {
         memcpy(sl.r, r, 32);
         memcpy(sl.s, s_, 32);
         Stream st = ctx->stream;
-        stage_z(ctx, sl, pk->m, pk->m + 2, z_host, z_dev, sl.check_idx >= 0);
+        stage_z(ctx, sl, pk->m, pk->m + 2, z_host, z_dev, sl.check_idx >= 0, false, zp);
         stage_scalars(ctx, pl, sl.scalars.p, pk->m, r, s_);
         event_record(sl.ev[0], st);
 
@@ -2430,14 +2474,7 @@ struct Prover {
                                          u64 payload_off) {
         Stream s = ctx->stream;
         DBuf flag;
-        a->scalars.ensure((a->m + 2) * 32);
-        ctx->zpack.ensure(len);
-        dev_h2d(ctx->zpack.p, packed, len, s);
-        flag.ensure(4);
-        dev_memset(flag.p, 0, 4, s);
-        const uint8_t* d = ptr<uint8_t>(ctx->zpack);
-        ZK_LAUNCH((k_unpack_assignment<Fr>), dim3(blocks_for(a->m, ZPACK_BLOCK_ELEMS)), dim3(256), 0, s, d + tags_off, (const u64*)(d + index_off),
-                  d + payload_off, ptr<Fr>(a->scalars), a->m, ptr<u32>(flag));
+        unpack_z(ctx, a->scalars, a->m, a->m + 2, PackedZ{packed, len, tags_off, index_off, payload_off}, flag);
         u32 verdict = 0;
         dev_d2h(&verdict, flag.p, 4, s);
         stream_sync(s);
@@ -2652,6 +2689,11 @@ struct CurveOps {
     u64 (*gm17_key_bytes)(u64, u64, u64);
     void (*gm17_prove_partial)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, uint8_t*, zkhip_timings*);
     void (*gm17_combine)(const zkhip_pk*, u32, const uint8_t*, const uint8_t*, uint8_t*);
+    // the proof queue (gm17.cuh QueueOps): either scheme, the key's
+    void (*queue_check)(const zkhip_pk*, const zkhip_r1cs*);
+    void (*queue_enqueue)(zkhip_ctx*, ProofSlot&, const zkhip_pk*, const zkhip_r1cs*, const uint8_t* z_host, const void* z_dev, const PackedZ*, const uint8_t* rnd,
+                          bool checked);
+    void (*queue_finish)(zkhip_ctx*, ProofSlot&, const zkhip_pk*, uint8_t*, zkhip_timings*);
 };
 // fields of zkhip_field_op: 0 Fr, 1 Fq, 2 Fq2 in the saturated form; 3 Fq2, 4 Fr, 5 Fq in the unsaturated limbs of the MSM kernels
 // and the transform passes (k_field_op_fq2, k_field_op_unsat)
@@ -2713,6 +2755,9 @@ static CurveOps make_curve_ops() {
     o.gm17_key_bytes = &Gm17<C>::key_bytes;
     o.gm17_prove_partial = &Gm17<C>::prove_partial;
     o.gm17_combine = &Gm17<C>::combine;
+    o.queue_check = &QueueOps<C>::check;
+    o.queue_enqueue = &QueueOps<C>::enqueue;
+    o.queue_finish = &QueueOps<C>::finish;
     return o;
 }
 const CurveOps* curve_ops_bn254();

@@ -439,6 +439,13 @@ inline Event event_create() {
 inline void event_destroy(Event e) { (void)hipEventDestroy(e); }
 inline void event_record(Event e, Stream s) { ZK_HIP_CHECK(hipEventRecord(e, s)); }
 inline void event_sync(Event e) { ZK_HIP_CHECK(hipEventSynchronize(e)); }
+// has everything recorded before `e` completed?  Never blocks (zkhip_queue_ready)
+inline bool event_done(Event e) {
+    const hipError_t rc = hipEventQuery(e);
+    if (rc == hipErrorNotReady) return false;
+    ZK_HIP_CHECK(rc);
+    return true;
+}
 inline void stream_wait_event(Stream s, Event e) { ZK_HIP_CHECK(hipStreamWaitEvent(s, e, 0)); }
 // Both events have been recorded; the caller has waited for the work it depends on, but an event on ANOTHER stream (the
 // main stream's "MSMs issued" marker, say) may still sit in a hardware queue behind a different context's kernels —
@@ -538,6 +545,7 @@ inline Event event_create() { return new double(0); }
 inline void event_destroy(Event e) { delete e; }
 inline void event_record(Event e, Stream) { *e = emu::now_ms(); }
 inline void event_sync(Event) {}
+inline bool event_done(Event) { return true; }      // (the emulator has run everything by the time a launch returns)
 inline void stream_wait_event(Stream, Event) {}
 inline float event_elapsed_ms(Event a, Event b) { return (float)(*b - *a); }
 inline void dev_check_last() {}

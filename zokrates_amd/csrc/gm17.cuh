@@ -117,7 +117,7 @@ struct Gm17 {
     // SAP rows and the extension of the assignment on the main stream (they feed the z sort), the quotient's transforms on the
     // context's NTT stream behind them
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
-                        const uint8_t* d1, const uint8_t* r, int check_idx = -1) {
+                        const uint8_t* d1, const uint8_t* r, int check_idx = -1, const PackedZ* zp = nullptr) {
         L::check_match(pk, cs, 1);
         const u64 m = cs->l + cs->w, n = cs->n, l = cs->l, M = pk->m, D = pk->N;
         Fr dd = fe_from_bytes_canon<Fr>(d1), rr = fe_from_bytes_canon<Fr>(r);
@@ -129,7 +129,7 @@ struct Gm17 {
         memcpy(sl.r, rho.v, 32);
         memset(sl.s, 0, 32);
         Stream st = ctx->stream;
-        P::stage_z(ctx, sl, m, M + 2, z_host, z_dev, check_idx >= 0);
+        P::stage_z(ctx, sl, m, M + 2, z_host, z_dev, check_idx >= 0, false, zp);
         uint8_t* d_scalars = (uint8_t*)sl.scalars.p;
         sl.zmont.ensure(m * 32);
         dev_h2d(d_scalars + M * 32, sl.r, 32, st);
@@ -371,6 +371,31 @@ struct Gm17 {
         p = S::put_len(p, D + 1);
         S::template mul_and_write<Fq, 2>(ctx, tbl1, ptr<Fr>(d_t), D + 1, p); p += (D + 1) * G1B;        // g_gamma2_z_t
         require((u64)(p - out) == need, ZKHIP_ERR_DEVICE, "internal: key size mismatch");
+    }
+};
+
+// ---- the proof queue's share of the two provers (zkhip_queue_*: zkhip_api.hip holds the tickets): ONE proof enqueued exactly as the
+// batch calls enqueue theirs (Groth16: lone = false; a checked proof has index 0, it is the only one of its collect), ONE slot
+// finished; the scheme is the key's.  rnd = r | s (Groth16) or d1 | d2 | r (GM17).  Everything `enqueue` refuses with ZKHIP_ERR_BAD_ARG
+// — a key of another system, a non-canonical blinding scalar, z[0] != 1 — it refuses before its first copy or launch.
+template <class C>
+struct QueueOps {
+    typedef Prover<C> P;
+    typedef Gm17<C> G;
+    static void check(const zkhip_pk* pk, const zkhip_r1cs* cs) { PkLoader<C>::check_match(pk, cs, pk->scheme); }
+    static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const PackedZ* zp,
+                        const uint8_t* rnd, bool checked) {
+        const int idx = checked ? 0 : -1;
+        if (pk->scheme == 0) {
+            P::enqueue(ctx, sl, pk, cs, z_host, z_dev, rnd, rnd + 32, false, idx, zp);
+        } else {
+            G::check_d2(rnd);
+            G::enqueue(ctx, sl, pk, cs, z_host, z_dev, rnd, rnd + 64, idx, zp);
+        }
+    }
+    static void finish(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, uint8_t* out, zkhip_timings* tm) {
+        if (pk->scheme == 0) P::finish(ctx, sl, pk, out, tm);
+        else G::finish(ctx, sl, pk, out, tm);
     }
 };
 

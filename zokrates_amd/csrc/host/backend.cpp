@@ -326,63 +326,47 @@ Proof Hip::prove(Scheme scheme, const Program& program, const uint8_t* witness, 
     return p;
 }
 
-Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, size_t witness_len, const Key& key, StdRng& rng, Timings* tm) {
-    const Program& program = system.program();
-    const int32_t curve = program.curve();
-    const size_t fq = curve == ZKHIP_CURVE_BN128 ? 32 : 48;
-    // (1) the assignment in ark order and the public inputs as the ark backend computes them (groth16.rs:33-38)
-    auto t0 = std::chrono::steady_clock::now();
-    const uint64_t m = program.variables();
-    std::vector<uint8_t> z, packed;
-    const uint64_t cap = witness_len / 40 + 2;
-    std::vector<uint8_t> inputs(cap * 32);
+namespace {
+// (1) of a proof: the assignment in ark order and the public inputs as the ark backend computes them (groth16.rs:33-38).  `compact`:
+// the witness straight into the packed form; packed when that is less than half of the plain bytes, else widened on the host
+struct WitnessBytes {
+    std::vector<uint8_t> z, packed, inputs;
     uint64_t n_inputs = 0, packed_len = 0;
+    bool use_packed = false;
+};
+WitnessBytes read_witness(const Program& program, const uint8_t* witness, size_t witness_len, bool compact) {
+    WitnessBytes w;
+    const uint64_t m = program.variables();
+    const uint64_t cap = witness_len / 40 + 2;
+    w.inputs.resize(cap * 32);
     int32_t rc;
-    last_packed_ = false;
-    if (compact_) {
-        // the witness straight into the packed form; packed when that is less than half of the plain bytes, else widened on the host
+    if (compact) {
         uint64_t bound = 0;
         zkhip_assignment_pack_bound(m, &bound);
-        packed.resize(bound);
-        rc = zkhip_prog_assignment_packed(program.get(), witness, witness_len, packed.data(), bound, &packed_len, inputs.data(), cap, &n_inputs);
+        w.packed.resize(bound);
+        rc = zkhip_prog_assignment_packed(program.get(), witness, witness_len, w.packed.data(), bound, &w.packed_len, w.inputs.data(), cap, &w.n_inputs);
         if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
-        last_packed_ = 2 * packed_len < 32 * m;
-        if (!last_packed_) {
-            z.resize(m * 32);
+        w.use_packed = 2 * w.packed_len < 32 * m;
+        if (!w.use_packed) {
+            w.z.resize(m * 32);
             uint64_t got = 0;
-            rc = zkhip_assignment_unpack(packed.data(), packed_len, z.data(), m, &got);
+            rc = zkhip_assignment_unpack(w.packed.data(), w.packed_len, w.z.data(), m, &got);
             if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
         }
     } else {
-        z.resize(m * 32);
-        rc = zkhip_prog_assignment(program.get(), witness, witness_len, z.data(), inputs.data(), cap, &n_inputs);
+        w.z.resize(m * 32);
+        rc = zkhip_prog_assignment(program.get(), witness, witness_len, w.z.data(), w.inputs.data(), cap, &w.n_inputs);
         if (rc != ZKHIP_OK) throw Error(rc, zkhip_last_error(nullptr));
     }
-    if (tm) tm->witness_to_assignment = ms_since(t0);
-    // (2) the constraint system: resident
-    zkhip_r1cs* cs = system.get();
-    if (tm) tm->r1cs_upload = 0;
-    // (3) the blinding scalars: the first draws ark makes from the caller's RNG; (4) the GPU
-    t0 = std::chrono::steady_clock::now();
-    std::vector<uint8_t> raw(8 * fq + 3);
-    struct Resident {      // the packed witness widened on the device (zkhip_assignment_upload_packed)
-        zkhip_assignment* a = nullptr;
-        ~Resident() { if (a) zkhip_assignment_free(a); }
-    } resident;
-    if (last_packed_) check(zkhip_assignment_upload_packed(ctx_, cs, packed.data(), packed_len, &resident.a));
-    if (scheme == Scheme::GM17) {
-        uint8_t rnd[96];
-        for (int i = 0; i < 3; ++i) memcpy(rnd + 32 * i, fr_rand(rng, curve).data(), 32);      // d1, d2, r
-        rc = last_packed_ ? zkhip_prove_gm17_resident(ctx_, key.get(), cs, resident.a, rnd, raw.data(), nullptr)
-                          : zkhip_prove_gm17(ctx_, key.get(), cs, z.data(), rnd, raw.data(), nullptr);
-    } else {
-        const std::array<uint8_t, 32> r = fr_rand(rng, curve), s = fr_rand(rng, curve);
-        rc = last_packed_ ? zkhip_prove_g16_resident(ctx_, key.get(), cs, resident.a, r.data(), s.data(), raw.data(), nullptr)
-                          : zkhip_prove_g16(ctx_, key.get(), cs, z.data(), r.data(), s.data(), raw.data(), nullptr);
-    }
-    check(rc);
-    if (tm) tm->prove = ms_since(t0);
-    // (5) raw little-endian coordinates -> big-endian hex; a point at infinity is printed as ark's zero() = (0, 1)
+    return w;
+}
+// (3) the blinding scalars: the first draws ark makes from the caller's RNG — d1, d2, r (GM17) or r, s (Groth16)
+void draw_rnd(Scheme scheme, int32_t curve, StdRng& rng, uint8_t rnd[96]) {
+    for (int i = 0; i < (scheme == Scheme::GM17 ? 3 : 2); ++i) memcpy(rnd + 32 * i, fr_rand(rng, curve).data(), 32);
+}
+// (5) raw little-endian coordinates -> big-endian hex; a point at infinity is printed as ark's zero() = (0, 1)
+Proof proof_from_raw(Scheme scheme, int32_t curve, std::vector<uint8_t>& raw, const uint8_t* inputs, uint64_t n_inputs) {
+    const size_t fq = curve == ZKHIP_CURVE_BN128 ? 32 : 48;
     std::vector<uint8_t> one(fq, 0);
     one[0] = 1;
     if (raw[8 * fq]) memcpy(&raw[fq], one.data(), fq);
@@ -397,6 +381,116 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     p.proof.c = {hex_be(&raw[6 * fq], fq), hex_be(&raw[7 * fq], fq)};
     for (uint64_t i = 0; i < n_inputs; ++i) p.inputs.push_back(hex_be(&inputs[32 * i], 32));
     return p;
+}
+}  // namespace
+
+Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, size_t witness_len, const Key& key, StdRng& rng, Timings* tm) {
+    const Program& program = system.program();
+    const int32_t curve = program.curve();
+    const size_t fq = curve == ZKHIP_CURVE_BN128 ? 32 : 48;
+    // (1) the assignment and the public inputs
+    auto t0 = std::chrono::steady_clock::now();
+    last_packed_ = false;
+    WitnessBytes w = read_witness(program, witness, witness_len, compact_);
+    last_packed_ = w.use_packed;
+    if (tm) tm->witness_to_assignment = ms_since(t0);
+    // (2) the constraint system: resident
+    zkhip_r1cs* cs = system.get();
+    if (tm) tm->r1cs_upload = 0;
+    // (3) the blinding scalars; (4) the GPU
+    t0 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> raw(8 * fq + 3);
+    struct Resident {      // the packed witness widened on the device (zkhip_assignment_upload_packed)
+        zkhip_assignment* a = nullptr;
+        ~Resident() { if (a) zkhip_assignment_free(a); }
+    } resident;
+    if (last_packed_) check(zkhip_assignment_upload_packed(ctx_, cs, w.packed.data(), w.packed_len, &resident.a));
+    uint8_t rnd[96];
+    draw_rnd(scheme, curve, rng, rnd);
+    int32_t rc;
+    if (scheme == Scheme::GM17) {
+        rc = last_packed_ ? zkhip_prove_gm17_resident(ctx_, key.get(), cs, resident.a, rnd, raw.data(), nullptr)
+                          : zkhip_prove_gm17(ctx_, key.get(), cs, w.z.data(), rnd, raw.data(), nullptr);
+    } else {
+        rc = last_packed_ ? zkhip_prove_g16_resident(ctx_, key.get(), cs, resident.a, rnd, rnd + 32, raw.data(), nullptr)
+                          : zkhip_prove_g16(ctx_, key.get(), cs, w.z.data(), rnd, rnd + 32, raw.data(), nullptr);
+    }
+    check(rc);
+    if (tm) tm->prove = ms_since(t0);
+    return proof_from_raw(scheme, curve, raw, w.inputs.data(), w.n_inputs);
+}
+
+// ------------------------------------------------------------------ the proof queue (zkhip.h "proof queue")
+Queue Hip::open_queue(Scheme scheme, const System& system, const Key& key) {
+    Queue q;
+    check(zkhip_queue_open(ctx_, key.get(), system.get(), &q.q_));
+    q.hip_ = this;
+    q.prog_ = &system.program();
+    q.scheme_ = scheme;
+    return q;
+}
+Queue::~Queue() { close(); }
+Queue::Queue(Queue&& o) noexcept : q_(o.q_), hip_(o.hip_), prog_(o.prog_), scheme_(o.scheme_), last_packed_(o.last_packed_), inputs_(std::move(o.inputs_)) { o.q_ = nullptr; }
+Queue& Queue::operator=(Queue&& o) noexcept {
+    if (this != &o) {
+        close();
+        q_ = o.q_; hip_ = o.hip_; prog_ = o.prog_; scheme_ = o.scheme_; last_packed_ = o.last_packed_;
+        inputs_ = std::move(o.inputs_);
+        o.q_ = nullptr;
+    }
+    return *this;
+}
+void Queue::close() {
+    if (q_) zkhip_queue_close(q_);
+    q_ = nullptr;
+    inputs_.clear();
+}
+uint32_t Queue::capacity() const {
+    uint32_t cap = 0;
+    if (q_) zkhip_queue_state(q_, &cap, nullptr);
+    return cap;
+}
+uint32_t Queue::in_flight() const {
+    uint32_t n = 0;
+    if (q_) zkhip_queue_state(q_, nullptr, &n);
+    return n;
+}
+uint64_t Queue::submit(const uint8_t* witness, size_t witness_len, StdRng& rng) {
+    if (!q_) throw Error(ZKHIP_ERR_BAD_ARG, "the queue is closed");
+    if (full()) throw Error(ZKHIP_ERR_BUSY, "the proof queue is full: collect a proof first");      // (before the RNG is touched)
+    const int32_t curve = prog_->curve();
+    WitnessBytes w = read_witness(*prog_, witness, witness_len, hip_->compact_);
+    uint8_t rnd[96];
+    draw_rnd(scheme_, curve, rng, rnd);
+    uint64_t ticket = 0;
+    // the buffers are the library's copies when the call returns: `w` may go
+    hip_->check(w.use_packed ? zkhip_queue_submit_packed(q_, w.packed.data(), w.packed_len, rnd, &ticket) : zkhip_queue_submit(q_, w.z.data(), nullptr, rnd, &ticket));
+    last_packed_ = w.use_packed;
+    w.inputs.resize(w.n_inputs * 32);
+    inputs_.push_back(std::move(w.inputs));
+    return ticket;
+}
+bool Queue::ready() {
+    int32_t r = 0;
+    if (!q_) return false;
+    hip_->check(zkhip_queue_ready(q_, &r));
+    return r != 0;
+}
+Proof Queue::collect(uint64_t* ticket) {
+    if (!q_) throw Error(ZKHIP_ERR_BAD_ARG, "the queue is closed");
+    const int32_t curve = prog_->curve();
+    std::vector<uint8_t> raw(8 * (curve == ZKHIP_CURVE_BN128 ? 32 : 48) + 3);
+    uint64_t t = 0;
+    const bool had = in_flight() > 0;
+    const int32_t rc = zkhip_queue_collect(q_, &t, raw.data(), nullptr);
+    std::vector<uint8_t> inputs;
+    if (had && !inputs_.empty()) {      // (its ticket is spent whether the proof came out or not)
+        inputs = std::move(inputs_.front());
+        inputs_.erase(inputs_.begin());
+    }
+    hip_->check(rc);
+    if (ticket) *ticket = t;
+    return proof_from_raw(scheme_, curve, raw, inputs.data(), inputs.size() / 32);
 }
 
 // ------------------------------------------------------------------ setup

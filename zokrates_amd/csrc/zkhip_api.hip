@@ -19,6 +19,9 @@ static thread_local std::string g_create_err;
 
 // after a failed call: let whatever was enqueued drain and mark the proof slots free, so the context stays usable
 static void release_slots(zkhip_ctx* ctx) {
+    // (under an open proof queue the busy slots are ITS proofs in flight, and the only calls that come this far are the ones the
+    // pending rule lets through: they enqueue nothing, so there is nothing of theirs to drain)
+    if (ctx->queue) return;
     bool any = false;
     for (auto& sl : ctx->slots) any = any || sl.busy;
     if (!any) return;
@@ -33,10 +36,16 @@ static const char* const SPLIT_PENDING_MSG =
     "a split proof is pending in this context (zkhip_prove_g16_split_begin): finish it with zkhip_prove_g16_split_end or drop it with "
     "zkhip_prove_g16_split_abort first";
 static bool split_pending(const zkhip_ctx* ctx) { return ctx->slots[0].split_pending; }
+// An open proof queue (zkhip_queue_open .. zkhip_queue_close) makes its context pending in the same sense, for the same reason — up to
+// ctx->nslots proofs are in flight in the slots between two calls — and the same gate refuses the same calls.  The two states exclude
+// each other: each one's opening call is among the calls the other refuses.
+static const char* const QUEUE_OPEN_MSG =
+    "a proof queue is open in this context (zkhip_queue_open): its proofs in flight own the context's buffers and streams; collect them "
+    "and close it with zkhip_queue_close first";
 // an abandoned or failed split proof: what is enqueued drains, the slot is free again
 static void split_drop(zkhip_ctx* ctx) {
     ProofSlot& sl = ctx->slots[0];
-    if (!sl.split_pending && !sl.busy) return;
+    if (!sl.split_pending && (!sl.busy || ctx->queue)) return;      // (nothing pending; a busy slot 0 under a queue is the queue's)
     try { dev_set(ctx->device); dev_sync_all(); } catch (...) {}
     sl.busy = false;
     sl.split_pending = false;
@@ -48,6 +57,10 @@ template <class Fn>
 static int32_t guarded(zkhip_ctx* ctx, Fn&& fn, bool while_pending = false) {
     if (ctx && !while_pending && split_pending(ctx)) {
         ctx->err = SPLIT_PENDING_MSG;
+        return ZKHIP_ERR_BAD_ARG;
+    }
+    if (ctx && !while_pending && ctx->queue) {
+        ctx->err = QUEUE_OPEN_MSG;
         return ZKHIP_ERR_BAD_ARG;
     }
     try {
@@ -134,6 +147,87 @@ static int32_t bind_key(zkhip_ctx* ctx, zkhip_pk* pk, const zkhip_r1cs* r1cs, bo
     });
     if (rc != ZKHIP_OK && pk && started) zkhip_pk_unbind(pk);   // whatever failed half-way: the key is as it was loaded
     return rc;
+}
+
+// ---- the proof queue (zkhip_queue_*): the tickets, and the guard of its entry points.
+// The hazard is guarded(): on ANY exception it runs release_slots, which waits for the device and frees every slot — right for a call
+// that owns everything in flight, wrong here, where the other slots hold other tickets.  So the queue's calls have a guard of their own
+// that tells two kinds of failure apart:
+//   * one call's or one proof's — a submit refused for its arguments (thrown before its first copy or launch: QueueOps, and the checks
+//     in queue_submit), a collected proof whose assignment was not canonical or not satisfying (thrown by `finish` AFTER it has waited
+//     for its own slot and marked it free): the code and the message go to the caller, every other slot stays as it is;
+//   * the device's (DevError, and anything that is neither ZKHIP_ERR_BAD_ARG, _PARSE nor _UNSATISFIED: it may have left half a proof
+//     enqueued): the queue is broken.  The error is kept, the device drained, the slots freed; every ticket still counted as in flight
+//     collects with ZKHIP_ERR_DEVICE and that text, submit answers the same, zkhip_queue_close works.
+static void queue_break(zkhip_queue* q, const std::string& msg) {
+    q->broken = true;
+    q->dev_err = msg;
+    dev_sync_all();
+    for (auto& sl : q->ctx->slots) sl.busy = false;
+}
+template <class Fn>
+static int32_t queue_guarded(zkhip_queue* q, Fn&& fn) {
+    zkhip_ctx* ctx = q->ctx;
+    auto broke = [&](const std::string& msg, int32_t code) {
+        ctx->err = msg;
+        queue_break(q, msg);
+        return code;
+    };
+    try {
+        dev_set(ctx->device);
+        fn();
+        return ZKHIP_OK;
+    } catch (const ApiError& e) {
+        if (e.code != ZKHIP_ERR_BAD_ARG && e.code != ZKHIP_ERR_PARSE && e.code != ZKHIP_ERR_UNSATISFIED) return broke(e.msg, e.code);
+        ctx->err = e.msg;
+        return e.code;
+    } catch (const DevError& e) {
+        return broke(e.msg, ZKHIP_ERR_DEVICE);
+    } catch (const std::bad_alloc&) {
+        return broke("out of host memory", ZKHIP_ERR_NOMEM);
+    } catch (...) {
+        return broke("unexpected internal error", ZKHIP_ERR_DEVICE);
+    }
+}
+// what the three witness sources share: the state first (broken, full), then the source's own checks — all on the host —, then the
+// proof enqueued into the slot of the next ticket exactly as a batch call enqueues its proof of that index
+static int32_t queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* z_resident, const uint8_t* packed, size_t len, bool is_packed, const uint8_t* rnd,
+                            uint64_t* ticket) {
+    if (!q || !q->ctx) return ZKHIP_ERR_BAD_ARG;
+    zkhip_ctx* ctx = q->ctx;
+    if (q->broken) { ctx->err = q->dev_err; return ZKHIP_ERR_DEVICE; }
+    if (q->next - q->head >= q->cap) {
+        ctx->err = "the proof queue holds " + std::to_string(q->cap) + " proofs in flight and all are: collect one first (zkhip_queue_collect)";
+        return ZKHIP_ERR_BUSY;
+    }
+    return queue_guarded(q, [&] {
+        const zkhip_r1cs* cs = q->cs;
+        require(rnd != nullptr, ZKHIP_ERR_BAD_ARG, "null argument");
+        PackedZ zp{};
+        if (is_packed) {
+            require(packed != nullptr, ZKHIP_ERR_BAD_ARG, "null argument");
+            // the whole structure on the host, before anything is enqueued (as zkhip_assignment_upload_packed): the kernel never sees an inconsistent buffer
+            PackedLayout ly;
+            try {
+                ly = assignment_packed_validate(packed, len);
+            } catch (const IngestError& e) {
+                throw ApiError{e.code, e.msg};
+            }
+            const std::string dims = "the packed assignment has " + std::to_string(ly.m) + " elements, the constraint system " + std::to_string(cs->l + cs->w) + " variables (l + w)";
+            require(ly.m == cs->l + cs->w, ZKHIP_ERR_BAD_ARG, dims.c_str());
+            require(packed_first_is_one(packed, ly), ZKHIP_ERR_BAD_ARG, Z0_NOT_ONE_MSG);
+            zp = PackedZ{packed, len, ly.tags_off, ly.index_off, ly.payload_off};
+        } else {
+            require((z != nullptr) != (z_resident != nullptr), ZKHIP_ERR_BAD_ARG, "exactly one of z and z_resident");
+            if (z_resident)
+                require(z_resident->ctx == ctx && z_resident->curve == cs->curve && z_resident->m == cs->l + cs->w, ZKHIP_ERR_BAD_ARG,
+                        "assignment does not match the constraint system");
+        }
+        ops_for(q->pk->curve)->queue_enqueue(ctx, ctx->slots[q->next % q->cap], q->pk, cs, z, z_resident ? z_resident->scalars.p : nullptr, is_packed ? &zp : nullptr,
+                                             rnd, q->checked);
+        if (ticket) *ticket = q->next;
+        ++q->next;
+    });
 }
 
 extern "C" {
@@ -238,6 +332,7 @@ void zkhip_ctx_free(zkhip_ctx* ctx) {
     } catch (...) {
     }
     dev_sync_all();
+    if (ctx->queue) ctx->queue->ctx = nullptr;      // (a queue left open: its zkhip_queue_close only frees the handle)
     staging_drain();          // (the device's staging ring may still track transfers recorded on this context's streams)
     for (auto& sl : ctx->slots) {
         // (streams first, whether or not the slot was ever used: a stream plan makes the streams of every slot at the first proof)
@@ -619,6 +714,10 @@ int32_t zkhip_ctx_set_checked(zkhip_ctx* ctx, int32_t on) {
         ctx->err = SPLIT_PENDING_MSG;
         return ZKHIP_ERR_BAD_ARG;
     }
+    if (on >= 0 && ctx->queue) {      // (an open queue read the mode when it was opened)
+        ctx->err = QUEUE_OPEN_MSG;
+        return ZKHIP_ERR_BAD_ARG;
+    }
     if (on >= 0) ctx->checked = on != 0;
     return was;
 }
@@ -630,6 +729,79 @@ int32_t zkhip_ctx_unsatisfied(const zkhip_ctx* ctx, uint32_t cap, uint32_t* proo
         if (n_bad) n_bad[k] = ctx->unsat[k].n_bad;
     }
     if (count) *count = (uint32_t)ctx->unsat.size();
+    return ZKHIP_OK;
+}
+
+// ---- the proof queue: ctx->nslots proofs in flight ACROSS calls (the helpers above hold the rules)
+int32_t zkhip_queue_open(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_queue** out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {      // (the gate: refused while a split proof is pending or another queue is open)
+        require(pk && r1cs && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        require(pk->ctx == ctx && r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "key / constraint system belong to another context");
+        require(pk->world == 1, ZKHIP_ERR_BAD_ARG, "this proving key is one shard of a multi-GPU key: a proof queue takes a whole key");
+        for (auto& sl : ctx->slots) require(!sl.busy, ZKHIP_ERR_BAD_ARG, "a proof is in flight in this context");
+        ops_for(pk->curve)->queue_check(pk, r1cs);
+        std::unique_ptr<zkhip_queue> q(new zkhip_queue());
+        q->ctx = ctx;
+        q->pk = pk;
+        q->cs = r1cs;
+        q->cap = (u32)std::max(1, std::min(ctx->nslots, ZK_NSLOTS));
+        q->checked = ctx->checked;
+        ctx->queue = q.get();
+        *out = q.release();
+    });
+}
+int32_t zkhip_queue_state(const zkhip_queue* q, uint32_t* capacity, uint32_t* in_flight) {
+    if (!q) return ZKHIP_ERR_BAD_ARG;
+    if (capacity) *capacity = q->cap;
+    if (in_flight) *in_flight = (uint32_t)(q->next - q->head);
+    return ZKHIP_OK;
+}
+int32_t zkhip_queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* z_resident, const uint8_t* rnd, uint64_t* ticket) {
+    return queue_submit(q, z, z_resident, nullptr, 0, false, rnd, ticket);
+}
+int32_t zkhip_queue_submit_packed(zkhip_queue* q, const uint8_t* packed, size_t len, const uint8_t* rnd, uint64_t* ticket) {
+    return queue_submit(q, nullptr, nullptr, packed, len, true, rnd, ticket);
+}
+int32_t zkhip_queue_ready(zkhip_queue* q, int32_t* ready) {
+    if (!q || !q->ctx || !ready) return ZKHIP_ERR_BAD_ARG;
+    *ready = 0;
+    if (q->head == q->next) return ZKHIP_OK;                    // nothing to collect
+    if (q->broken) { *ready = 1; return ZKHIP_OK; }             // (collect answers at once)
+    return queue_guarded(q, [&] { *ready = event_done(q->ctx->slots[q->head % q->cap].ev[3]) ? 1 : 0; });
+}
+int32_t zkhip_queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, zkhip_timings* timings) {
+    if (!q || !q->ctx) return ZKHIP_ERR_BAD_ARG;
+    zkhip_ctx* ctx = q->ctx;
+    if (!proof_out) { ctx->err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
+    if (q->head == q->next) { ctx->err = "the proof queue is empty: nothing to collect"; return ZKHIP_ERR_BAD_ARG; }
+    const u64 t = q->head++;      // whatever happens to this proof, its ticket is spent
+    if (ticket) *ticket = t;
+    if (q->broken) { ctx->err = q->dev_err; return ZKHIP_ERR_DEVICE; }
+    return queue_guarded(q, [&] {
+        ctx->unsat.clear();
+        ops_for(q->pk->curve)->queue_finish(ctx, ctx->slots[t % q->cap], q->pk, proof_out, timings);
+        if (!ctx->unsat.empty()) {      // (checked mode: `finish` has zero-filled the slot and noted the one triple, proof index 0)
+            const auto& u = ctx->unsat.front();
+            char msg[200];
+            snprintf(msg, sizeof(msg), "ticket %llu: constraint %llu of %llu is not satisfied (%llu in all)", (unsigned long long)t,
+                     (unsigned long long)u.first_row, (unsigned long long)q->cs->n, (unsigned long long)u.n_bad);
+            throw ApiError{ZKHIP_ERR_UNSATISFIED, msg};
+        }
+    });
+}
+int32_t zkhip_queue_close(zkhip_queue* q) {
+    if (!q) return ZKHIP_ERR_BAD_ARG;
+    if (zkhip_ctx* ctx = q->ctx) {
+        if (q->head != q->next && !q->broken) {      // what is uncollected drains and is dropped
+            try { dev_set(ctx->device); } catch (...) {}
+            dev_sync_all();
+            for (auto& sl : ctx->slots) sl.busy = false;
+        }
+        ctx->queue = nullptr;
+    }
+    delete q;
     return ZKHIP_OK;
 }
 

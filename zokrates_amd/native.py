@@ -16,7 +16,7 @@ DEFAULT_LIB = os.environ.get("ZKHIP_LIBRARY") or os.path.join(HERE, "libzkhip.so
 CURVE_IDS = {"bn128": 0, "bls12_381": 1, "bls12_377": 2}
 FQ_BYTES = {0: 32, 1: 48, 2: 48}
 
-ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "PARSE", -3: "NOMEM", -4: "DEVICE", -5: "UNSATISFIED"}
+ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "PARSE", -3: "NOMEM", -4: "DEVICE", -5: "UNSATISFIED", -6: "BUSY"}
 
 
 class ZkhipError(RuntimeError):
@@ -74,6 +74,8 @@ class Library:
         "zkhip_r1cs_check", "zkhip_ctx_set_checked", "zkhip_ctx_unsatisfied",
         "zkhip_assignment_pack_bound", "zkhip_assignment_pack", "zkhip_assignment_unpack", "zkhip_prog_assignment_packed",
         "zkhip_assignment_upload_packed",
+        "zkhip_queue_open", "zkhip_queue_state", "zkhip_queue_submit", "zkhip_queue_submit_packed", "zkhip_queue_ready", "zkhip_queue_collect",
+        "zkhip_queue_close",
     ]
 
     def __init__(self, path=None):
@@ -170,6 +172,13 @@ class Library:
         L.zkhip_assignment_unpack.restype = i32; L.zkhip_assignment_unpack.argtypes = [vp, sz, vp, u64, vp]
         L.zkhip_prog_assignment_packed.restype = i32; L.zkhip_prog_assignment_packed.argtypes = [vp, vp, sz, vp, u64, vp, vp, u64, vp]
         L.zkhip_assignment_upload_packed.restype = i32; L.zkhip_assignment_upload_packed.argtypes = [vp, vp, vp, sz, pp]
+        L.zkhip_queue_open.restype = i32; L.zkhip_queue_open.argtypes = [vp, vp, vp, pp]
+        L.zkhip_queue_state.restype = i32; L.zkhip_queue_state.argtypes = [vp, vp, vp]
+        L.zkhip_queue_submit.restype = i32; L.zkhip_queue_submit.argtypes = [vp, vp, vp, vp, vp]
+        L.zkhip_queue_submit_packed.restype = i32; L.zkhip_queue_submit_packed.argtypes = [vp, vp, sz, vp, vp]
+        L.zkhip_queue_ready.restype = i32; L.zkhip_queue_ready.argtypes = [vp, vp]
+        L.zkhip_queue_collect.restype = i32; L.zkhip_queue_collect.argtypes = [vp, vp, vp, vp]
+        L.zkhip_queue_close.restype = i32; L.zkhip_queue_close.argtypes = [vp]
         self.L = L
 
     def init(self, hw_queues):
@@ -697,6 +706,95 @@ def prove_gm17_resident_batch(ctx, pk, cs, assignments, rnds):
     tm = Timings()
     ctx._check(ctx.lib.L.zkhip_prove_gm17_resident_batch(ctx.h, pk.h, cs.h, count, handles, _ptr(rb), _ptr(out), C.byref(tm)), lambda: _split_proofs(out, count, 8 * nb + 3))
     return _split_proofs(out, count, 8 * nb + 3), tm.as_dict()
+
+
+# ---- the proof queue: proofs in flight across calls ----
+BUSY = -6
+
+
+class ProofQueue:
+    """`zkhip_queue`: up to `capacity` proofs of one (context, key, constraint system) in flight ACROSS calls — the pipeline of the
+    batch calls with the caller as the loop.  `submit` / `submit_packed` return the ticket, `collect` the oldest proof (FIFO); a
+    submit at capacity raises ZkhipError with code BUSY (-6).  While it is open its context refuses every other proving call
+    (include/zkhip.h, Conventions); use it as a context manager or `close` it."""
+
+    def __init__(self, ctx, pk, cs):
+        self.ctx, self.pk, self.cs = ctx, pk, cs
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.L.zkhip_queue_open(ctx.h, pk.h, cs.h, C.byref(self.h)))
+        self.proof_bytes = 8 * FQ_BYTES[pk.curve_id] + 3
+        self.rnd_bytes = 96 if pk.scheme == "gm17" else 64
+
+    def _rnd(self, rnd):
+        """(r, s) / (d1, d2, r) as ints, or the 64 / 96 bytes themselves (a numpy array is passed as it is, not copied)"""
+        if isinstance(rnd, (tuple, list)):
+            rnd = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in rnd), dtype=np.uint8)
+        return _u8(rnd, self.rnd_bytes)
+
+    def state(self):
+        """`zkhip_queue_state`: (capacity, proofs in flight)"""
+        cap, n = C.c_uint32(), C.c_uint32()
+        self.ctx._check(self.ctx.lib.L.zkhip_queue_state(self.h, C.byref(cap), C.byref(n)))
+        return int(cap.value), int(n.value)
+
+    def submit(self, z, rnd):
+        """`zkhip_queue_submit`: z is a host assignment (uint8[m*32]) or a resident `Assignment`, which must stay alive until its
+        ticket is collected; the host buffers are the caller's again when this returns.  Returns the ticket."""
+        rb = self._rnd(rnd)
+        ticket = C.c_uint64()
+        if isinstance(z, Assignment):
+            zp, za = None, z.h
+        else:
+            z = _u8(z, self.cs.m * 32)
+            zp, za = _ptr(z), None
+        self.ctx._check(self.ctx.lib.L.zkhip_queue_submit(self.h, zp, za, _ptr(rb), C.byref(ticket)))
+        return int(ticket.value)
+
+    def submit_packed(self, packed, rnd):
+        """`zkhip_queue_submit_packed`: the assignment in the packed form (`pack_assignment`), widened on the device."""
+        rb = self._rnd(rnd)
+        packed = _u8(packed)
+        ticket = C.c_uint64()
+        self.ctx._check(self.ctx.lib.L.zkhip_queue_submit_packed(self.h, _ptr(packed), packed.size, _ptr(rb), C.byref(ticket)))
+        return int(ticket.value)
+
+    def ready(self):
+        """`zkhip_queue_ready`: would `collect` return without waiting for the device?  Never blocks; False on an empty queue."""
+        out = C.c_int32()
+        self.ctx._check(self.ctx.lib.L.zkhip_queue_ready(self.h, C.byref(out)))
+        return bool(out.value)
+
+    def collect(self, want_timings=False):
+        """`zkhip_queue_collect`: (ticket, proof bytes) of the oldest proof in flight; blocks until it is done.  A proof that failed
+        raises ZkhipError — its `ticket` attribute says which — and the others stay in flight."""
+        out = np.zeros(self.proof_bytes, dtype=np.uint8)
+        ticket = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        tm = Timings()
+        try:
+            self.ctx._check(self.ctx.lib.L.zkhip_queue_collect(self.h, C.byref(ticket), _ptr(out), C.byref(tm)), lambda: [out.tobytes()])
+        except ZkhipError as e:
+            e.ticket = None if ticket.value == 0xFFFFFFFFFFFFFFFF else int(ticket.value)
+            raise
+        return (int(ticket.value), out.tobytes(), tm.as_dict()) if want_timings else (int(ticket.value), out.tobytes())
+
+    def close(self):
+        """`zkhip_queue_close`: waits for what is in flight, drops it, and gives the context back."""
+        if self.h:
+            self.ctx.lib.L.zkhip_queue_close(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---- ZoKrates' own files (N1): host only ----
