@@ -502,6 +502,27 @@ int32_t zkhip_multi_unbind(zkhip_multi* m);
  * whether the last zkhip_prove_*_multi did split. */
 int32_t zkhip_multi_transform_split(zkhip_multi* m, int32_t on);
 int32_t zkhip_multi_last_split(const zkhip_multi* m);
+/* ---- the transform DOMAIN sharded across the members (csrc/ntt_shard.h) ----
+ * A plan's domain N = N1 x Nb is an N1 x Nb matrix.  Member k of G runs the outer pass on its strip — columns [k Nb/G, (k+1) Nb/G) —
+ * and every other pass on its range — elements [k N/G, (k+1) N/G) —, with ONE all-to-all of N/G x 32 bytes per member between them
+ * (packed on the device, copied device to device: xGMI peer copies between GPUs, plain copies between members that share one).
+ * A transform shards when G is a power of two >= 2, its plan has at least two passes, G <= N1 and 2 G <= Nb.
+ *   zkhip_multi_ntt           zkhip_ntt over the members: same arguments, same bytes out (natural order in and out);
+ *   zkhip_multi_witness_map   zkhip_witness_map over the members' constraint system (zkhip_multi_r1cs_load): the same h bytes
+ *                             (N x 32 B, natural order); three all-to-alls, the mat-vec replicated on every member.
+ * Both shard whenever they can; otherwise member 0 runs the single-context call.  Errors: zkhip_multi_last_error.
+ *   zkhip_multi_transform_shard(m, 0 / 1)   lets zkhip_prove_g16_multi shard the witness map of a proof over a Groth16 key that is
+ *                             NOT bound to its system (-1: leave it); returns the previous setting.  OFF by default: no machine with
+ *                             more than one GPU has measured it.  Bound keys keep the a/b split above, GM17 and whatever does not
+ *                             shard stay replicated; the proof bytes are the same on every path.
+ *   zkhip_multi_last_shard    the number of members the transforms of the last zkhip_multi_ntt / _witness_map / zkhip_prove_*_multi
+ *                             were sharded over (0: they were not).
+ * Not sharded: bound keys, GM17, replicas and zkhip_prove_g16_multi_batch, ranks in separate processes (split_begin / _end), member
+ * counts that are not powers of two. */
+int32_t zkhip_multi_ntt(zkhip_multi* m, int32_t curve, uint32_t log_n, int32_t dir, uint8_t* data);
+int32_t zkhip_multi_witness_map(zkhip_multi* m, const uint8_t* z, uint8_t* h_out);
+int32_t zkhip_multi_transform_shard(zkhip_multi* m, int32_t on);
+int32_t zkhip_multi_last_shard(const zkhip_multi* m);
 int32_t zkhip_prove_g16_multi_batch(zkhip_multi* m, uint32_t count, const uint8_t* z, const uint8_t* rs, uint8_t* proofs_out,
                                     zkhip_timings* timings);
 

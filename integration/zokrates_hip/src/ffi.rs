@@ -110,6 +110,11 @@ extern "C" {
     pub fn zkhip_multi_bind(m: *mut zkhip_multi, key_bytes: *const u8, len: usize) -> i32;
     pub fn zkhip_multi_unbind(m: *mut zkhip_multi) -> i32;
     pub fn zkhip_multi_transform_split(m: *mut zkhip_multi, on: i32) -> i32;
+    /// the transform domain sharded across the members: stand-alone calls, and the switch for unbound Groth16 proofs (off by default)
+    pub fn zkhip_multi_ntt(m: *mut zkhip_multi, curve: i32, log_n: u32, dir: i32, data: *mut u8) -> i32;
+    pub fn zkhip_multi_witness_map(m: *mut zkhip_multi, z: *const u8, h_out: *mut u8) -> i32;
+    pub fn zkhip_multi_transform_shard(m: *mut zkhip_multi, on: i32) -> i32;
+    pub fn zkhip_multi_last_shard(m: *const zkhip_multi) -> i32;
     pub fn zkhip_prove_g16_multi(m: *mut zkhip_multi, z: *const u8, r: *const u8, s: *const u8, proof_out: *mut u8,
         timings: *mut zkhip_timings) -> i32;
     pub fn zkhip_prove_gm17_multi(m: *mut zkhip_multi, z: *const u8, d1_d2_r: *const u8, proof_out: *mut u8,

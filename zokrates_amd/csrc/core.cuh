@@ -21,6 +21,7 @@
 
 #include "../../include/zkhip.h"
 #include "devrt.h"
+#include "ntt_shard.h"
 #include "ec.cuh"
 #include "kernels_msm.cuh"
 #include "kernels_ntt.cuh"
@@ -235,6 +236,15 @@ struct zkhip_ctx {
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
     // process would leave the second GPU of a process at the 64 KiB default)
     std::unordered_set<const void*> lds_opted;
+    // a member of a zkhip_multi whose transforms are sharded (ntt_shard.h): the staging of its all-to-alls.  Consecutive exchanges
+    // alternate between the two `send` sets: a member packs exchange e + 2 into the set of exchange e only after it has waited, in
+    // exchange e + 1, for every peer's `packed` event of e + 1 — recorded on the peer's stream behind that peer's copies of e
+    struct Shard {
+        DBuf send[2], recv, out;
+        Event packed[2] = {nullptr, nullptr};   // made once (shard_state)
+        unsigned turn = 0;                      // exchanges entered so far: the next one packs into send[turn & 1]
+        std::vector<uint8_t> host;              // a strip on its way in, a range on its way out
+    } shard;
 };
 // ---- streams by dispatcher.  The hardware queues of a process are dealt round-robin to the chip's four compute dispatchers
 // ("pipes") in the order they are made, whatever their priority, and a dispatch that still has workgroups to place holds its
@@ -582,6 +592,98 @@ static void ntt_kind_b(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, boo
     } else {
         ntt_rows<C>(ctx, pl, data, inverse, final_post, nvec, vec_stride, canon);
     }
+}
+
+// ------------------------------------------------------------------ transforms sharded across the members of a zkhip_multi
+// (ntt_shard.h: member k runs the outer pass on its strip of columns and every other pass on its range of rows, one all-to-all
+// between them.)  The passes are the plan's kernels over a strip or a range of the full-length vector: a pointer offset, a smaller
+// grid, a tile that fits — columns per workgroup <= the strip's width, rows per workgroup <= the rows of the range; `post` and
+// `minus` tables as long as the vector move with the data, tables per block (post_mask = Nb - 1) stay: a range starts on a
+// multiple of Nb.
+template <class C>
+static bool shard_ok(const NttPlan<C>* pl, size_t G) { return ntt_shardable(pl->log1, pl->N1, pl->Nb, G); }
+static inline size_t ntt_smem_for(u32 nseq, u32 n) { return (size_t)9 * nseq * ntt_seq_stride((int)n) * 4; }
+static inline int ntt_threads_for(u64 butterflies) { return (int)std::min<u64>(512, std::max<u64>(64, (butterflies + 63) / 64 * 64)); }
+template <class C>
+static void shard_cols(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, typename C::Fr* data, bool inverse, const typename C::Fr* post, int nvec,
+                       u64 vec_stride, int canon = 0) {
+    typedef typename C::Fr Fr;
+    const int Cw = (int)std::min<u32>((u32)pl->C_cols, g.W);
+    const u64 off = g.strip_origin(k);
+    ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3((unsigned)(g.W / (u32)Cw), nvec), dim3(ntt_threads_for((u64)Cw * pl->N1 / 4)), ntt_smem_for((u32)Cw, pl->N1),
+              ctx->ws, data + off, vec_stride, pl->log1, (u32)pl->Nb, Cw, ptr<u32>(pl->plan1[inverse ? 1 : 0]), pl->plen1, post ? post + off : post, canon,
+              (const Fr*)nullptr, (u64)0, ~(u64)0, ctx->ntt_fuse_first);
+}
+template <class C>
+static void shard_mid(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, typename C::Fr* data, bool inverse, const typename C::Fr* post, u64 post_mask,
+                      int nvec, u64 vec_stride) {
+    typedef typename C::Fr Fr;
+    const u64 off = g.range_origin(k);
+    ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3(pl->N3 / pl->C_mid, nvec, g.rows), dim3(pl->threads_mid), pl->smem_mid, ctx->ws, data + off, vec_stride,
+              pl->log2, pl->N3, pl->C_mid, ptr<u32>(pl->plan2[inverse ? 1 : 0]), pl->plen2, (post && post_mask == ~(u64)0) ? post + off : post, 0, (const Fr*)nullptr,
+              pl->Nb, post_mask, ctx->ntt_fuse_first);
+}
+template <class C>
+static void shard_rows(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, typename C::Fr* data, bool inverse, const typename C::Fr* post, int nvec,
+                       u64 vec_stride, int canon = 0, const typename C::Fr* minus = nullptr, u64 post_mask = ~(u64)0) {
+    typedef typename C::Fr Fr;
+    const bool three = pl->log3 > 0;
+    const int lg = three ? pl->log3 : pl->log2;
+    const u64 off = g.range_origin(k), nrows = g.range_len() >> lg;
+    const u32 R = (u32)std::min<u64>((u64)pl->R_rows, nrows), last = 1u << lg;
+    ZK_LAUNCH((k_ntt_rows<typename Fr::Params>), dim3((unsigned)(nrows / R), nvec), dim3(ntt_threads_for((u64)R * last / 4)), ntt_smem_for(R, last), ctx->ws,
+              data + off, vec_stride, lg, (int)R, ptr<u32>((three ? pl->plan3 : pl->plan2)[inverse ? 1 : 0]), three ? pl->plen3 : pl->plen2,
+              (post && post_mask == ~(u64)0) ? post + off : post, canon, minus ? minus + off : minus, post_mask, ctx->ntt_fuse_first);
+}
+// the staging of member `ctx` for exchanges of up to `nvec` vectors, its two events
+static inline void shard_state(zkhip_ctx* ctx, const ShardGeom& g, u32 nvec) {
+    const size_t bytes = (size_t)g.staging_len(nvec) * 32;
+    ctx->shard.send[0].ensure(bytes);
+    ctx->shard.send[1].ensure(bytes);
+    ctx->shard.recv.ensure(bytes);
+    for (Event& e : ctx->shard.packed)
+        if (!e) e = event_create();
+}
+static inline ShardMove shard_move_args(const ShardGeom& g, u32 k, u64 vec_stride, bool by_row, bool own) {
+    ShardMove a;
+    a.vec_stride = vec_stride;
+    a.nb = g.Nb;
+    a.G = g.G;
+    a.me = k;
+    a.rows = g.rows;
+    a.log_w = ilog2_floor(g.W);
+    a.by_row = by_row ? 1 : 0;
+    a.own = own ? 1 : 0;
+    return a;
+}
+static inline unsigned shard_move_blocks(const ShardGeom& g) { return (unsigned)std::min<u64>(1024, std::max<u64>(1, (2 * g.block + 255) / 256)); }
+// first half of an exchange: this member's G - 1 foreign blocks of `nvec` vectors into the staging set of this turn, `packed` behind
+template <class C>
+static void shard_pack(zkhip_ctx* ctx, const ShardGeom& g, u32 k, const typename C::Fr* data, u32 nvec, u64 vec_stride, bool by_row) {
+    typedef typename C::Fr Fr;
+    zkhip_ctx::Shard& sh = ctx->shard;
+    const unsigned set = sh.turn & 1u;
+    ZK_LAUNCH((k_ntt_shard_pack<typename Fr::Params>), dim3(shard_move_blocks(g), nvec, g.G), dim3(256), 0, ctx->ws, data, ptr<Fr>(sh.send[set]),
+              shard_move_args(g, k, vec_stride, by_row, false));
+    event_record(sh.packed[set], ctx->ws);
+}
+// second half, entered only when EVERY member has packed (the caller's two phases): the blocks the peers packed for this member
+// travel into its staging behind their `packed` events, one launch scatters them
+template <class C>
+static void shard_fetch(zkhip_ctx* ctx, const ShardGeom& g, u32 k, typename C::Fr* data, u32 nvec, u64 vec_stride, bool by_row, zkhip_ctx* const* members) {
+    typedef typename C::Fr Fr;
+    zkhip_ctx::Shard& sh = ctx->shard;
+    const unsigned set = sh.turn & 1u;
+    for (u32 j = 0; j < g.G; ++j) {
+        if (j == k) continue;
+        event_sync(members[j]->shard.packed[set]);      // (the peer's stream, possibly on another device: waited for on the host, as split_fetch does)
+        for (u32 v = 0; v < nvec; ++v)
+            dev_copy_between(ptr<Fr>(sh.recv) + g.slot_origin(v, j), ctx->device, ptr<Fr>(members[j]->shard.send[set]) + g.slot_origin(v, k), members[j]->device,
+                             (size_t)g.block * sizeof(Fr), ctx->ws);
+    }
+    ZK_LAUNCH((k_ntt_shard_unpack<typename Fr::Params>), dim3(shard_move_blocks(g), nvec, g.G), dim3(256), 0, ctx->ws, data, ptr<Fr>(sh.recv),
+              shard_move_args(g, k, vec_stride, by_row, false));
+    ++sh.turn;
 }
 
 // ------------------------------------------------------------------ MSM driver
@@ -2350,6 +2452,68 @@ struct Prover {
         enqueue_tail(ctx, sl, pk, cs);
         hand_out_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2, tm);
     }
+    // ---- a member's share of a proof whose witness map is SHARDED across the members (an UNBOUND Groth16 key; shard_witness_map's
+    // four steps, each run on every member before the next on any): between shard_begin and shard_end_* the proof is pending in
+    // slot 0 as a split proof is.  The member's h coefficients end where its H MSM reads them — positions [h_lo, h_lo + h_n) of va —
+    // so the tail is an ordinary proof's.
+    static int can_shard(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 G, u32 k) {
+        if (pk->scheme != 0 || is_bound(pk, cs)) return -1;
+        const NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
+        return (shard_ok(pl, G) && pk->h_lo == (u64)k * (pl->N / G) && pk->h_n == pl->N / G) ? pl->split() : -1;
+    }
+    static void shard_begin(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const uint8_t* r, const uint8_t* s_, u32 G, u32 k) {
+        ProofSlot& sl = ctx->slots[0];
+        PkLoader<C>::check_match(pk, cs, 0);
+        require(z_host && pk->scheme == 0 && !is_bound(pk, cs), ZKHIP_ERR_BAD_ARG, "internal: only a Groth16 proof over an unbound key shards its witness map");
+        Fr rr = fe_from_bytes_canon<Fr>(r), ss = fe_from_bytes_canon<Fr>(s_);
+        require(canon_lt_mod(rr) && canon_lt_mod(ss), ZKHIP_ERR_BAD_ARG, "r or s not a canonical field element");
+        NttPlan<C>* pl = open_slot(ctx, sl, pk);
+        sl.half = -1;
+        sl.lone = false;
+        sl.check_idx = -1;
+        memcpy(sl.r, r, 32);
+        memcpy(sl.s, s_, 32);
+        Stream st = ctx->stream;
+        stage_z(ctx, sl, pk->m, pk->m + 2, z_host, nullptr, false);
+        stage_scalars(ctx, pl, sl.scalars.p, pk->m, r, s_);
+        event_record(sl.ev[0], st);
+        const Lay ly(ctx, pk);
+        ly.reserve(sl);
+        start_z_lanes(ctx, sl, pk, ly);
+        Stream wn = ctx->serial ? st : slot_ntt_stream(ctx, sl);
+        stream_wait_event(wn, sl.ev[0]);
+        event_record(sl.ev[1], wn);
+        ctx->ws = wn;
+        shard_witness_map(ctx, cs, pl, G, k, 0, nullptr);
+        ctx->ws = ctx->stream;
+        sl.split_pk = pk;
+        sl.split_cs = cs;
+        sl.split_bound = false;
+        sl.split_pending = true;
+    }
+    static ProofSlot& shard_slot(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs) {
+        ProofSlot& s0 = ctx->slots[0];
+        require(s0.split_pending && s0.half < 0 && s0.split_pk == pk && s0.split_cs == cs, ZKHIP_ERR_BAD_ARG, "no sharded proof of these handles pending in this context");
+        return s0;
+    }
+    static void shard_step(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 G, u32 k, int step, zkhip_ctx* const* members) {
+        ProofSlot& sl = shard_slot(ctx, pk, cs);
+        ctx->cur = &sl;
+        ctx->ws = ctx->serial ? ctx->stream : slot_ntt_stream(ctx, sl);
+        shard_witness_map(ctx, cs, get_plan<C>(ctx, pk->logN), G, k, step, members);
+        ctx->ws = ctx->stream;
+    }
+    static void shard_end_partial(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, uint8_t* partial_out, zkhip_timings* tm) {
+        ProofSlot& sl = shard_slot(ctx, pk, cs);
+        enqueue_tail(ctx, sl, pk, cs);
+        emit_partial(ctx, ctx->slots[0], pk, partial_out, tm);
+    }
+    static void shard_end_device_sums(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const void** d_ws1, size_t* b1, const void** d_ws2, size_t* b2,
+                                      zkhip_timings* tm) {
+        ProofSlot& sl = shard_slot(ctx, pk, cs);
+        enqueue_tail(ctx, sl, pk, cs);
+        hand_out_sums(ctx, ctx->slots[0], pk, d_ws1, b1, d_ws2, b2, tm);
+    }
     // one rank's share of a proof, left ON THE DEVICE: the raw bucket-set sums of its five MSMs (ws1: 4 G1 MSMs x Wmax XYZZ
     // sums, ws2: the G2 MSM), for an exchange that never touches host memory (zkhip_multi_use_rccl: RCCL all-gather over
     // xGMI).  Valid until the slot's next proof.
@@ -2578,6 +2742,126 @@ struct Prover {
         stream_sync(ctx->stream);
     }
 
+    // ---- the same two calls over the members of a zkhip_multi, the domain sharded (ntt_shard.h).  Every step below is one member's
+    // part; the caller (zkhip_api.hip) runs a step on every member before the next on any, because a member fetches what its
+    // peers packed in the step before.
+    // (the plan's split if this member's plan shards over G members, else -1: the members must agree on it)
+    static int ntt_shardable_api(zkhip_ctx* ctx, u32 log_n, u32 G) { const NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n); return shard_ok(pl, G) ? pl->split() : -1; }
+    // zkhip_multi_ntt, first step: the member's strip of the input, the outer pass, its blocks packed
+    static void shard_ntt_begin(zkhip_ctx* ctx, u32 G, u32 k, u32 log_n, int dir, const uint8_t* data) {
+        NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n);
+        require(shard_ok(pl, G), ZKHIP_ERR_BAD_ARG, "internal: this transform does not shard");
+        const ShardGeom g = ntt_shard_geom(pl->N1, pl->Nb, G);
+        Stream s = ctx->stream;
+        ctx->ws = s;
+        ctx->cur->va.ensure(pl->N * sizeof(Fr));
+        shard_state(ctx, g, 1);
+        zkhip_ctx::Shard& sh = ctx->shard;
+        Fr* a = ptr<Fr>(ctx->cur->va);
+        // the strip arrives as the G blocks of its column of blocks, rows back to back: the layout of the staging
+        const u64 n = g.range_len();           // (a strip holds as many elements as a range)
+        sh.host.resize(n * 32);
+        for (u32 r = 0; r < pl->N1; ++r) memcpy(sh.host.data() + (size_t)r * g.W * 32, data + ((size_t)r * pl->Nb + g.strip_origin(k)) * 32, (size_t)g.W * 32);
+        dev_h2d(sh.recv.p, sh.host.data(), n * 32, s);
+        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(n, 256)), dim3(256), 0, s, ptr<Fr>(sh.recv), ptr<Fr>(sh.recv), n, pl->k_to_rp);   // canonical -> R'-form
+        ZK_LAUNCH((k_ntt_shard_unpack<typename Fr::Params>), dim3(shard_move_blocks(g), 1, G), dim3(256), 0, s, a, ptr<Fr>(sh.recv), shard_move_args(g, k, 0, true, true));
+        if (dir == 2)     // coset_fft: x_i * g^i first
+            ZK_LAUNCH((k_shard_strip_pow<Fr>), dim3(blocks_for(n, 256)), dim3(256), 0, s, a + g.strip_origin(k), pl->g, pl->N1, ilog2_floor(g.W), pl->Nb, g.strip_origin(k));
+        const bool inverse = dir == 1 || dir == 3;
+        shard_cols<C>(ctx, pl, g, k, a, inverse, inverse ? ptr<Fr>(pl->tw_inv) : ptr<Fr>(pl->tw_fwd), 1, 0);
+        shard_pack<C>(ctx, g, k, a, 1, 0, true);
+    }
+    // second step: the peers' blocks, the passes over the member's range, and its part of the output in natural order
+    static void shard_ntt_end(zkhip_ctx* ctx, u32 G, u32 k, u32 log_n, int dir, uint8_t* data, zkhip_ctx* const* members) {
+        NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n);
+        const ShardGeom g = ntt_shard_geom(pl->N1, pl->Nb, G);
+        Stream s = ctx->stream;
+        ctx->ws = s;
+        Fr* a = ptr<Fr>(ctx->cur->va);
+        const bool inverse = dir == 1 || dir == 3;
+        shard_fetch<C>(ctx, g, k, a, 1, 0, false, members);
+        if (pl->log3 > 0) shard_mid<C>(ctx, pl, g, k, a, inverse, inverse ? ptr<Fr>(pl->tw2_inv) : ptr<Fr>(pl->tw2_fwd), pl->Nb - 1, 1, 0);
+        shard_rows<C>(ctx, pl, g, k, a, inverse, nullptr, 1, 0, 1);
+        range_out(ctx, pl, g, k, a, inverse ? 2 : 1, dir == 3 ? pl->g_inv : Fr::one(), pl->n_inv, data);
+    }
+    // a member's range (sigma order) to the natural positions of the host vector `out` it holds: permuted (and scaled) on the device
+    // into runs of g.rows elements, one run per inner index
+    static void range_out(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, const Fr* vec, int mode, const Fr& base, const Fr& scale, uint8_t* out) {
+        zkhip_ctx::Shard& sh = ctx->shard;
+        Stream s = ctx->ws;
+        const u64 n = g.range_len();
+        sh.out.ensure(n * sizeof(Fr));
+        ZK_LAUNCH((k_shard_range_out<Fr>), dim3(blocks_for(n, 256)), dim3(256), 0, s, vec + g.range_origin(k), ptr<Fr>(sh.out), g.rows, pl->Nb, pl->N1, pl->N2, pl->N3,
+                  k * g.rows, mode, base, scale);
+        sh.host.resize(n * 32);
+        dev_d2h(sh.host.data(), sh.out.p, n * 32, s);
+        stream_sync(s);
+        for (u64 inner = 0; inner < pl->Nb; ++inner)
+            memcpy(out + (inner * pl->N1 + (u64)k * g.rows) * 32, sh.host.data() + inner * g.rows * 32, (size_t)g.rows * 32);
+    }
+    // The witness map of `witness_map` (unbound: six transforms) in four steps around three all-to-alls; a, b, c in the slot's va,
+    // on ctx->ws.  Step 0 ends with a, b, c packed behind their inverse transforms' outer pass; 1: their ranges (a, b leave with
+    // s_coset, c with s_cexit as canonical integers), the coset transform's passes over the range, a and b packed; 2: its outer pass,
+    // the quotient on the strip, the last transform's outer pass, one vector packed; 3: its range, canonical, minus c's share — the
+    // member's h coefficients are positions [k N/G, (k+1) N/G) of va, sigma order.
+    static void shard_witness_map(zkhip_ctx* ctx, const zkhip_r1cs* cs, NttPlan<C>* pl, u32 G, u32 k, int step, zkhip_ctx* const* members, bool check = false) {
+        require(shard_ok(pl, G), ZKHIP_ERR_BAD_ARG, "internal: this transform does not shard");
+        const ShardGeom g = ntt_shard_geom(pl->N1, pl->Nb, G);
+        Stream s = ctx->ws;
+        const u64 N = pl->N;
+        Fr *a = ptr<Fr>(ctx->cur->va), *b = a + N, *c = b + N;
+        const bool three = pl->log3 > 0;
+        if (step == 0) {
+            ctx->cur->va.ensure(3 * N * sizeof(Fr));
+            a = ptr<Fr>(ctx->cur->va); b = a + N; c = b + N;
+            shard_state(ctx, g, 3);
+            matvec(ctx, cs, ptr<Fr>(ctx->cur->zmont), a, b, c, cs->n, cs->l, N, 3);
+            if (check) enqueue_check(*ctx->cur, a, b, c, cs->n, s);
+            event_record(ctx->cur->ntt_b, s);
+            shard_cols<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw_inv), 3, N);
+            shard_pack<C>(ctx, g, k, a, 3, N, true);
+        } else if (step == 1) {
+            shard_fetch<C>(ctx, g, k, a, 3, N, false, members);
+            if (three) shard_mid<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw2_inv), pl->Nb - 1, 3, N);
+            shard_rows<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->s_coset), 2, N);
+            shard_rows<C>(ctx, pl, g, k, c, true, ptr<Fr>(pl->s_cexit), 1, 0, 1);
+            if (three) {
+                shard_rows<C>(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw2_fwd), 2, N, 0, nullptr, pl->Nb - 1);
+                shard_mid<C>(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw_fwd), ~(u64)0, 2, N);
+            } else {
+                shard_rows<C>(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw_fwd), 2, N);
+            }
+            shard_pack<C>(ctx, g, k, a, 2, N, false);
+        } else if (step == 2) {
+            shard_fetch<C>(ctx, g, k, a, 2, N, true, members);
+            shard_cols<C>(ctx, pl, g, k, a, false, nullptr, 2, N);
+            const u64 off = g.strip_origin(k);
+            ZK_LAUNCH((k_quotient_strip<typename Fr::Params>), dim3(blocks_for(g.range_len(), 256)), dim3(256), 0, s, a + off, b + off, pl->zinv_rp, a + off, pl->N1,
+                      ilog2_floor(g.W), pl->Nb);
+            shard_cols<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw_inv), 1, 0);
+            shard_pack<C>(ctx, g, k, a, 1, 0, true);
+        } else {
+            shard_fetch<C>(ctx, g, k, a, 1, 0, false, members);
+            if (three) shard_mid<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw2_inv), pl->Nb - 1, 1, 0);
+            shard_rows<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->s_cosetinv_canon), 1, 0, 1, c);
+            event_record(ctx->cur->ntt_e, s);
+        }
+    }
+    static int witness_map_shardable_api(zkhip_ctx* ctx, const zkhip_r1cs* cs, u32 G) { return ntt_shardable_api(ctx, (u32)cs->logN, G); }
+    // zkhip_multi_witness_map: step 0 stages the assignment first, step 3 hands the member's part of h out (h_out: N x 32 B, natural order)
+    static void shard_witness_map_api(zkhip_ctx* ctx, const zkhip_r1cs* cs, const uint8_t* z, uint8_t* h_out, u32 G, u32 k, int step, zkhip_ctx* const* members) {
+        ctx->ws = ctx->stream;
+        NttPlan<C>* pl = get_plan<C>(ctx, cs->logN);
+        if (step == 0) {
+            const u64 m = cs->l + cs->w;
+            uint8_t zero[32] = {0};
+            upload_z(ctx, ctx->cur->scalars, m, m + 2, z, ctx->cur->zflag);
+            stage_scalars(ctx, pl, ctx->cur->scalars.p, m, zero, zero);
+        }
+        shard_witness_map(ctx, cs, pl, G, k, step, members);
+        if (step == 3) range_out(ctx, pl, ntt_shard_geom(pl->N1, pl->Nb, G), k, ptr<Fr>(ctx->cur->va), 0, Fr::one(), Fr::one(), h_out);
+    }
+
     // zkhip_field_op: count x (a op b) over elements F, canonical integers in and out, in workgroups of T; `launch` runs the kernel
     // of the field's form on the two Montgomery vectors, result into the first (field_op_dispatch names the six)
     template <class F, class Launch>
@@ -2677,6 +2961,17 @@ struct CurveOps {
     void (*r1cs_check)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const void*, u64 out[2]);
     void (*ntt)(zkhip_ctx*, u32, int, uint8_t*);
     void (*witness_map)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, uint8_t*);
+    // sharded across the members of a zkhip_multi (ntt_shard.h): member k of G, step by step
+    int (*ntt_shardable)(zkhip_ctx*, u32 log_n, u32 G);       // the plan's split, or -1
+    void (*shard_ntt_begin)(zkhip_ctx*, u32 G, u32 k, u32 log_n, int dir, const uint8_t*);
+    void (*shard_ntt_end)(zkhip_ctx*, u32 G, u32 k, u32 log_n, int dir, uint8_t*, zkhip_ctx* const* members);
+    int (*witness_map_shardable)(zkhip_ctx*, const zkhip_r1cs*, u32 G);
+    void (*shard_witness_map)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t* z, uint8_t* h_out, u32 G, u32 k, int step, zkhip_ctx* const* members);
+    int (*can_shard)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, u32 G, u32 k);
+    void (*shard_begin)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const uint8_t*, const uint8_t*, u32 G, u32 k);
+    void (*shard_step)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, u32 G, u32 k, int step, zkhip_ctx* const* members);
+    void (*shard_end_partial)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, uint8_t*, zkhip_timings*);
+    void (*shard_end_device_sums)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const void**, size_t*, const void**, size_t*, zkhip_timings*);
     void (*msm_g1)(zkhip_ctx*, u64, const uint8_t*, const uint8_t*, uint8_t*);
     void (*msm_g2)(zkhip_ctx*, u64, const uint8_t*, const uint8_t*, uint8_t*);
     void (*field_op)(zkhip_ctx*, int field, int op, u64, const uint8_t*, const uint8_t*, uint8_t*);
@@ -2745,6 +3040,16 @@ static CurveOps make_curve_ops() {
     o.r1cs_check = &Prover<C>::r1cs_check;
     o.ntt = &Prover<C>::ntt_api;
     o.witness_map = &Prover<C>::witness_map_api;
+    o.ntt_shardable = &Prover<C>::ntt_shardable_api;
+    o.shard_ntt_begin = &Prover<C>::shard_ntt_begin;
+    o.shard_ntt_end = &Prover<C>::shard_ntt_end;
+    o.witness_map_shardable = &Prover<C>::witness_map_shardable_api;
+    o.shard_witness_map = &Prover<C>::shard_witness_map_api;
+    o.can_shard = &Prover<C>::can_shard;
+    o.shard_begin = &Prover<C>::shard_begin;
+    o.shard_step = &Prover<C>::shard_step;
+    o.shard_end_partial = &Prover<C>::shard_end_partial;
+    o.shard_end_device_sums = &Prover<C>::shard_end_device_sums;
     o.msm_g1 = &Prover<C>::template msm_api<typename C::Fq, 2>;
     o.msm_g2 = &Prover<C>::template msm_api<typename C::Fq2, 4>;
     o.field_op = &field_op_dispatch<C>;

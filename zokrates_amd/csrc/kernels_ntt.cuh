@@ -781,4 +781,79 @@ __global__ void __launch_bounds__(512, ZK_NTT_WGS_PER_CU) k_ntt_rows(Fe<P>* __re
     }
 }
 
+// ---------------- a transform sharded across the members of a zkhip_multi (ntt_shard.h) ----------------
+// The all-to-all between the outer pass (on a member's strip of columns) and the passes after it (on its range of rows) moves
+// blocks of `rows` row segments of 2^log_w elements, `nb` elements apart in the full-length vector.  A member packs the blocks it
+// owes its peers into contiguous staging — slot (vector, peer), `block` = rows << log_w elements each — the bytes travel with
+// dev_copy_between, and the receiver unpacks them to the same positions of its own vector.  `by_row`: the block exchanged with
+// `peer` is (rows of the peer's range x columns of my strip), else (rows of my range x columns of the peer's strip): kind A packs
+// by row and unpacks by column, kind B the other way round.  grid = (pieces, vectors, peers); a member's own block stays where it
+// is unless `own` (the upload of a strip arrives as G blocks).  16-byte pieces, two per element: consecutive work-items take
+// consecutive pieces of a row segment.
+struct ShardMove {
+    u64 vec_stride;   // elements between consecutive vectors
+    u64 nb;           // row stride
+    u32 G, me, rows;
+    int log_w;
+    int by_row, own;
+};
+template <bool PACK>
+static __device__ __forceinline__ void ntt_shard_move(uint4* __restrict__ vec, uint4* __restrict__ staging, const ShardMove& g) {
+    const u32 v = blockIdx.y, peer = blockIdx.z;
+    if (peer == g.me && !g.own) return;
+    const u64 w = (u64)1 << g.log_w, block = (u64)g.rows << g.log_w;
+    const u64 origin = g.by_row ? (u64)peer * g.rows * g.nb + (u64)g.me * w : (u64)g.me * g.rows * g.nb + (u64)peer * w;
+    uint4* data = vec + 2 * ((u64)v * g.vec_stride + origin);
+    uint4* slot = staging + 2 * (((u64)v * g.G + peer) * block);
+    const u64 pieces = 2 * block;
+    for (u64 q = (u64)blockIdx.x * blockDim.x + threadIdx.x; q < pieces; q += (u64)gridDim.x * blockDim.x) {
+        const u64 row = q >> (g.log_w + 1), in_row = q & (2 * w - 1);
+        if (PACK) slot[q] = data[2 * row * g.nb + in_row];
+        else data[2 * row * g.nb + in_row] = slot[q];
+    }
+}
+template <class P>
+__global__ void __launch_bounds__(256) k_ntt_shard_pack(const Fe<P>* __restrict__ vec, Fe<P>* __restrict__ staging, ShardMove g) {
+    ZK_PRIO_HIGH();
+    ntt_shard_move<true>((uint4*)vec, (uint4*)staging, g);
+}
+template <class P>
+__global__ void __launch_bounds__(256) k_ntt_shard_unpack(Fe<P>* __restrict__ vec, const Fe<P>* __restrict__ staging, ShardMove g) {
+    ZK_PRIO_HIGH();
+    ntt_shard_move<false>((uint4*)vec, (uint4*)staging, g);
+}
+// k_quotient over a strip: `rows` segments of `w` elements, `nb` apart (a, b and out point at the strip's first element)
+template <class P>
+__global__ void k_quotient_strip(const Fe<P>* __restrict__ a, const Fe<P>* __restrict__ b, Fe<P> zinv, Fe<P>* __restrict__ out, u32 rows, int log_w, u64 nb) {
+    ZK_PRIO_HIGH();
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ((u64)rows << log_w)) return;
+    const u64 i = (e >> log_w) * nb + (e & (((u64)1 << log_w) - 1));
+    const Fu<P> ab = fu_mul_inl(fu_unpack<P>(a[i].v), fu_unpack<P>(b[i].v));
+    out[i] = rp_canon(fu_mul_inl(ab, fu_unpack<P>(zinv.v)));
+}
+// x_i *= base^i over a strip whose first element has index i0 (the coset factor on the way into a sharded coset_fft)
+template <class F>
+__global__ void k_shard_strip_pow(F* __restrict__ data, F base, u32 rows, int log_w, u64 nb, u64 i0) {
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ((u64)rows << log_w)) return;
+    const u64 i = (e >> log_w) * nb + (e & (((u64)1 << log_w) - 1));
+    data[i] = fe_mul(data[i], fe_pow_u64(base, i0 + i));
+}
+// A member's range on the way out, sigma order -> natural order: position p = k1 * nb + rem of the range (k1 counted from its
+// first outer index k1_0) holds natural index (k1_0 + k1) + n1 * inner(rem) (sigma_nat), and goes to out[inner * rows + k1] —
+// the host then copies nb runs of `rows` elements to natural index inner * n1 + k1_0.  mode 0: the value as it is; 1: out of
+// the R'-form; 2: times scale * base^natural first (what zkhip_ntt applies to an inverse transform).
+template <class F>
+__global__ void k_shard_range_out(const F* __restrict__ in, F* __restrict__ out, u32 rows, u64 nb, u32 n1, u32 n2, u32 n3, u32 k1_0, int mode, F base, F scale) {
+    const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= rows * nb) return;
+    const u64 k1 = p / nb, rem = p % nb;
+    const u64 inner = rem / n3 + (u64)n2 * (rem % n3);
+    F x = in[p];
+    if (mode == 2) x = fe_mul(x, fe_mul(scale, fe_pow_u64(base, k1_0 + k1 + (u64)n1 * inner)));
+    if (mode >= 1) x = rp_to_plain(x);
+    out[inner * rows + k1] = x;
+}
+
 }  // namespace zk

@@ -351,6 +351,7 @@ void zkhip_ctx_free(zkhip_ctx* ctx) {
         event_destroy(sl.g1_go);
         host_free_pinned(sl.h_ws);
     }
+    for (Event e : ctx->shard.packed) if (e) event_destroy(e);
     for (Stream q : ctx->idle_streams) stream_destroy(q);
     if (ctx->ntt_lone_made) stream_destroy(ctx->ntt_lone_stream);
     if (ctx->out_made) stream_destroy(ctx->out_stream);
@@ -963,6 +964,8 @@ struct zkhip_multi {
     std::vector<DBuf> gather1, gather2;   // all members' ws1 / ws2, rank-major, on every member's device
     std::string rccl_desc;
     bool last_split = false;         // the last zkhip_prove_*_multi split its witness map
+    bool transform_shard = false;    // unbound Groth16 proofs shard their witness map's domain across the members (zkhip_multi_transform_shard)
+    int last_shard = 0;              // members the transforms of the last zkhip_multi_ntt / _witness_map / zkhip_prove_*_multi were sharded over
 };
 }  // extern "C"
 
@@ -1044,6 +1047,19 @@ static int32_t multi_each(zkhip_multi* m, Fn&& fn) try {
 static bool multi_loaded(const zkhip_multi* m) {
     for (auto* c : m->cs) if (!c) return false;
     for (auto* p : m->pk) if (!p) return false;
+    return true;
+}
+// fn(k) on every member: the plan's split where member k can shard, -1 where it cannot.  Sharded only if all agree.
+template <class Fn>
+static bool multi_all_shard(zkhip_multi* m, Fn&& fn) {
+    const size_t n = m->ctx.size();
+    if (n < 2) return false;
+    int first = -1;
+    for (size_t k = 0; k < n; ++k) {
+        int v = -1;
+        if (guarded(m->ctx[k], [&] { v = fn(k); }) != ZKHIP_OK || v < 0 || (k && v != first)) return false;
+        first = v;
+    }
     return true;
 }
 extern "C" {
@@ -1261,6 +1277,69 @@ int32_t zkhip_prove_g16_multi_batch(zkhip_multi* m, uint32_t count, const uint8_
 static void multi_split_drop(zkhip_multi* m) {
     for (auto* c : m->ctx) split_drop(c);
 }
+// ---- transforms sharded across the members (ntt_shard.h): every step runs on every member before the next step on any — a
+// member fetches what its peers packed in the step before — and a failure in any step drops every member: nothing stays pending, no
+// staging turn is left half taken, and nobody waits for an event that will never be recorded
+static void multi_shard_drop(zkhip_multi* m) {
+    for (auto* c : m->ctx) {
+        try { dev_set(c->device); dev_sync_all(); } catch (...) {}
+        c->shard.turn = 0;
+        split_drop(c);
+    }
+}
+int32_t zkhip_multi_transform_shard(zkhip_multi* m, int32_t on) {
+    if (!m) return ZKHIP_ERR_BAD_ARG;
+    const int32_t was = m->transform_shard ? 1 : 0;
+    if (on >= 0) m->transform_shard = on != 0;
+    return was;
+}
+int32_t zkhip_multi_last_shard(const zkhip_multi* m) { return m ? m->last_shard : 0; }
+int32_t zkhip_multi_ntt(zkhip_multi* m, int32_t curve, uint32_t log_n, int32_t dir, uint8_t* data) {
+    if (!m) return ZKHIP_ERR_BAD_ARG;
+    m->last_shard = 0;
+    const CurveOps* ops = nullptr;
+    int32_t rc = guarded(m->ctx[0], [&] {
+        require(data && dir >= 0 && dir <= 3, ZKHIP_ERR_BAD_ARG, "bad argument");
+        ops = ops_for(curve);
+    });
+    if (rc != ZKHIP_OK) { m->err = std::string("member 0: ") + zkhip_last_error(m->ctx[0]); return rc; }
+    const uint32_t n = (uint32_t)m->ctx.size();
+    if (!multi_all_shard(m, [&](size_t k) { return ops->ntt_shardable(m->ctx[k], log_n, n); })) {
+        rc = zkhip_ntt(m->ctx[0], curve, log_n, dir, data);      // not shardable: the single-context transform on member 0
+        if (rc != ZKHIP_OK) m->err = std::string("member 0: ") + zkhip_last_error(m->ctx[0]);
+        return rc;
+    }
+    // (in place: every member has read its strip of `data` before any member writes its part of the result)
+    rc = multi_each(m, [&](size_t k) { return guarded(m->ctx[k], [&] { ops->shard_ntt_begin(m->ctx[k], n, (uint32_t)k, log_n, dir, data); }); });
+    if (rc == ZKHIP_OK)
+        rc = multi_each(m, [&](size_t k) { return guarded(m->ctx[k], [&] { ops->shard_ntt_end(m->ctx[k], n, (uint32_t)k, log_n, dir, data, m->ctx.data()); }); });
+    if (rc != ZKHIP_OK) { multi_shard_drop(m); return rc; }
+    m->last_shard = (int)n;
+    return ZKHIP_OK;
+}
+int32_t zkhip_multi_witness_map(zkhip_multi* m, const uint8_t* z, uint8_t* h_out) {
+    if (!m) return ZKHIP_ERR_BAD_ARG;
+    m->last_shard = 0;
+    if (!z || !h_out) { m->err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
+    for (auto* c : m->cs) if (!c) { m->err = "load the constraint system first"; return ZKHIP_ERR_BAD_ARG; }
+    const CurveOps* ops = nullptr;
+    int32_t rc = guarded(m->ctx[0], [&] { ops = ops_for(m->cs[0]->curve); });
+    if (rc != ZKHIP_OK) { m->err = std::string("member 0: ") + zkhip_last_error(m->ctx[0]); return rc; }
+    const uint32_t n = (uint32_t)m->ctx.size();
+    if (!multi_all_shard(m, [&](size_t k) { return ops->witness_map_shardable(m->ctx[k], m->cs[k], n); })) {
+        rc = zkhip_witness_map(m->ctx[0], m->cs[0], z, h_out);
+        if (rc != ZKHIP_OK) m->err = std::string("member 0: ") + zkhip_last_error(m->ctx[0]);
+        return rc;
+    }
+    for (int step = 0; step < 4; ++step) {
+        rc = multi_each(m, [&](size_t k) {
+            return guarded(m->ctx[k], [&] { ops->shard_witness_map(m->ctx[k], m->cs[k], z, h_out, n, (uint32_t)k, step, m->ctx.data()); });
+        });
+        if (rc != ZKHIP_OK) { multi_shard_drop(m); return rc; }
+    }
+    m->last_shard = (int)n;
+    return ZKHIP_OK;
+}
 static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const uint8_t* rnd, const uint8_t* s_, uint8_t* proof_out, zkhip_timings* timings) {
     if (!m) return ZKHIP_ERR_BAD_ARG;
     if (!z || !rnd || !proof_out || (scheme == 0 && !s_)) { m->err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
@@ -1287,6 +1366,29 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
         sops->split_fetch(m->ctx[k], m->pk[k], sops->split_half_ptr(m->ctx[p], m->pk[p], half_of(p)), m->ctx[p]->device, m->ctx[p]->slots[0].half_ready);
     };
     m->last_split = split;
+    // ... or its DOMAIN sharded across them (zkhip_multi_transform_shard; ntt_shard.h): an unbound Groth16 key, a power-of-two member
+    // count the plan divides by, every member's h range the range the sharded last transform leaves its h coefficients in.  Bound keys
+    // keep the split above; GM17 and whatever does not shard stay replicated.  The first three of shard_witness_map's four steps run
+    // here, each on every member before the next on any; the fourth leads a member's tail below.
+    const uint32_t G = (uint32_t)n;
+    const bool shard = !split && scheme == 0 && m->transform_shard && multi_all_shard(m, [&](size_t k) { return sops->can_shard(m->ctx[k], m->pk[k], m->cs[k], G, (uint32_t)k); });
+    m->last_shard = shard ? (int)n : 0;
+    if (shard) {
+        rc = multi_each(m, [&](size_t k) {
+            return guarded(m->ctx[k], [&] {
+                require(m->pk[k]->ctx == m->ctx[k] && m->cs[k]->ctx == m->ctx[k], ZKHIP_ERR_BAD_ARG, "handles belong to another context");
+                for (auto& sl : m->ctx[k]->slots) require(!sl.busy, ZKHIP_ERR_BAD_ARG, "a proof is in flight in this context");
+                sops->shard_begin(m->ctx[k], m->pk[k], m->cs[k], z, rnd, s_, G, (uint32_t)k);
+            });
+        });
+        for (int step = 1; step <= 2 && rc == ZKHIP_OK; ++step)
+            rc = multi_each(m, [&](size_t k) {
+                return guarded(m->ctx[k], [&] { sops->shard_step(m->ctx[k], m->pk[k], m->cs[k], G, (uint32_t)k, step, m->ctx.data()); }, true);
+            });
+        if (rc != ZKHIP_OK) { multi_shard_drop(m); return rc; }
+    }
+    auto shard_last = [&](size_t k) { sops->shard_step(m->ctx[k], m->pk[k], m->cs[k], G, (uint32_t)k, 3, m->ctx.data()); };
+    auto drop = [&] { if (shard) multi_shard_drop(m); else multi_split_drop(m); };
     if (split) {
         // phase A on every member before phase B on any: a member fetches its partner's half only when that half is enqueued
         rc = multi_each(m, [&](size_t k) {
@@ -1309,15 +1411,16 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
                 zkhip_ctx* c = m->ctx[k];
                 require(m->pk[k]->ctx == c && m->cs[k]->ctx == c, ZKHIP_ERR_BAD_ARG, "handles belong to another context");
                 if (split) { fetch(k); ops->split_end_device_sums(c, m->pk[k], m->cs[k], &d1[k], &b1[k], &d2[k], &b2[k], &tm[k]); }
+                else if (shard) { shard_last(k); ops->shard_end_device_sums(c, m->pk[k], m->cs[k], &d1[k], &b1[k], &d2[k], &b2[k], &tm[k]); }
                 else if (scheme == 0) ops->prove_device_sums(c, m->pk[k], m->cs[k], z, rnd, s_, &d1[k], &b1[k], &d2[k], &b2[k], &tm[k]);
                 else ops->gm17_prove_device_sums(c, m->pk[k], m->cs[k], z, rnd, &d1[k], &b1[k], &d2[k], &b2[k], &tm[k]);
                 m->gather1[k].ensure(n * b1[k]);
                 m->gather2[k].ensure(n * b2[k]);
-            }, split);
+            }, split || shard);
         };
 #ifdef ZK_EMU
         rc = multi_each(m, share);
-        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }
+        if (rc != ZKHIP_OK) { drop(); return rc; }
         for (size_t k = 0; k < n; ++k) {
             dev_d2d((uint8_t*)m->gather1[0].p + k * b1[0], d1[k], b1[0], m->ctx[0]->stream);
             dev_d2d((uint8_t*)m->gather2[0].p + k * b2[0], d2[k], b2[0], m->ctx[0]->stream);
@@ -1326,7 +1429,7 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
         // two phases: a member enters the collective only when EVERY member has its share (one that failed alone would
         // leave the others waiting in ncclAllGather for ever)
         rc = multi_each(m, share);
-        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }
+        if (rc != ZKHIP_OK) { drop(); return rc; }
         rc = multi_each(m, [&](size_t k) {
             return guarded(m->ctx[k], [&] {
                 Rccl& R = rccl();
@@ -1351,10 +1454,11 @@ static int32_t multi_prove(zkhip_multi* m, int scheme, const uint8_t* z, const u
     } else {
         rc = multi_each(m, [&](size_t k) {
             if (split) return guarded(m->ctx[k], [&] { fetch(k); sops->split_end_partial(m->ctx[k], m->pk[k], m->cs[k], &records[k * rec], &tm[k]); }, true);
+            if (shard) return guarded(m->ctx[k], [&] { shard_last(k); sops->shard_end_partial(m->ctx[k], m->pk[k], m->cs[k], &records[k * rec], &tm[k]); }, true);
             return scheme == 0 ? zkhip_prove_g16_partial(m->ctx[k], m->pk[k], m->cs[k], z, nullptr, rnd, s_, &records[k * rec], &tm[k])
                                : zkhip_prove_gm17_partial(m->ctx[k], m->pk[k], m->cs[k], z, nullptr, rnd, &records[k * rec], &tm[k]);
         });
-        if (rc != ZKHIP_OK) { multi_split_drop(m); return rc; }
+        if (rc != ZKHIP_OK) { drop(); return rc; }
     }
     rc = scheme == 0 ? zkhip_combine_g16(m->ctx[0], m->pk[0], (uint32_t)n, records.data(), rnd, s_, proof_out)
                      : zkhip_combine_gm17(m->ctx[0], m->pk[0], (uint32_t)n, records.data(), rnd, proof_out);

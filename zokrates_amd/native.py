@@ -76,6 +76,7 @@ class Library:
         "zkhip_assignment_upload_packed",
         "zkhip_queue_open", "zkhip_queue_state", "zkhip_queue_submit", "zkhip_queue_submit_packed", "zkhip_queue_ready", "zkhip_queue_collect",
         "zkhip_queue_close",
+        "zkhip_multi_ntt", "zkhip_multi_witness_map", "zkhip_multi_transform_shard", "zkhip_multi_last_shard",
     ]
 
     def __init__(self, path=None):
@@ -152,6 +153,10 @@ class Library:
         L.zkhip_multi_unbind.restype = i32; L.zkhip_multi_unbind.argtypes = [vp]
         L.zkhip_multi_transform_split.restype = i32; L.zkhip_multi_transform_split.argtypes = [vp, i32]
         L.zkhip_multi_last_split.restype = i32; L.zkhip_multi_last_split.argtypes = [vp]
+        L.zkhip_multi_ntt.restype = i32; L.zkhip_multi_ntt.argtypes = [vp, i32, u32, i32, vp]
+        L.zkhip_multi_witness_map.restype = i32; L.zkhip_multi_witness_map.argtypes = [vp, vp, vp]
+        L.zkhip_multi_transform_shard.restype = i32; L.zkhip_multi_transform_shard.argtypes = [vp, i32]
+        L.zkhip_multi_last_shard.restype = i32; L.zkhip_multi_last_shard.argtypes = [vp]
         L.zkhip_prove_g16_split_begin.restype = i32; L.zkhip_prove_g16_split_begin.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
         L.zkhip_prove_g16_split_end.restype = i32; L.zkhip_prove_g16_split_end.argtypes = [vp, vp, vp, vp, vp, vp]
         L.zkhip_prove_g16_split_abort.restype = i32; L.zkhip_prove_g16_split_abort.argtypes = [vp]
@@ -964,6 +969,9 @@ class Multi:
             args += [_ptr(rp), _ptr(col), _ptr(val)]
         self._check(self.lib.L.zkhip_multi_r1cs_load(self.h, curve_id, n, l, w, *args))
         self.curve_id, self.m = curve_id, l + w
+        self.domain = 1
+        while self.domain < n + l:
+            self.domain *= 2
 
     def load_proving_key(self, curve_id, pk_bytes, scheme="g16"):
         b = _u8(pk_bytes)
@@ -992,6 +1000,34 @@ class Multi:
 
     def last_split(self):
         return bool(self.lib.L.zkhip_multi_last_split(self.h))
+
+    def transform_shard(self, on=None):
+        """`zkhip_multi_transform_shard`: let proofs over an unbound Groth16 key shard their witness map's domain across the members
+        (None: only report; off by default).  Returns the previous setting."""
+        return bool(self.lib.L.zkhip_multi_transform_shard(self.h, -1 if on is None else int(bool(on))))
+
+    def last_shard(self):
+        """Members the transforms of the last `ntt` / `witness_map` / `prove_*` were sharded over (0: they were not)."""
+        return int(self.lib.L.zkhip_multi_last_shard(self.h))
+
+    def ntt(self, curve_id, data, direction):
+        """`zkhip_multi_ntt`: `Context.ntt` with the domain sharded across the members where the plan allows it."""
+        d = np.array(_u8(data), dtype=np.uint8, copy=True)
+        n = d.size // 32
+        logn = n.bit_length() - 1
+        if n == 0 or (1 << logn) != n:
+            raise ValueError("NTT size must be a power of two")
+        code = {"fft": 0, "ifft": 1, "coset_fft": 2, "coset_ifft": 3}[direction]
+        self._check(self.lib.L.zkhip_multi_ntt(self.h, curve_id, logn, code, _ptr(d)))
+        return d
+
+    def witness_map(self, z):
+        """`zkhip_multi_witness_map` over the loaded constraint system: h as N x 32 bytes, natural order, as
+        `ConstraintSystem.witness_map` returns it."""
+        z = _u8(z, self.m * 32)
+        out = np.zeros(self.domain * 32, dtype=np.uint8)
+        self._check(self.lib.L.zkhip_multi_witness_map(self.h, _ptr(z), _ptr(out)))
+        return out
 
     def prove_g16_batch(self, zs, rss):
         """Independent proofs dealt over the members (`zkhip_prove_g16_multi_batch`): zs = list of host assignments,
