@@ -27,7 +27,8 @@
  *    zkhip_pk_is_bound, zkhip_pk_export_size, zkhip_partial_size, zkhip_combine_*, zkhip_ctx_set_checked(ctx, -1),
  *    zkhip_ctx_unsatisfied, zkhip_setup_*_size, the zkhip_prog_* family).  Every other call on that context or on one of its keys —
  *    the prove calls, zkhip_r1cs_check, a second begin, zkhip_pk_bind_r1cs / _shard / zkhip_pk_unbind, zkhip_ctx_tune,
- *    zkhip_ctx_set_checked(ctx, 0 / 1), key loads, imports and exports, setups, uploads and the primitives (they work in the
+ *    zkhip_ctx_set_checked(ctx, 0 / 1), key loads, imports and exports, setups, uploads (zkhip_assignment_upload, _upload_packed,
+ *    _upload_witness), zkhip_wplan_create (it enqueues the copies of its tables) and the primitives (they work in the
  *    pending proof's buffers and on its streams) — returns ZKHIP_ERR_BAD_ARG with a message that names the pending split proof,
  *    before anything is enqueued, and leaves the pending proof as it is.  Freeing a handle a pending proof uses is the caller's
  *    error, as it is during any call.
@@ -37,7 +38,8 @@
  *    a collect on an empty queue ZKHIP_ERR_BAD_ARG, and neither changes anything; proofs are enqueued exactly as the batch calls enqueue
  *    theirs, slots round-robin, so submit, submit, submit, collect, submit, collect ... is the batch calls' own schedule.  Bytes: every
  *    collected proof is byte-identical to what zkhip_prove_g16 / zkhip_prove_gm17 returns for the same inputs, for any order of calls,
- *    a bound or an unbound key, and each of the three witness sources.  Buffers: z, packed and rnd belong to the caller again as soon as
+ *    a bound or an unbound key, and each of the four witness sources (host z, resident, packed, witness file).  Buffers: z, packed, the
+ *    bytes of a witness file and rnd belong to the caller again as soon as
  *    submit returns (the library copies host memory through its own pinned ring; the measurement switch ZKHIP_COPY_MODE=0, which
  *    hands the caller's pointer to the runtime instead, gives that up); a resident assignment must stay alive until its ticket is
  *    collected.  Failures of ONE proof fail that ticket only
@@ -45,8 +47,10 @@
  *    the message of zkhip_prove_g16), an assignment that does not satisfy the system in checked mode (ZKHIP_ERR_UNSATISFIED at collect,
  *    the output zero-filled, the message names the ticket and the constraint, zkhip_ctx_unsatisfied reports one triple with proof index
  *    0), and a submit refused for its arguments — null or both sources, z[0] != 1, a blinding scalar that is not canonical, an assignment
- *    of another system, a malformed packed buffer (ZKHIP_ERR_PARSE, the messages of zkhip_assignment_upload_packed) — which consumes no
- *    ticket.  Only a device error breaks the queue: it is kept, every ticket still in flight collects with ZKHIP_ERR_DEVICE and its text,
+ *    of another system, a malformed packed buffer (ZKHIP_ERR_PARSE, the messages of zkhip_assignment_upload_packed), a witness file whose
+ *    length does not match its count or a plan of another system (zkhip_queue_submit_witness) — which consumes no
+ *    ticket.  A witness file's own defects, found on the device — a value that is not canonical, an id out of range (ZKHIP_ERR_PARSE), a
+ *    variable without a value (ZKHIP_ERR_UNSATISFIED) — fail their ticket at collect like the others, with the host reader's messages.  Only a device error breaks the queue: it is kept, every ticket still in flight collects with ZKHIP_ERR_DEVICE and its text,
  *    further submits answer the same, and zkhip_queue_close still works.  Pending: an open queue makes its context pending in the sense
  *    of the split-proof paragraph above — every call that paragraph refuses is refused, on the host and before anything is enqueued,
  *    with ZKHIP_ERR_BAD_ARG and a message that names the open queue (zkhip_prove_g16_split_begin and a second zkhip_queue_open among
@@ -54,7 +58,8 @@
  *    (zkhip_prove_g16_split_end finds nothing pending, zkhip_prove_g16_split_abort has nothing to drop).  Checked mode is read when the
  *    queue is opened.  Freeing the key, the constraint system or the context under an open queue is the caller's error.  Resources:
  *    opening, submitting and collecting create no stream and no event beyond the ones the proof slots own, and allocate nothing once
- *    every slot has been used (a packed buffer longer than any before grows the context's one buffer for packed bytes): a process near
+ *    every slot has been used (a packed buffer longer than any before grows the context's one buffer for packed bytes, a witness file
+ *    longer than any before the context's one buffer for file bytes): a process near
  *    the hardware-queue budget of INTEGRATION.md section 4 stays where it is.
  *  - There is no CPU fallback: without a usable gfx950 device zkhip_ctx_create fails with
  *    ZKHIP_ERR_DEVICE.
@@ -75,8 +80,9 @@ extern "C" {
 #define ZKHIP_ERR_NOMEM (-3)        /* host or device allocation failed                            */
 #define ZKHIP_ERR_DEVICE (-4)       /* no GPU, HIP runtime error, kernel launch failure            */
 #define ZKHIP_ERR_UNSATISFIED (-5)  /* the assignment does not satisfy the R1CS: zkhip_r1cs_check, and the single-GPU prove calls of a
-                                     * context in checked mode (zkhip_ctx_set_checked); also zkhip_prog_assignment for a variable
-                                     * the witness file gives no value                                                            */
+                                     * context in checked mode (zkhip_ctx_set_checked); also zkhip_prog_assignment and the device
+                                     * route of a witness file (zkhip_assignment_upload_witness, a ticket of
+                                     * zkhip_queue_submit_witness) for a variable the witness file gives no value                   */
 #define ZKHIP_ERR_BUSY (-6)         /* zkhip_queue_submit*: as many proofs in flight as the queue holds; collect one first        */
 
 /* curve ids; names are zokrates_common::constants (/root/reference/zokrates_common/src/constants.rs:5-9) */
@@ -292,6 +298,53 @@ int32_t zkhip_prog_assignment_packed(const zkhip_prog* prog, const uint8_t* witn
 int32_t zkhip_assignment_upload_packed(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, const uint8_t* packed, size_t len,
                                        zkhip_assignment** out);
 
+/* ---- witness files on the device ----
+ * A prover service is handed ZoKrates `witness` files.  zkhip_prog_assignment turns one into z on one host thread: it tests every
+ * value against r, builds an id -> entry table and gathers m x 32 B into ark order.  The file is fixed-width (u64 count, then
+ * count x (i64 id, 32-byte canonical LE value)) and the program's column order is known once the program is parsed, so the same
+ * work is a table lookup and a gather, and the device can do it beside the previous proof: the file's bytes are copied as they are
+ * (40 B per entry instead of 32 B per variable) and two launches test, order and check them.  Nothing here is a default: the
+ * callers choose the route (DESIGN.md section 3 has the measurement).
+ *
+ * The plan.  zkhip_wplan_create builds, from the program's variable order, two u32 tables — ZoKrates id -> column for ids >= 0 and
+ * for ids < 0, each as long as the largest id the program names, "no column" elsewhere — and uploads them; on the host it keeps where
+ * the public inputs sit in z: the public arguments in argument order, then ~out_0 .. ~out_{R-1}, R = the program's return count
+ * (zkhip_prog_dims [4]), every one an instance column.  It refuses, with ZKHIP_ERR_BAD_ARG and a message that names the reason: an
+ * `r1cs` of another curve, l or w than `prog`; an id that occurs at two columns (the reader's "consumed twice (repeated parameter)"
+ * case); a public argument or an output below R that has no column or is not an instance column; an id at or above
+ * max(2^20, 64 (l + w)) (the reader's range rule refuses it in any file of about the program's size; it would only size the tables).
+ * Callers with such programs keep zkhip_prog_assignment.  The plan is tied to its context and to `r1cs`; it may be freed as soon as
+ * the last call that takes it has returned (proofs in flight keep what they need of it), and freed and made again at will.  It
+ * enqueues copies, so it is refused while a split proof or a queue is pending, like every upload: make it before the queue is opened.
+ *
+ * zkhip_assignment_upload_witness returns an ordinary zkhip_assignment, bit for bit the one
+ * zkhip_assignment_upload(zkhip_prog_assignment(..)) gives, so every *_resident call, zkhip_r1cs_check and the GM17 entry points work
+ * unchanged.  Like zkhip_assignment_upload_packed it waits for its verdict.  inputs_out (may be NULL) receives public_inputs_values,
+ * *n_inputs (may be NULL) = public arguments + R; an inputs_cap below that is ZKHIP_ERR_BAD_ARG before anything is enqueued.  The
+ * host checks the framing first (len >= 8, len == 8 + 40 count, count below 2^32 - 1: ZKHIP_ERR_PARSE with the reader's messages) and
+ * that the plan is this context's (ZKHIP_ERR_BAD_ARG).  The context keeps one device buffer for the file's bytes and one u32 per
+ * variable, as large as the largest file and system it has seen, until zkhip_ctx_free.
+ *
+ * Errors are the host reader's wherever the reader defines them:
+ *   a value >= r in ANY entry        ZKHIP_ERR_PARSE        "non-canonical field element in the witness"
+ *   an id out of range in ANY entry  ZKHIP_ERR_PARSE        "variable id out of range in the witness"  (index — id, or -(id + 1) — at or
+ *                                                           above min(2^31, max(2^20, 64 count)))
+ *   a variable without a value       ZKHIP_ERR_UNSATISFIED  "assignment missing for variable <name>", the variable of the LOWEST missing
+ *                                                           column in the reader's spelling (_k, ~out_k)
+ * A PARSE condition wins over a missing variable.  When a file has both PARSE conditions the message is that of the non-canonical
+ * value, wherever the two entries are (the reader reports whichever comes first in the file).  Of several entries with one id the last
+ * in file order wins, as in the reader; column 0 is 1 whatever the file says about ~one.
+ *
+ * ONE difference from the host reader: entries for variables the system does not have are ignored (they are still tested against r
+ * and the range rule) — negative ids at or above R among them — and the inputs are always the program's public arguments + R outputs,
+ * whereas the reader sizes the outputs by the negative ids the file contains.  On a file the reference wrote for the program the two
+ * agree. */
+typedef struct zkhip_wplan zkhip_wplan;
+int32_t zkhip_wplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r1cs* r1cs, zkhip_wplan** out);
+void zkhip_wplan_free(zkhip_wplan* plan);
+int32_t zkhip_assignment_upload_witness(zkhip_ctx* ctx, const zkhip_wplan* plan, const uint8_t* witness, size_t len,
+                                        uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs, zkhip_assignment** out);
+
 /* Steady-state variant for proofs/sec: `count` assignments (each m x 32 B, contiguous), `count`
  * (r, s) pairs (64 B each) and `count` proof slots (8*sz(Fq)+3 B each).  Same results as `count`
  * calls of zkhip_prove_g16; two proofs are kept in flight, so the latency-bound tail of one proof
@@ -340,18 +393,30 @@ int32_t zkhip_ctx_unsatisfied(const zkhip_ctx* ctx, uint32_t cap, uint32_t* proo
  *   submit_packed : the assignment in the packed form of zkhip_assignment_pack, validated on the host like
  *                   zkhip_assignment_upload_packed and widened on the device into the proof's own buffer; unlike that upload it does not
  *                   wait for the device: whether every 32-byte value is below r is read when the ticket is collected
+ *   submit_witness: the assignment as the bytes of a ZoKrates `witness` file, ordered on the device through `plan` (section "witness files
+ *                   on the device") into the proof's own buffer.  The framing and the plan are checked on the host first (a refusal
+ *                   consumes no ticket); what the device finds — a value >= r, an id out of range, a missing variable — is read when the
+ *                   ticket is collected, with the errors of zkhip_assignment_upload_witness.  No host synchronisation
  *   ready         : never blocks.  *ready = 1 if the OLDEST proof in flight is done on the device (collect will not wait), 0 if it is
  *                   not or the queue is empty
  *   collect       : the oldest proof; blocks until it is done.  *ticket (may be NULL) = its number, proof_out as zkhip_prove_g16,
  *                   timings optional (total_ms: from submit to the end of collect)
+ *   collect_inputs: collect, and the public inputs of a ticket that was submitted as a witness file: inputs_out (may be NULL; inputs_cap
+ *                   elements of 32 B) and *n_inputs = public arguments + return count.  A ticket from another source gives *n_inputs = 0.
+ *                   An inputs_cap that is too small is ZKHIP_ERR_BAD_ARG and spends no ticket.  Plain collect on a witness ticket works and
+ *                   drops the inputs
  *   close         : waits for what is in flight, discards it, frees q.  The context is an ordinary context again. */
 typedef struct zkhip_queue zkhip_queue;
 int32_t zkhip_queue_open(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_queue** out);
 int32_t zkhip_queue_state(const zkhip_queue* q, uint32_t* capacity, uint32_t* in_flight);
 int32_t zkhip_queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* z_resident, const uint8_t* rnd, uint64_t* ticket);
 int32_t zkhip_queue_submit_packed(zkhip_queue* q, const uint8_t* packed, size_t len, const uint8_t* rnd, uint64_t* ticket);
+int32_t zkhip_queue_submit_witness(zkhip_queue* q, const zkhip_wplan* plan, const uint8_t* witness, size_t len, const uint8_t* rnd,
+                                   uint64_t* ticket);
 int32_t zkhip_queue_ready(zkhip_queue* q, int32_t* ready);
 int32_t zkhip_queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, zkhip_timings* timings);
+int32_t zkhip_queue_collect_inputs(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, uint8_t* inputs_out, uint64_t inputs_cap,
+                                   uint64_t* n_inputs, zkhip_timings* timings);
 int32_t zkhip_queue_close(zkhip_queue* q);
 
 /* ---- one proof across several GPUs ----

@@ -121,6 +121,7 @@ class Program {
     int32_t curve() const { return curve_; }
     uint64_t constraints() const { return n_; }
     uint64_t variables() const { return l_ + w_; }
+    uint64_t public_inputs() const { return inputs_; }     // public arguments + return count: the length of a proof's `inputs`
     zkhip_prog* get() const { return prog_; }
     // the ZoKrates names ("~one", "_7", "~out_0": zkhip_prog_variable_order) of the variables in row `row` of A (0), B (1) or C (2),
     // joined by " + " — what a failing constraint index (Hip::check) is worth to the author of the program
@@ -129,7 +130,7 @@ class Program {
   private:
     zkhip_prog* prog_ = nullptr;
     int32_t curve_ = 0;
-    uint64_t n_ = 0, l_ = 0, w_ = 0;
+    uint64_t n_ = 0, l_ = 0, w_ = 0, inputs_ = 0;
 };
 
 // A program's constraint system resident on the GPU (zkhip_prog_r1cs_load).  `Backend::generate_proof` consumes its program
@@ -140,7 +141,9 @@ class System {
   public:
     System() = default;
     ~System();
-    System(System&& o) noexcept : cs_(o.cs_), prog_(o.prog_) { o.cs_ = nullptr; o.prog_ = nullptr; }
+    System(System&& o) noexcept : cs_(o.cs_), prog_(o.prog_), plan_(o.plan_), plan_tried_(o.plan_tried_), plan_why_(std::move(o.plan_why_)) {
+        o.cs_ = nullptr; o.prog_ = nullptr; o.plan_ = nullptr;
+    }
     System& operator=(System&& o) noexcept;
     System(const System&) = delete;
     System& operator=(const System&) = delete;
@@ -151,6 +154,11 @@ class System {
     friend class Hip;
     zkhip_r1cs* cs_ = nullptr;
     const Program* prog_ = nullptr;
+    // the program's column order on the device (zkhip_wplan_create), made the first time a proof wants it (Hip::set_device_witness);
+    // stays null — with the library's reason in plan_why_ — for a program the plan refuses, which keeps the host reader
+    mutable zkhip_wplan* plan_ = nullptr;
+    mutable bool plan_tried_ = false;
+    mutable std::string plan_why_;
 };
 
 // NonUniversalBackend::setup's result (zokrates_proof_systems/src/lib.rs:59-65,113-118): the verification key as the text of
@@ -170,7 +178,9 @@ class Hip;
 // (System, Key) in flight across calls.  submit() reads the witness, draws the blinding scalars from the caller's RNG in the order
 // Hip::prove draws them (so equal seeds give equal proofs, whatever the order of submit and collect) and returns without waiting for
 // the device; collect() returns the OLDEST proof.  It honours Hip::set_compact_witness with prove()'s rule — a witness whose packed form
-// is less than half of the m x 32 B goes to the device packed (zkhip_queue_submit_packed).  While a Queue is open its Hip refuses
+// is less than half of the m x 32 B goes to the device packed (zkhip_queue_submit_packed) — and, where that is off,
+// Hip::set_device_witness as it stood when the queue was opened (zkhip_queue_submit_witness; the inputs then come back with the proof).
+// While a Queue is open its Hip refuses
 // every other proving call (zkhip.h, Conventions); close() — or the destructor — drops what is uncollected.  The Hip, the System and
 // the Key must outlive it.  An Error from collect() concerns that one proof (its ticket is spent); the others stay in flight.
 class Queue {
@@ -188,6 +198,7 @@ class Queue {
     bool ready();                                                                  // would collect() return without waiting?  Never blocks
     Proof collect(uint64_t* ticket = nullptr);
     bool last_witness_packed() const { return last_packed_; }
+    bool last_witness_on_device() const { return last_on_device_; }
     void close();
     explicit operator bool() const { return q_ != nullptr; }
 
@@ -197,8 +208,10 @@ class Queue {
     const Hip* hip_ = nullptr;
     const Program* prog_ = nullptr;
     Scheme scheme_ = Scheme::G16;
-    bool last_packed_ = false;
-    std::vector<std::vector<uint8_t>> inputs_;      // public_inputs_values of the tickets in flight, oldest first
+    bool last_packed_ = false, last_on_device_ = false;
+    zkhip_wplan* plan_ = nullptr;                   // the System's, when the Hip's device-witness setting was on at open_queue and the plan exists
+    std::vector<std::vector<uint8_t>> inputs_;      // public_inputs_values of the tickets in flight, oldest first (empty: the device has them)
+    std::vector<bool> on_device_;                   // which of those tickets were submitted as witness files
 };
 
 // One GPU.  (The reference's backends are unit structs — `pub struct Ark;` — because they own nothing; this one owns a
@@ -258,6 +271,15 @@ class Hip {
     // off by default.  Returns the previous setting; last_witness_packed() says which way the last prove() went.
     bool set_compact_witness(bool on) { const bool was = compact_; compact_ = on; return was; }
     bool last_witness_packed() const { return last_packed_; }
+    // Witness files on the device (zkhip.h "witness files on the device"): prove(System, ..) and Queue::submit hand the file's bytes
+    // to the device, which tests, orders and checks them (zkhip_assignment_upload_witness / zkhip_queue_submit_witness) — no host pass
+    // over the entries.  The System owns the plan, made on first use (a Queue: when it is opened, so set this before open_queue).
+    // Where zkhip_wplan_create refuses the program (a repeated parameter, an output without a column) the host reader is used as
+    // before and last_witness_on_device() says so.  The blinding scalars are drawn in the same order either way: equal seeds give
+    // equal Proofs.  set_compact_witness wins if both are set.  One difference in what is accepted: zkhip.h names it (entries for
+    // variables the program lacks are ignored).  Off by default; returns the previous setting.
+    bool set_device_witness(bool on) { const bool was = device_witness_; device_witness_ = on; return was; }
+    bool last_witness_on_device() const { return last_on_device_; }
     // a long-lived prover fed one witness at a time: a proof queue over a resident system and key (see Queue above)
     Queue open_queue(Scheme scheme, const System& system, const Key& key);
     std::string describe() const;
@@ -266,6 +288,8 @@ class Hip {
     friend class Queue;
     zkhip_ctx* ctx_ = nullptr;
     bool compact_ = false, last_packed_ = false;
+    bool device_witness_ = false, last_on_device_ = false;
+    zkhip_wplan* plan_of(const System& system) const;      // the System's plan, made on first use; null if the program is refused
     void check(int32_t rc) const;
 };
 

@@ -9,6 +9,7 @@ use std::os::raw::c_char;
 #[repr(C)] pub struct zkhip_prog { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_assignment { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_queue { _p: [u8; 0] }
+#[repr(C)] pub struct zkhip_wplan { _p: [u8; 0] }
 /// zkhip_queue_submit*: as many proofs in flight as the queue holds; collect one first
 pub const ZKHIP_ERR_BUSY: i32 = -6;
 /// 16 floats: h2d, matvec, ntt, msm_h, msm_z, finish, total, accum_g1, accum_g2, kernel_ntt, 6 reserved (milliseconds)
@@ -56,6 +57,12 @@ extern "C" {
         cap: u64, packed_len: *mut u64, inputs_out: *mut u8, inputs_cap: u64, n_inputs: *mut u64) -> i32;
     pub fn zkhip_assignment_upload_packed(ctx: *mut zkhip_ctx, r1cs: *const zkhip_r1cs, packed: *const u8, len: usize,
         out: *mut *mut zkhip_assignment) -> i32;
+    // witness files on the device: a program's column order resident (the plan), and the bytes of a `witness` file tested, ordered
+    // and checked there into an ordinary resident assignment — no host pass over the entries; the inputs come back with it
+    pub fn zkhip_wplan_create(ctx: *mut zkhip_ctx, prog: *const zkhip_prog, r1cs: *const zkhip_r1cs, out: *mut *mut zkhip_wplan) -> i32;
+    pub fn zkhip_wplan_free(plan: *mut zkhip_wplan);
+    pub fn zkhip_assignment_upload_witness(ctx: *mut zkhip_ctx, plan: *const zkhip_wplan, witness: *const u8, len: usize,
+        inputs_out: *mut u8, inputs_cap: u64, n_inputs: *mut u64, out: *mut *mut zkhip_assignment) -> i32;
     pub fn zkhip_assignment_free(z: *mut zkhip_assignment);
     pub fn zkhip_prove_g16_resident(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, cs: *const zkhip_r1cs, z: *mut zkhip_assignment,
         r: *const u8, s: *const u8, proof_out: *mut u8, timings: *mut zkhip_timings) -> i32;
@@ -80,8 +87,12 @@ extern "C" {
     pub fn zkhip_queue_state(q: *const zkhip_queue, capacity: *mut u32, in_flight: *mut u32) -> i32;
     pub fn zkhip_queue_submit(q: *mut zkhip_queue, z: *const u8, z_resident: *mut zkhip_assignment, rnd: *const u8, ticket: *mut u64) -> i32;
     pub fn zkhip_queue_submit_packed(q: *mut zkhip_queue, packed: *const u8, len: usize, rnd: *const u8, ticket: *mut u64) -> i32;
+    pub fn zkhip_queue_submit_witness(q: *mut zkhip_queue, plan: *const zkhip_wplan, witness: *const u8, len: usize, rnd: *const u8,
+        ticket: *mut u64) -> i32;
     pub fn zkhip_queue_ready(q: *mut zkhip_queue, ready: *mut i32) -> i32;
     pub fn zkhip_queue_collect(q: *mut zkhip_queue, ticket: *mut u64, proof_out: *mut u8, timings: *mut zkhip_timings) -> i32;
+    pub fn zkhip_queue_collect_inputs(q: *mut zkhip_queue, ticket: *mut u64, proof_out: *mut u8, inputs_out: *mut u8, inputs_cap: u64,
+        n_inputs: *mut u64, timings: *mut zkhip_timings) -> i32;
     pub fn zkhip_queue_close(q: *mut zkhip_queue) -> i32;
     /// a shard of a multi-GPU key (or a whole key, Groth16 or GM17) bound from the key FILE: the transforms need every base once
     pub fn zkhip_pk_bind_r1cs_shard(ctx: *mut zkhip_ctx, pk: *mut zkhip_pk, r1cs: *const zkhip_r1cs, key_bytes: *const u8, len: usize) -> i32;

@@ -26,6 +26,8 @@
 #include "kernels_msm.cuh"
 #include "kernels_ntt.cuh"
 #include "zpack.cuh"
+#include "wingest.cuh"
+#include "wplan.h"
 
 namespace zk {
 
@@ -157,6 +159,12 @@ struct ProofSlot {
     // the proof currently in flight in this slot
     bool busy = false;
     uint8_t r[32], s[32];
+    // a proof whose assignment came as a witness file (WitnessZ): the plan's host tables — they name a missing variable and place the
+    // public inputs when the ticket is collected, and are shared with the plan, so a plan freed in between costs nothing — and the
+    // pinned copy of the head of z (l x 32 B) the inputs are read from.  Null for every other source
+    std::shared_ptr<const WPlanTables> wit;
+    void* h_inputs = nullptr;
+    size_t h_inputs_cap = 0;
     std::chrono::steady_clock::time_point t_start;
 };
 // an assignment in the packed form of zkhip_assignment_pack, validated on the host (assignment_packed_validate): where its sections start
@@ -164,6 +172,15 @@ struct PackedZ {
     const uint8_t* bytes;
     size_t len;
     u64 tags_off, index_off, payload_off;
+};
+// an assignment as the bytes of a ZoKrates `witness` file whose framing the host has checked (witness_header_validate: `count`
+// entries), to be ordered by the tables of `plan` on the device (wingest.cuh)
+struct zkhip_wplan;
+struct WitnessZ {
+    const uint8_t* bytes;
+    size_t len;
+    u64 count;
+    const zkhip_wplan* plan;
 };
 // zkhip_queue: the loop of Prover::run_batch — "enqueue i, finish i - (NS - 1)" — with the CALLER as the loop (zkhip_api.hip).  Ticket t
 // is in flight in slot t % cap, the slot run_batch gives proof t; head .. next - 1 are in flight, so a submit finds its slot free
@@ -231,6 +248,7 @@ struct zkhip_ctx {
     ProofSlot* cur = &slots[0];   // the slot the primitives (ntt, msm, ...) and the next enqueue work in
     zkhip_queue* queue = nullptr; // the open proof queue of this context (zkhip_queue_open .. zkhip_queue_close): the context is pending
     DBuf tmp;
+    DBuf wraw, wowner;        // the bytes of the witness file being ordered and the entry that owns each column (Prover::ingest_z); kept between calls
     DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed, zkhip_queue_submit_packed); kept between calls
     std::vector<std::unique_ptr<NttPlanBase>> plans;
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
@@ -1045,6 +1063,15 @@ struct zkhip_assignment {
     zkhip_ctx* ctx;
     u64 m;
     DBuf scalars;
+};
+
+// zkhip_wplan: the column order of one program, resident — the two id -> column tables of wplan.h on the device, what the host needs
+// of them (shared with the proof slots that hold a proof made through the plan), and which system it was made for
+struct zkhip_wplan {
+    zkhip_ctx* ctx = nullptr;
+    u64 cs_uid = 0;
+    std::shared_ptr<const WPlanTables> host;
+    DBuf pos, neg;
 };
 
 namespace zk {
@@ -1982,13 +2009,74 @@ struct Prover {
         ZK_LAUNCH((k_unpack_assignment<Fr>), dim3(blocks_for(m, ZPACK_BLOCK_ELEMS)), dim3(256), 0, s, d + zp.tags_off, (const u64*)(d + zp.index_off),
                   d + zp.payload_off, ptr<Fr>(dst), m, ptr<u32>(flag));
     }
+    // the same from the bytes of a witness file (framing checked on the host: witness_header_validate) into a buffer of `cap` entries:
+    // one copy of the file into the context's buffer, k_witness_claim over its entries, k_witness_gather over the columns.  `flag`
+    // becomes 16 bytes: the verdict word (bit 0 is never set on this route: every value is tested where it is claimed), a pad, and
+    // the lowest missing column as a u64.
+    // ctx->wraw and ctx->wowner stay ONE buffer each however many witness proofs are in flight, by the argument of ctx->zpack: the
+    // copy in, the clearing of `owner`, the two launches and the next proof's copy in are all enqueued on ctx->stream, so the gather
+    // has read the bytes and the owners of proof t before the copy and the memset of proof t + 1 overwrite them, and nothing else
+    // ever reads either (every later stage works from the slot's scalars; the slot's verdict words and its pinned head of z are its
+    // own).  Growing one frees the old buffer, which waits for the device: a longer file than any before costs that once.
+    // `owner` is cleared by a memset per ingest rather than tagged with a generation number: a tag would take bits from the 32 that
+    // hold entry + 1 (a file may have 2^32 - 2 entries), and the memset is m x 4 bytes beside a copy of 40 bytes per entry.
+    static void ingest_z(zkhip_ctx* ctx, DBuf& dst, u64 m, u64 cap, const WitnessZ& wz, DBuf& flag) {
+        Stream s = ctx->stream;
+        const zkhip_wplan* plan = wz.plan;
+        const u64 slots = (wz.len + 15) / 16;
+        dst.ensure(cap * 32);
+        ctx->wraw.ensure(slots * 16);
+        ctx->wowner.ensure(m * 4);
+        dev_h2d(ctx->wraw.p, wz.bytes, wz.len, s);
+        dev_memset(ctx->wowner.p, 0, m * 4, s);
+        flag.ensure(16);
+        dev_memset(flag.p, 0, 8, s);
+        dev_memset((uint8_t*)flag.p + 8, 0xff, 8, s);
+        ZK_LAUNCH((k_witness_claim<Fr>), dim3(blocks_for(wz.count, WIT_BLOCK)), dim3(WIT_BLOCK), 0, s, ptr<uint4>(ctx->wraw), slots, wz.count, ptr<u32>(plan->pos),
+                  (u64)plan->host->pos.size(), ptr<u32>(plan->neg), (u64)plan->host->neg.size(), witness_id_bound(wz.count), ptr<u32>(ctx->wowner), ptr<u32>(flag));
+        ZK_LAUNCH((k_witness_gather<Fr>), dim3(blocks_for(m, WIT_BLOCK)), dim3(WIT_BLOCK), 0, s, ptr<uint8_t>(ctx->wraw), ptr<u32>(ctx->wowner), ptr<Fr>(dst), m,
+                  ptr<u32>(flag), (unsigned long long*)((uint8_t*)flag.p + 8));
+    }
+    // what the verdict words of a slot say (flag, lowest missing column): the host reader's errors for a witness file, the message of
+    // zkhip_prove_g16 for an entry of a host or packed assignment that is not canonical.  A PARSE condition wins over a missing variable
+    static void require_verdict(u32 flag, u32 low, const WPlanTables* wit) {
+        require(!(flag & WIT_FLAG_NON_CANONICAL), ZKHIP_ERR_PARSE, "non-canonical field element in the witness");
+        require(!(flag & WIT_FLAG_ID_RANGE), ZKHIP_ERR_PARSE, "variable id out of range in the witness");
+        if (flag & WIT_FLAG_MISSING) {
+            const std::string name = wit && low < wit->order.size() ? witness_var_name(wit->order[low]) : "column " + std::to_string(low);
+            throw ApiError{ZKHIP_ERR_UNSATISFIED, "assignment missing for variable " + name};
+        }
+        require_canonical(flag);
+    }
+    static void require_verdict(const ProofSlot& sl, const Lay& ly) {
+        u32 low = 0;
+        memcpy(&low, ly.zflag(sl) + 4, 4);
+        require_verdict(ly.zflag_word(sl), low, sl.wit.get());
+    }
     // the assignment into the slot, from host memory or from a resident one (checked when it was uploaded: a clean zflag word), and
     // the verdict of a checked proof reset behind it.  Returns where it is: a resident one stays where it was if the caller only
     // reads it (`in_place`; the provers append to theirs)
     // (`zp`: the assignment comes packed — zkhip_queue_submit_packed — and is widened into the slot; its verdict word is the slot's)
+    // (`wz`: the assignment comes as a witness file — zkhip_queue_submit_witness — and is ordered into the slot; its verdict words are
+    // the slot's, and the head of z, where the public inputs are, is copied to the slot's pinned buffer on the stream that wrote it)
     static const Fr* stage_z(zkhip_ctx* ctx, ProofSlot& sl, u64 m, u64 cap, const uint8_t* z_host, const void* z_dev, bool checked, bool in_place = false,
-                             const PackedZ* zp = nullptr) {
+                             const PackedZ* zp = nullptr, const WitnessZ* wz = nullptr) {
         Stream st = ctx->stream;
+        sl.wit.reset();
+        if (wz) {
+            const u64 l = wz->plan->host->l;
+            if (sl.h_inputs_cap < l * 32) {
+                host_free_pinned(sl.h_inputs);
+                sl.h_inputs = nullptr; sl.h_inputs_cap = 0;
+                sl.h_inputs = host_alloc_pinned(l * 32);
+                sl.h_inputs_cap = l * 32;
+            }
+            ingest_z(ctx, sl.scalars, m, cap, *wz, sl.zflag);
+            dev_d2h_pinned(sl.h_inputs, sl.scalars.p, l * 32, st);
+            sl.wit = wz->plan->host;
+            if (checked) verdict_reset(sl, st);
+            return ptr<Fr>(sl.scalars);
+        }
         if (zp) {
             unpack_z(ctx, sl.scalars, m, cap, *zp, sl.zflag);
             if (checked) verdict_reset(sl, st);
@@ -2027,8 +2115,9 @@ struct Prover {
     // z_dev != nullptr: the assignment is already in HBM (copied device-to-device into the slot); else z is a host buffer
     // `lone`: nothing else of this context is in flight beside this proof (the single-proof entry points; a batch pipelines)
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
-                        const uint8_t* r, const uint8_t* s_, bool lone = false, int check_idx = -1, const PackedZ* zp = nullptr) {
-        enqueue_head(ctx, sl, pk, cs, z_host, z_dev, r, s_, lone, -1, check_idx, zp);
+                        const uint8_t* r, const uint8_t* s_, bool lone = false, int check_idx = -1, const PackedZ* zp = nullptr,
+                        const WitnessZ* wz = nullptr) {
+        enqueue_head(ctx, sl, pk, cs, z_host, z_dev, r, s_, lone, -1, check_idx, zp, wz);
         enqueue_tail(ctx, sl, pk, cs);
     }
     // whether a proof over (pk, cs) may be split between members: a bound key (its proof needs a and b on the coset and nothing else
@@ -2053,7 +2142,8 @@ struct Prover {
     // (0: a, 1: b) of a bound key's, after which sl.half_ready is recorded and the caller brings the other vector into
     // sl.va + (1 - half) * N before enqueue_tail
     static void enqueue_head(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
-                             const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1, const PackedZ* zp = nullptr) {
+                             const uint8_t* r, const uint8_t* s_, bool lone, int half, int check_idx = -1, const PackedZ* zp = nullptr,
+                             const WitnessZ* wz = nullptr) {
         PkLoader<C>::check_match(pk, cs, 0);
         const bool bound = is_bound(pk, cs);
         require(half < 0 || (bound && half <= 1), ZKHIP_ERR_BAD_ARG, "internal: only a proof over a bound key splits its witness map");
@@ -2066,7 +2156,7 @@ struct Prover {
         memcpy(sl.r, r, 32);
         memcpy(sl.s, s_, 32);
         Stream st = ctx->stream;
-        stage_z(ctx, sl, pk->m, pk->m + 2, z_host, z_dev, sl.check_idx >= 0, false, zp);
+        stage_z(ctx, sl, pk->m, pk->m + 2, z_host, z_dev, sl.check_idx >= 0, false, zp, wz);
         stage_scalars(ctx, pl, sl.scalars.p, pk->m, r, s_);
         event_record(sl.ev[0], st);
 
@@ -2211,6 +2301,7 @@ struct Prover {
         for (int k = 0; k < ZK_NLANES; ++k) stream_wait_event(so, sl.lanes[k].done);
         sl.zflag.ensure(4);
         dev_d2h_pinned(ly.zflag(sl), sl.zflag.p, 4, so);   // written on the main stream before ev[0], which every lane waits for
+        if (sl.wit) dev_d2h_pinned(ly.zflag(sl) + 4, (const uint8_t*)sl.zflag.p + 8, 4, so);   // (a witness file: the lowest missing column — below 2^32 — beside it)
         if (sl.check_idx >= 0) {
             stream_wait_event(so, sl.ev[2]);      // "h ready": recorded behind the check on the stream of the witness map
             dev_d2h_pinned(ly.verdict(sl), sl.verdict.p, 16, so);
@@ -2250,7 +2341,7 @@ struct Prover {
         sl.busy = false;
         split_clear(sl);
         const Lay ly(ctx, pk);
-        require_canonical(ly.zflag_word(sl));
+        require_verdict(sl, ly);
         // five independent Horner chains (W x c doublings each): one host thread per MSM, the G2 chain on this one
         Sums g;
         HostThreads th;
@@ -2350,7 +2441,7 @@ struct Prover {
             throw;
         }
         sl.busy = false;
-        require_canonical(ly.zflag_word(sl));
+        require_verdict(sl, ly);
         if (unsatisfied(ctx, sl, ly)) memset(out, 0, PROOF_BYTES);      // a refused proof: all zero
         else assemble_tail(g, sA, rB1, rsD, out);
         fill_timings(sl, tm, t_fin);
@@ -2643,6 +2734,19 @@ struct Prover {
         dev_d2h(&verdict, flag.p, 4, s);
         stream_sync(s);
         require_canonical(verdict);
+    }
+
+    // the same resident assignment from the bytes of a witness file (framing checked on the host: zkhip_api.hip), waiting for its verdict;
+    // `head` (l x 32 B, may be null) receives the head of z, where the public inputs are
+    static void assignment_upload_witness(zkhip_ctx* ctx, zkhip_assignment* a, const WitnessZ& wz, uint8_t* head) {
+        Stream s = ctx->stream;
+        DBuf flag;
+        ingest_z(ctx, a->scalars, a->m, a->m + 2, wz, flag);
+        u32 verdict[4] = {0, 0, 0, 0};
+        dev_d2h(verdict, flag.p, 16, s);
+        if (head) dev_d2h(head, a->scalars.p, wz.plan->host->l * 32, s);
+        stream_sync(s);
+        require_verdict(verdict[0], verdict[2], wz.plan->host.get());
     }
 
     // generic MSM primitive (bases in ark encoding)
@@ -2958,6 +3062,7 @@ struct CurveOps {
     void (*record_from_sums)(zkhip_ctx*, const zkhip_pk*, const uint8_t*, const uint8_t*, uint8_t*);
     void (*assignment_upload)(zkhip_ctx*, zkhip_assignment*, const uint8_t*);
     void (*assignment_upload_packed)(zkhip_ctx*, zkhip_assignment*, const uint8_t*, size_t, u64, u64, u64);
+    void (*assignment_upload_witness)(zkhip_ctx*, zkhip_assignment*, const WitnessZ&, uint8_t* head);
     void (*r1cs_check)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const void*, u64 out[2]);
     void (*ntt)(zkhip_ctx*, u32, int, uint8_t*);
     void (*witness_map)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, uint8_t*);
@@ -2986,8 +3091,8 @@ struct CurveOps {
     void (*gm17_combine)(const zkhip_pk*, u32, const uint8_t*, const uint8_t*, uint8_t*);
     // the proof queue (gm17.cuh QueueOps): either scheme, the key's
     void (*queue_check)(const zkhip_pk*, const zkhip_r1cs*);
-    void (*queue_enqueue)(zkhip_ctx*, ProofSlot&, const zkhip_pk*, const zkhip_r1cs*, const uint8_t* z_host, const void* z_dev, const PackedZ*, const uint8_t* rnd,
-                          bool checked);
+    void (*queue_enqueue)(zkhip_ctx*, ProofSlot&, const zkhip_pk*, const zkhip_r1cs*, const uint8_t* z_host, const void* z_dev, const PackedZ*, const WitnessZ*,
+                          const uint8_t* rnd, bool checked);
     void (*queue_finish)(zkhip_ctx*, ProofSlot&, const zkhip_pk*, uint8_t*, zkhip_timings*);
 };
 // fields of zkhip_field_op: 0 Fr, 1 Fq, 2 Fq2 in the saturated form; 3 Fq2, 4 Fr, 5 Fq in the unsaturated limbs of the MSM kernels
@@ -3037,6 +3142,7 @@ static CurveOps make_curve_ops() {
     o.record_from_sums = &Prover<C>::record_from_sums;
     o.assignment_upload = &Prover<C>::assignment_upload;
     o.assignment_upload_packed = &Prover<C>::assignment_upload_packed;
+    o.assignment_upload_witness = &Prover<C>::assignment_upload_witness;
     o.r1cs_check = &Prover<C>::r1cs_check;
     o.ntt = &Prover<C>::ntt_api;
     o.witness_map = &Prover<C>::witness_map_api;

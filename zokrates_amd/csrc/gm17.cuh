@@ -117,7 +117,7 @@ struct Gm17 {
     // SAP rows and the extension of the assignment on the main stream (they feed the z sort), the quotient's transforms on the
     // context's NTT stream behind them
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev,
-                        const uint8_t* d1, const uint8_t* r, int check_idx = -1, const PackedZ* zp = nullptr) {
+                        const uint8_t* d1, const uint8_t* r, int check_idx = -1, const PackedZ* zp = nullptr, const WitnessZ* wz = nullptr) {
         L::check_match(pk, cs, 1);
         const u64 m = cs->l + cs->w, n = cs->n, l = cs->l, M = pk->m, D = pk->N;
         Fr dd = fe_from_bytes_canon<Fr>(d1), rr = fe_from_bytes_canon<Fr>(r);
@@ -129,7 +129,7 @@ struct Gm17 {
         memcpy(sl.r, rho.v, 32);
         memset(sl.s, 0, 32);
         Stream st = ctx->stream;
-        P::stage_z(ctx, sl, m, M + 2, z_host, z_dev, check_idx >= 0, false, zp);
+        P::stage_z(ctx, sl, m, M + 2, z_host, z_dev, check_idx >= 0, false, zp, wz);
         uint8_t* d_scalars = (uint8_t*)sl.scalars.p;
         sl.zmont.ensure(m * 32);
         dev_h2d(d_scalars + M * 32, sl.r, 32, st);
@@ -384,13 +384,13 @@ struct QueueOps {
     typedef Gm17<C> G;
     static void check(const zkhip_pk* pk, const zkhip_r1cs* cs) { PkLoader<C>::check_match(pk, cs, pk->scheme); }
     static void enqueue(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, const PackedZ* zp,
-                        const uint8_t* rnd, bool checked) {
+                        const WitnessZ* wz, const uint8_t* rnd, bool checked) {
         const int idx = checked ? 0 : -1;
         if (pk->scheme == 0) {
-            P::enqueue(ctx, sl, pk, cs, z_host, z_dev, rnd, rnd + 32, false, idx, zp);
+            P::enqueue(ctx, sl, pk, cs, z_host, z_dev, rnd, rnd + 32, false, idx, zp, wz);
         } else {
             G::check_d2(rnd);
-            G::enqueue(ctx, sl, pk, cs, z_host, z_dev, rnd, rnd + 64, idx, zp);
+            G::enqueue(ctx, sl, pk, cs, z_host, z_dev, rnd, rnd + 64, idx, zp, wz);
         }
     }
     static void finish(zkhip_ctx* ctx, ProofSlot& sl, const zkhip_pk* pk, uint8_t* out, zkhip_timings* tm) {

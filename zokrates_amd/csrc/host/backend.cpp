@@ -204,6 +204,7 @@ Program::Program(const uint8_t* bytes, size_t len) {
     uint64_t d[8];
     zkhip_prog_dims(prog_, d);
     curve_ = (int32_t)d[0]; n_ = d[1]; l_ = d[2]; w_ = d[3];
+    inputs_ = d[4] + d[5];
 }
 Program::~Program() { if (prog_) zkhip_prog_free(prog_); }
 std::string Program::row_variables(int32_t which, uint64_t row) const {
@@ -282,14 +283,32 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 }
 }  // namespace
 
-System::~System() { if (cs_) zkhip_r1cs_free(cs_); }
+System::~System() {
+    if (plan_) zkhip_wplan_free(plan_);
+    if (cs_) zkhip_r1cs_free(cs_);
+}
 System& System::operator=(System&& o) noexcept {
     if (this != &o) {
+        if (plan_) zkhip_wplan_free(plan_);
         if (cs_) zkhip_r1cs_free(cs_);
-        cs_ = o.cs_; prog_ = o.prog_;
-        o.cs_ = nullptr; o.prog_ = nullptr;
+        cs_ = o.cs_; prog_ = o.prog_; plan_ = o.plan_; plan_tried_ = o.plan_tried_; plan_why_ = std::move(o.plan_why_);
+        o.cs_ = nullptr; o.prog_ = nullptr; o.plan_ = nullptr;
     }
     return *this;
+}
+// the System's plan, made on first use.  ZKHIP_ERR_BAD_ARG from zkhip_wplan_create is the library refusing the PROGRAM (or a pending
+// context: then nothing is remembered and the next call tries again); anything else is an error like any other
+zkhip_wplan* Hip::plan_of(const System& system) const {
+    if (system.plan_ || system.plan_tried_) return system.plan_;
+    const int32_t rc = zkhip_wplan_create(ctx_, system.program().get(), system.get(), &system.plan_);
+    if (rc == ZKHIP_ERR_BAD_ARG) {
+        system.plan_why_ = zkhip_last_error(ctx_);
+        system.plan_tried_ = system.plan_why_.find("pending") == std::string::npos && system.plan_why_.find("queue is open") == std::string::npos;
+        return nullptr;
+    }
+    check(rc);
+    system.plan_tried_ = true;
+    return system.plan_;
 }
 System Hip::load_system(const Program& program) {
     System s;
@@ -391,7 +410,20 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     // (1) the assignment and the public inputs
     auto t0 = std::chrono::steady_clock::now();
     last_packed_ = false;
-    WitnessBytes w = read_witness(program, witness, witness_len, compact_);
+    last_on_device_ = false;
+    struct Resident {      // the witness on the device before the proof: widened from the packed form, or ordered from the file's bytes
+        zkhip_assignment* a = nullptr;
+        ~Resident() { if (a) zkhip_assignment_free(a); }
+    } resident;
+    zkhip_wplan* plan = device_witness_ && !compact_ ? plan_of(system) : nullptr;
+    WitnessBytes w;
+    if (plan) {
+        w.inputs.resize(program.public_inputs() * 32);
+        check(zkhip_assignment_upload_witness(ctx_, plan, witness, witness_len, w.inputs.data(), program.public_inputs(), &w.n_inputs, &resident.a));
+        last_on_device_ = true;
+    } else {
+        w = read_witness(program, witness, witness_len, compact_);
+    }
     last_packed_ = w.use_packed;
     if (tm) tm->witness_to_assignment = ms_since(t0);
     // (2) the constraint system: resident
@@ -400,19 +432,15 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     // (3) the blinding scalars; (4) the GPU
     t0 = std::chrono::steady_clock::now();
     std::vector<uint8_t> raw(8 * fq + 3);
-    struct Resident {      // the packed witness widened on the device (zkhip_assignment_upload_packed)
-        zkhip_assignment* a = nullptr;
-        ~Resident() { if (a) zkhip_assignment_free(a); }
-    } resident;
     if (last_packed_) check(zkhip_assignment_upload_packed(ctx_, cs, w.packed.data(), w.packed_len, &resident.a));
     uint8_t rnd[96];
     draw_rnd(scheme, curve, rng, rnd);
     int32_t rc;
     if (scheme == Scheme::GM17) {
-        rc = last_packed_ ? zkhip_prove_gm17_resident(ctx_, key.get(), cs, resident.a, rnd, raw.data(), nullptr)
+        rc = resident.a ? zkhip_prove_gm17_resident(ctx_, key.get(), cs, resident.a, rnd, raw.data(), nullptr)
                           : zkhip_prove_gm17(ctx_, key.get(), cs, w.z.data(), rnd, raw.data(), nullptr);
     } else {
-        rc = last_packed_ ? zkhip_prove_g16_resident(ctx_, key.get(), cs, resident.a, rnd, rnd + 32, raw.data(), nullptr)
+        rc = resident.a ? zkhip_prove_g16_resident(ctx_, key.get(), cs, resident.a, rnd, rnd + 32, raw.data(), nullptr)
                           : zkhip_prove_g16(ctx_, key.get(), cs, w.z.data(), rnd, rnd + 32, raw.data(), nullptr);
     }
     check(rc);
@@ -423,6 +451,7 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
 // ------------------------------------------------------------------ the proof queue (zkhip.h "proof queue")
 Queue Hip::open_queue(Scheme scheme, const System& system, const Key& key) {
     Queue q;
+    q.plan_ = device_witness_ ? plan_of(system) : nullptr;      // (before the queue is open: the plan's tables are copied in)
     check(zkhip_queue_open(ctx_, key.get(), system.get(), &q.q_));
     q.hip_ = this;
     q.prog_ = &system.program();
@@ -430,12 +459,16 @@ Queue Hip::open_queue(Scheme scheme, const System& system, const Key& key) {
     return q;
 }
 Queue::~Queue() { close(); }
-Queue::Queue(Queue&& o) noexcept : q_(o.q_), hip_(o.hip_), prog_(o.prog_), scheme_(o.scheme_), last_packed_(o.last_packed_), inputs_(std::move(o.inputs_)) { o.q_ = nullptr; }
+Queue::Queue(Queue&& o) noexcept
+    : q_(o.q_), hip_(o.hip_), prog_(o.prog_), scheme_(o.scheme_), last_packed_(o.last_packed_), last_on_device_(o.last_on_device_), plan_(o.plan_),
+      inputs_(std::move(o.inputs_)), on_device_(std::move(o.on_device_)) { o.q_ = nullptr; }
 Queue& Queue::operator=(Queue&& o) noexcept {
     if (this != &o) {
         close();
         q_ = o.q_; hip_ = o.hip_; prog_ = o.prog_; scheme_ = o.scheme_; last_packed_ = o.last_packed_;
+        last_on_device_ = o.last_on_device_; plan_ = o.plan_;
         inputs_ = std::move(o.inputs_);
+        on_device_ = std::move(o.on_device_);
         o.q_ = nullptr;
     }
     return *this;
@@ -444,6 +477,7 @@ void Queue::close() {
     if (q_) zkhip_queue_close(q_);
     q_ = nullptr;
     inputs_.clear();
+    on_device_.clear();
 }
 uint32_t Queue::capacity() const {
     uint32_t cap = 0;
@@ -459,15 +493,26 @@ uint64_t Queue::submit(const uint8_t* witness, size_t witness_len, StdRng& rng) 
     if (!q_) throw Error(ZKHIP_ERR_BAD_ARG, "the queue is closed");
     if (full()) throw Error(ZKHIP_ERR_BUSY, "the proof queue is full: collect a proof first");      // (before the RNG is touched)
     const int32_t curve = prog_->curve();
-    WitnessBytes w = read_witness(*prog_, witness, witness_len, hip_->compact_);
     uint8_t rnd[96];
-    draw_rnd(scheme_, curve, rng, rnd);
     uint64_t ticket = 0;
+    if (plan_ && !hip_->compact_) {      // the file's bytes as they are: the device tests, orders and checks them, and returns the inputs
+        draw_rnd(scheme_, curve, rng, rnd);
+        hip_->check(zkhip_queue_submit_witness(q_, plan_, witness, witness_len, rnd, &ticket));
+        last_packed_ = false;
+        last_on_device_ = true;
+        inputs_.emplace_back();
+        on_device_.push_back(true);
+        return ticket;
+    }
+    WitnessBytes w = read_witness(*prog_, witness, witness_len, hip_->compact_);
+    draw_rnd(scheme_, curve, rng, rnd);
     // the buffers are the library's copies when the call returns: `w` may go
     hip_->check(w.use_packed ? zkhip_queue_submit_packed(q_, w.packed.data(), w.packed_len, rnd, &ticket) : zkhip_queue_submit(q_, w.z.data(), nullptr, rnd, &ticket));
     last_packed_ = w.use_packed;
+    last_on_device_ = false;
     w.inputs.resize(w.n_inputs * 32);
     inputs_.push_back(std::move(w.inputs));
+    on_device_.push_back(false);
     return ticket;
 }
 bool Queue::ready() {
@@ -482,13 +527,22 @@ Proof Queue::collect(uint64_t* ticket) {
     std::vector<uint8_t> raw(8 * (curve == ZKHIP_CURVE_BN128 ? 32 : 48) + 3);
     uint64_t t = 0;
     const bool had = in_flight() > 0;
-    const int32_t rc = zkhip_queue_collect(q_, &t, raw.data(), nullptr);
+    const bool device = had && !on_device_.empty() && on_device_.front();
+    std::vector<uint8_t> from_device(device ? prog_->public_inputs() * 32 : 0);
+    uint64_t n_device = 0;
+    const int32_t rc = device ? zkhip_queue_collect_inputs(q_, &t, raw.data(), from_device.data(), prog_->public_inputs(), &n_device, nullptr)
+                              : zkhip_queue_collect(q_, &t, raw.data(), nullptr);
     std::vector<uint8_t> inputs;
     if (had && !inputs_.empty()) {      // (its ticket is spent whether the proof came out or not)
         inputs = std::move(inputs_.front());
         inputs_.erase(inputs_.begin());
+        on_device_.erase(on_device_.begin());
     }
     hip_->check(rc);
+    if (device) {
+        from_device.resize(n_device * 32);
+        inputs = std::move(from_device);
+    }
     if (ticket) *ticket = t;
     return proof_from_raw(scheme_, curve, raw, inputs.data(), inputs.size() / 32);
 }

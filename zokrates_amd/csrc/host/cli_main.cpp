@@ -1,7 +1,7 @@
 // zkhip-cli — `zokrates generate-proof` for the hip backend, as a native executable over zkhip_backend.hpp.
 //
 //   zkhip-cli generate-proof -i out -w witness -p proving.key -j proof.json [-s g16|gm17] [--entropy TEXT]
-//                            [--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--compact-witness]
+//                            [--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--compact-witness] [--device-witness]
 //
 // Mirrors /root/reference/zokrates_cli/src/ops/generate_proof.rs:95-202: the compiled program (`out`), the witness and the
 // proving key are read from files, the proof is written as JSON, one proof per process; `--entropy` seeds the RNG as
@@ -70,7 +70,7 @@ std::pair<int, int> cpu_and_node() {
 }
 int usage() {
     fprintf(stderr, "usage: zkhip-cli generate-proof -i <out> -w <witness> -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] "
-                    "[--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--compact-witness] [--full-tables]\n"
+                    "[--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--compact-witness] [--device-witness] [--full-tables]\n"
                     "       zkhip-cli setup -i <out> -p <proving.key> -v <verification.key> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
                     "       zkhip-cli verify [-v <verification.key>] [-j <proof.json>]\n"
                     "       zkhip-cli print-proof [-j <proof.json>] [-f remix|json]\n");
@@ -192,7 +192,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && strcmp(argv[1], "pairing-check") == 0) return cmd_pairing_check(argc, argv);
     if (argc < 2 || strcmp(argv[1], "generate-proof") != 0) return usage();
     std::string input = "out", witness_path = "witness", pk_path = "proving.key", proof_path = "proof.json", scheme_s = "g16", entropy, cache_dir;
-    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false;
+    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false, device_witness = false;
     int device = 0;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
@@ -201,6 +201,7 @@ int main(int argc, char** argv) {
         else if (a == "--verify") self_check = true;
         else if (a == "--check") check_first = true;                 // the witness against the constraints, on the device, before proving
         else if (a == "--compact-witness") compact = true;           // the witness packed on the host and widened on the device when that halves it
+        else if (a == "--device-witness") device_witness = true;     // the witness file's bytes tested, ordered and checked on the device (the same proof.json)
         else if (a == "--full-tables") resident_tables = true;      // (measurement: build the window-multiple tables a resident prover uses)
         else if (a == "-w" || a == "--witness") witness_path = val();
         else if (a == "-p" || a == "--proving-key-path") pk_path = val();
@@ -281,6 +282,7 @@ int main(int argc, char** argv) {
         Hip hip(device);
         if (!resident_tables) hip.one_shot();          // one proof, then the process ends: no window-multiple tables
         hip.set_compact_witness(compact);
+        hip.set_device_witness(device_witness);
         const double ms_init = ms_since(t0);
         t0 = std::chrono::steady_clock::now();
         key_reader.join();
@@ -373,6 +375,8 @@ int main(int argc, char** argv) {
             printf("verified against the verification key of %s\n", pk_path.c_str());
         }
         if (compact) printf("compact witness: %s\n", hip.last_witness_packed() ? "uploaded packed" : "dense, uploaded plain");
+        if (device_witness)
+            printf("device witness: %s\n", hip.last_witness_on_device() ? "read on the device" : compact ? "off (--compact-witness wins)" : "read on the host (the program has no plan)");
         printf("generate-proof (%s): wrote %s\n", scheme_s.c_str(), proof_path.c_str());
         const std::pair<int, int> where = cpu_and_node();
         if (timings)

@@ -189,10 +189,25 @@ static int32_t queue_guarded(zkhip_queue* q, Fn&& fn) {
         return broke("unexpected internal error", ZKHIP_ERR_DEVICE);
     }
 }
-// what the three witness sources share: the state first (broken, full), then the source's own checks — all on the host —, then the
+// a witness file and its plan, checked on the host before anything is enqueued: the framing with the reader's messages (ZKHIP_ERR_PARSE),
+// the plan against the context and — where the caller has one — the constraint system
+static WitnessZ witness_source(zkhip_ctx* ctx, const zkhip_wplan* plan, const zkhip_r1cs* cs, const uint8_t* witness, size_t len) {
+    require(plan && witness, ZKHIP_ERR_BAD_ARG, "null argument");
+    require(plan->ctx == ctx, ZKHIP_ERR_BAD_ARG, "the witness plan belongs to another context");
+    if (cs)
+        require(plan->cs_uid == cs->uid, ZKHIP_ERR_BAD_ARG, "the witness plan was made for another constraint system (zkhip_wplan_create)");
+    uint64_t count = 0;
+    try {
+        count = witness_header_validate(witness, len);
+    } catch (const IngestError& e) {
+        throw ApiError{e.code, e.msg};
+    }
+    return WitnessZ{witness, len, count, plan};
+}
+// what the four witness sources share: the state first (broken, full), then the source's own checks — all on the host —, then the
 // proof enqueued into the slot of the next ticket exactly as a batch call enqueues its proof of that index
 static int32_t queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* z_resident, const uint8_t* packed, size_t len, bool is_packed, const uint8_t* rnd,
-                            uint64_t* ticket) {
+                            uint64_t* ticket, const zkhip_wplan* plan = nullptr, bool is_witness = false) {
     if (!q || !q->ctx) return ZKHIP_ERR_BAD_ARG;
     zkhip_ctx* ctx = q->ctx;
     if (q->broken) { ctx->err = q->dev_err; return ZKHIP_ERR_DEVICE; }
@@ -204,7 +219,10 @@ static int32_t queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* 
         const zkhip_r1cs* cs = q->cs;
         require(rnd != nullptr, ZKHIP_ERR_BAD_ARG, "null argument");
         PackedZ zp{};
-        if (is_packed) {
+        WitnessZ wz{};
+        if (is_witness) {
+            wz = witness_source(ctx, plan, cs, packed, len);
+        } else if (is_packed) {
             require(packed != nullptr, ZKHIP_ERR_BAD_ARG, "null argument");
             // the whole structure on the host, before anything is enqueued (as zkhip_assignment_upload_packed): the kernel never sees an inconsistent buffer
             PackedLayout ly;
@@ -224,7 +242,7 @@ static int32_t queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* 
                         "assignment does not match the constraint system");
         }
         ops_for(q->pk->curve)->queue_enqueue(ctx, ctx->slots[q->next % q->cap], q->pk, cs, z, z_resident ? z_resident->scalars.p : nullptr, is_packed ? &zp : nullptr,
-                                             rnd, q->checked);
+                                             is_witness ? &wz : nullptr, rnd, q->checked);
         if (ticket) *ticket = q->next;
         ++q->next;
     });
@@ -338,6 +356,7 @@ void zkhip_ctx_free(zkhip_ctx* ctx) {
         // (streams first, whether or not the slot was ever used: a stream plan makes the streams of every slot at the first proof)
         for (int k = 0; k < ZK_NLANES; ++k)
             if (sl.lanes[k].made) stream_destroy(sl.lanes[k].stream);
+        host_free_pinned(sl.h_inputs);
         if (!sl.ready) continue;
         for (auto& so : sl.sorts) event_destroy(so.ready);
         for (int k = 0; k < ZK_NLANES; ++k) {
@@ -619,6 +638,56 @@ int32_t zkhip_assignment_upload_packed(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, c
     });
 }
 
+// ---- witness files on the device: the plan (two id -> column tables, resident), and the upload through it
+int32_t zkhip_wplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r1cs* r1cs, zkhip_wplan** out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {      // (the gate: it enqueues copies, so it is refused while a split proof or a queue is pending)
+        require(prog && r1cs && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        require(r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "constraint system belongs to another context");
+        std::shared_ptr<WPlanTables> host(new WPlanTables());
+        try {
+            wplan_build(*prog, r1cs->curve, r1cs->l, r1cs->w, *host);
+        } catch (const IngestError& e) {
+            throw ApiError{e.code, e.msg};
+        }
+        std::unique_ptr<zkhip_wplan> plan(new zkhip_wplan());
+        plan->ctx = ctx;
+        plan->cs_uid = r1cs->uid;
+        plan->pos.ensure(std::max<size_t>(host->pos.size(), 1) * 4);
+        plan->neg.ensure(std::max<size_t>(host->neg.size(), 1) * 4);
+        dev_h2d(plan->pos.p, host->pos.data(), host->pos.size() * 4, ctx->stream);
+        if (!host->neg.empty()) dev_h2d(plan->neg.p, host->neg.data(), host->neg.size() * 4, ctx->stream);
+        stream_sync(ctx->stream);
+        plan->host = host;
+        *out = plan.release();
+    });
+}
+void zkhip_wplan_free(zkhip_wplan* plan) { delete plan; }
+// the public inputs out of the head of z (l x 32 B), in the order of public_inputs_values
+static void witness_inputs(const WPlanTables& t, const uint8_t* head, uint8_t* inputs_out) {
+    for (size_t k = 0; k < t.input_cols.size(); ++k) memcpy(inputs_out + 32 * k, head + 32 * (size_t)t.input_cols[k], 32);
+}
+int32_t zkhip_assignment_upload_witness(zkhip_ctx* ctx, const zkhip_wplan* plan, const uint8_t* witness, size_t len, uint8_t* inputs_out, uint64_t inputs_cap,
+                                        uint64_t* n_inputs, zkhip_assignment** out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {
+        require(out != nullptr, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        if (n_inputs) *n_inputs = 0;
+        const WitnessZ wz = witness_source(ctx, plan, nullptr, witness, len);
+        const WPlanTables& t = *plan->host;
+        require(!inputs_out || inputs_cap >= t.input_cols.size(), ZKHIP_ERR_BAD_ARG, "inputs buffer too small");
+        std::unique_ptr<zkhip_assignment> a(new zkhip_assignment());
+        a->curve = t.curve; a->ctx = ctx; a->m = t.l + t.w;
+        std::vector<uint8_t> head(inputs_out ? t.l * 32 : 0);
+        ops_for(t.curve)->assignment_upload_witness(ctx, a.get(), wz, inputs_out ? head.data() : nullptr);
+        if (inputs_out) witness_inputs(t, head.data(), inputs_out);
+        if (n_inputs) *n_inputs = t.input_cols.size();
+        *out = a.release();
+    });
+}
+
 int32_t zkhip_prove_g16_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_assignment* z, const uint8_t* r,
                                  const uint8_t* s, uint8_t* proof_out, zkhip_timings* timings) {
     if (!ctx) return ZKHIP_ERR_BAD_ARG;
@@ -765,6 +834,9 @@ int32_t zkhip_queue_submit(zkhip_queue* q, const uint8_t* z, zkhip_assignment* z
 int32_t zkhip_queue_submit_packed(zkhip_queue* q, const uint8_t* packed, size_t len, const uint8_t* rnd, uint64_t* ticket) {
     return queue_submit(q, nullptr, nullptr, packed, len, true, rnd, ticket);
 }
+int32_t zkhip_queue_submit_witness(zkhip_queue* q, const zkhip_wplan* plan, const uint8_t* witness, size_t len, const uint8_t* rnd, uint64_t* ticket) {
+    return queue_submit(q, nullptr, nullptr, witness, len, false, rnd, ticket, plan, true);
+}
 int32_t zkhip_queue_ready(zkhip_queue* q, int32_t* ready) {
     if (!q || !q->ctx || !ready) return ZKHIP_ERR_BAD_ARG;
     *ready = 0;
@@ -772,11 +844,18 @@ int32_t zkhip_queue_ready(zkhip_queue* q, int32_t* ready) {
     if (q->broken) { *ready = 1; return ZKHIP_OK; }             // (collect answers at once)
     return queue_guarded(q, [&] { *ready = event_done(q->ctx->slots[q->head % q->cap].ev[3]) ? 1 : 0; });
 }
-int32_t zkhip_queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, zkhip_timings* timings) {
+// collect, with or without the public inputs of a ticket that was submitted as a witness file (the head of z in the slot's pinned
+// buffer, copied on the stream that wrote it before the slot's first event; permuted here by the plan's host tables)
+static int32_t queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs, zkhip_timings* timings) {
     if (!q || !q->ctx) return ZKHIP_ERR_BAD_ARG;
     zkhip_ctx* ctx = q->ctx;
+    if (n_inputs) *n_inputs = 0;
     if (!proof_out) { ctx->err = "null argument"; return ZKHIP_ERR_BAD_ARG; }
     if (q->head == q->next) { ctx->err = "the proof queue is empty: nothing to collect"; return ZKHIP_ERR_BAD_ARG; }
+    if (!q->broken && inputs_out) {      // (before the ticket is spent: a refusal for the caller's buffer changes nothing)
+        const ProofSlot& sl = ctx->slots[q->head % q->cap];
+        if (sl.wit && inputs_cap < sl.wit->input_cols.size()) { ctx->err = "inputs buffer too small"; return ZKHIP_ERR_BAD_ARG; }
+    }
     const u64 t = q->head++;      // whatever happens to this proof, its ticket is spent
     if (ticket) *ticket = t;
     if (q->broken) { ctx->err = q->dev_err; return ZKHIP_ERR_DEVICE; }
@@ -790,7 +869,19 @@ int32_t zkhip_queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out
                      (unsigned long long)u.first_row, (unsigned long long)q->cs->n, (unsigned long long)u.n_bad);
             throw ApiError{ZKHIP_ERR_UNSATISFIED, msg};
         }
+        const ProofSlot& sl = ctx->slots[t % q->cap];
+        if (sl.wit) {
+            if (inputs_out) witness_inputs(*sl.wit, (const uint8_t*)sl.h_inputs, inputs_out);
+            if (n_inputs) *n_inputs = sl.wit->input_cols.size();
+        }
     });
+}
+int32_t zkhip_queue_collect(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, zkhip_timings* timings) {
+    return queue_collect(q, ticket, proof_out, nullptr, 0, nullptr, timings);
+}
+int32_t zkhip_queue_collect_inputs(zkhip_queue* q, uint64_t* ticket, uint8_t* proof_out, uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs,
+                                   zkhip_timings* timings) {
+    return queue_collect(q, ticket, proof_out, inputs_out, inputs_cap, n_inputs, timings);
 }
 int32_t zkhip_queue_close(zkhip_queue* q) {
     if (!q) return ZKHIP_ERR_BAD_ARG;

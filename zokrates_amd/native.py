@@ -77,6 +77,7 @@ class Library:
         "zkhip_queue_open", "zkhip_queue_state", "zkhip_queue_submit", "zkhip_queue_submit_packed", "zkhip_queue_ready", "zkhip_queue_collect",
         "zkhip_queue_close",
         "zkhip_multi_ntt", "zkhip_multi_witness_map", "zkhip_multi_transform_shard", "zkhip_multi_last_shard",
+        "zkhip_wplan_create", "zkhip_wplan_free", "zkhip_assignment_upload_witness", "zkhip_queue_submit_witness", "zkhip_queue_collect_inputs",
     ]
 
     def __init__(self, path=None):
@@ -184,6 +185,11 @@ class Library:
         L.zkhip_queue_ready.restype = i32; L.zkhip_queue_ready.argtypes = [vp, vp]
         L.zkhip_queue_collect.restype = i32; L.zkhip_queue_collect.argtypes = [vp, vp, vp, vp]
         L.zkhip_queue_close.restype = i32; L.zkhip_queue_close.argtypes = [vp]
+        L.zkhip_wplan_create.restype = i32; L.zkhip_wplan_create.argtypes = [vp, vp, vp, pp]
+        L.zkhip_wplan_free.restype = None; L.zkhip_wplan_free.argtypes = [vp]
+        L.zkhip_assignment_upload_witness.restype = i32; L.zkhip_assignment_upload_witness.argtypes = [vp, vp, vp, sz, vp, u64, vp, pp]
+        L.zkhip_queue_submit_witness.restype = i32; L.zkhip_queue_submit_witness.argtypes = [vp, vp, vp, sz, vp, vp]
+        L.zkhip_queue_collect_inputs.restype = i32; L.zkhip_queue_collect_inputs.argtypes = [vp, vp, vp, vp, u64, vp, vp]
         self.L = L
 
     def init(self, hw_queues):
@@ -267,6 +273,20 @@ class Context:
     def tune(self, name, value):
         """`zkhip_ctx_tune`: development / measurement knobs (window width, slices, fold form, serial streams ...)."""
         self._check(self.lib.L.zkhip_ctx_tune(self.h, self.TUNABLES[name], int(value)))
+
+    def upload_witness(self, plan, witness_bytes, want_inputs=True):
+        """`zkhip_assignment_upload_witness`: a ZoKrates `witness` file ordered and checked on the device through `plan`
+        (`Program.plan`).  Returns (the resident `Assignment`, inputs uint8[k*32] = public_inputs_values), or the assignment alone."""
+        wit = _u8(witness_bytes)
+        a = Assignment.__new__(Assignment)
+        a.ctx = self
+        a.h = C.c_void_p()
+        cap = plan.n_inputs
+        inputs = np.zeros(max(cap, 1) * 32, dtype=np.uint8)
+        n_in = C.c_uint64()
+        self._check(self.lib.L.zkhip_assignment_upload_witness(self.h, plan.h, _ptr(wit), wit.size, _ptr(inputs) if want_inputs else None, cap,
+                                                               C.byref(n_in), C.byref(a.h)))
+        return (a, inputs[:32 * n_in.value].copy()) if want_inputs else a
 
     def close(self):
         if self.h:
@@ -763,24 +783,47 @@ class ProofQueue:
         self.ctx._check(self.ctx.lib.L.zkhip_queue_submit_packed(self.h, _ptr(packed), packed.size, _ptr(rb), C.byref(ticket)))
         return int(ticket.value)
 
+    def submit_witness(self, plan, witness_bytes, rnd):
+        """`zkhip_queue_submit_witness`: the assignment as the bytes of a ZoKrates `witness` file, ordered and checked on the device
+        through `plan` (`Program.plan`, made before the queue was opened).  What the device finds wrong with the file fails the
+        ticket at `collect`."""
+        rb = self._rnd(rnd)
+        wit = _u8(witness_bytes)
+        ticket = C.c_uint64()
+        self.ctx._check(self.ctx.lib.L.zkhip_queue_submit_witness(self.h, plan.h, _ptr(wit), wit.size, _ptr(rb), C.byref(ticket)))
+        return int(ticket.value)
+
     def ready(self):
         """`zkhip_queue_ready`: would `collect` return without waiting for the device?  Never blocks; False on an empty queue."""
         out = C.c_int32()
         self.ctx._check(self.ctx.lib.L.zkhip_queue_ready(self.h, C.byref(out)))
         return bool(out.value)
 
-    def collect(self, want_timings=False):
+    def collect(self, want_timings=False, want_inputs=False):
         """`zkhip_queue_collect`: (ticket, proof bytes) of the oldest proof in flight; blocks until it is done.  A proof that failed
-        raises ZkhipError — its `ticket` attribute says which — and the others stay in flight."""
+        raises ZkhipError — its `ticket` attribute says which — and the others stay in flight.  `want_inputs`
+        (`zkhip_queue_collect_inputs`): the public inputs (uint8[k*32]) follow the proof bytes — empty for a ticket that was not
+        submitted as a witness file."""
         out = np.zeros(self.proof_bytes, dtype=np.uint8)
         ticket = C.c_uint64(0xFFFFFFFFFFFFFFFF)
         tm = Timings()
+        L = self.ctx.lib.L
         try:
-            self.ctx._check(self.ctx.lib.L.zkhip_queue_collect(self.h, C.byref(ticket), _ptr(out), C.byref(tm)), lambda: [out.tobytes()])
+            if want_inputs:
+                cap = self.cs.l
+                inputs = np.zeros(max(cap, 1) * 32, dtype=np.uint8)
+                n_in = C.c_uint64()
+                self.ctx._check(L.zkhip_queue_collect_inputs(self.h, C.byref(ticket), _ptr(out), _ptr(inputs), cap, C.byref(n_in), C.byref(tm)),
+                                lambda: [out.tobytes()])
+            else:
+                self.ctx._check(L.zkhip_queue_collect(self.h, C.byref(ticket), _ptr(out), C.byref(tm)), lambda: [out.tobytes()])
         except ZkhipError as e:
             e.ticket = None if ticket.value == 0xFFFFFFFFFFFFFFFF else int(ticket.value)
             raise
-        return (int(ticket.value), out.tobytes(), tm.as_dict()) if want_timings else (int(ticket.value), out.tobytes())
+        res = (int(ticket.value), out.tobytes())
+        if want_inputs:
+            res += (inputs[:32 * n_in.value].copy(),)
+        return res + (tm.as_dict(),) if want_timings else res
 
     def close(self):
         """`zkhip_queue_close`: waits for what is in flight, drops it, and gives the context back."""
@@ -847,6 +890,12 @@ class Program:
         ctx._check(ctx.lib.L.zkhip_prog_r1cs_load(ctx.h, self.h, C.byref(cs.h)))
         return cs
 
+    def plan(self, ctx, cs):
+        """`zkhip_wplan_create`: this program's column order resident on `ctx`, for `Context.upload_witness` and
+        `ProofQueue.submit_witness` over `cs`.  Raises ZkhipError (BAD_ARG) for a program the device route cannot take (a repeated
+        parameter, an output without a column): such callers keep `assignment`."""
+        return WitnessPlan(ctx, self, cs)
+
     def assignment(self, witness_bytes):
         """(z uint8[m*32] in ark order, inputs uint8[k*32] = public_inputs_values) from a ZoKrates `witness` file."""
         wit = _u8(witness_bytes)
@@ -876,6 +925,27 @@ class Program:
     def close(self):
         if self.h:
             self.lib.L.zkhip_prog_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WitnessPlan:
+    """`zkhip_wplan`: the id -> column tables of one program on one context (`Program.plan`)."""
+
+    def __init__(self, ctx, prog, cs):
+        self.ctx = ctx
+        self.n_inputs = prog.n_public_args + prog.return_count
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.L.zkhip_wplan_create(ctx.h, prog.h, cs.h, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.zkhip_wplan_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
