@@ -464,6 +464,29 @@ int32_t zkhip_msm_g2(zkhip_ctx* ctx, int32_t curve, uint64_t n, const uint8_t* b
  * 14 = (a + b) a, 15 = -a b (lazy negation).  Fields above 5 are refused. */
 int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op, uint64_t count,
                        const uint8_t* a, const uint8_t* b, uint8_t* out);
+/* TESTS ONLY.  One function of the group law (csrc/ec.cuh, bind.cuh, kernels_msm.cuh) element by element on the device, called the
+ * way a kernel of the product calls it, on RAW limbs: nothing is converted or reduced on the way in or out.
+ * group: 1 (coordinates in Fq) or 2 (Fq2, c0 then c1).  form: 0 = the saturated Montgomery words of the fixed-base kernels and the
+ * host (sz(Fq) / 4 words per Fq element), 1 = the unsaturated limbs of the MSM, fold and bind kernels (9 limbs of 29 bits for
+ * bn128, 14 of 28 bits for the two BLS curves, one uint32 each).  a, b, out: count x 4 coordinates X, Y, ZZ, ZZZ, each coordinate
+ * its limbs back to back; an affine operand or result uses X and Y (results: ZZ = ZZZ = 0).  k: count x 8 words, the scalar
+ * (little-endian; ops 16 and 17 read word 0).  flags: one byte per element: bit 0 = the sign of the digit for op 2 (the only place
+ * where the product takes `neg` at run time; elsewhere it is a constant of the call, and so here: ops 18 and 19), bit 1 = a is the
+ * point at infinity, bit 2 = b is (the operand is overwritten on the device before the function reads it).
+ * op (b: A = affine, X = XYZZ, - = unused):
+ *    0 xyzz_madd_acc<false>(a, A)    1 xyzz_madd_cold(a, A)    2 xyzz_madd_begin<true> + xyzz_madd_finish<true> (a, A, neg; the
+ *    caller's precondition: a finite, the x coordinates differ; see the note below)    3 xyzz_add_acc(a, X)    4 xyzz_add_from(a, &X)
+ *    5 xyzz_add(a, X)    6 xyzz_add_to(&a, &X)    7 xyzz_dbl    8 xyzz_dbl_inl    9 xyzz_dbl_acc    10, 11 xyzz_dbl_affine_inl<false>,
+ *    <true> (a affine)    12 xyzz_neg_u    13 xyzz_to_affine    14 xyzz_to_affine_u    15 xyzz_mul_words(&a, k, 8)
+ *    16 xyzz_mul_u32(a, k[0])    17 xyzz_mul_small(a, k[0])    18 xyzz_madd_acc<false>(a, A, true)    19 xyzz_add_from(a, &X, true)
+ * Form 0 has ops 0, 5, 6, 7, 13, 16; form 1 the others, 12, 14, 15 and 19 for group 1 only (the kernels that call them exist for G1).
+ * Op 2 is the one op NO kernel calls in this form: k_msm_accum carries its own inlined copy of the addition proper (over G1 with X1
+ * kept un-reduced below 10p, Pp against 16p and no weak reduction of X3), which only MSMs and proofs reach; op 2 holds the two
+ * functions as ec.cuh defines them, with the hot products.
+ * Preconditions are the functions' own (operand bounds as written in ec.cuh); the call checks ids and pointers only and refuses
+ * every other (group, form, op). */
+int32_t zkhip_group_op(zkhip_ctx* ctx, int32_t curve, int32_t group, int32_t form, int32_t op, uint64_t count,
+                       const uint32_t* a, const uint32_t* b, const uint32_t* k, const uint8_t* flags, uint32_t* out);
 
 /* ---- "next" row N3: setup ----
  * Replaces `Groth16::<E>::circuit_specific_setup` at /root/reference/zokrates_ark/src/groth16.rs:95

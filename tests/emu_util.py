@@ -21,7 +21,13 @@ def emu_library():
         srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(host, f) for f in os.listdir(host)]
         srcs += [os.path.join(HERE, "..", "include", h) for h in ("zkhip.h", "zkhip_backend.hpp")]
         built = [EMU_LIB, os.path.join(EMU_DIR, "zkhip-cli-emu")]        # the library and the compiled host layer linked against it
-        if not all(os.path.exists(b) for b in built) or any(os.path.getmtime(s) > min(os.path.getmtime(b) for b in built) for s in srcs):
-            subprocess.check_call([os.path.join(EMU_DIR, "build_emu.sh")])
+        stale = lambda: not all(os.path.exists(b) for b in built) or any(os.path.getmtime(s) > min(os.path.getmtime(b) for b in built) for s in srcs)
+        if stale():
+            # the suite's worker processes all arrive here with the same stale library: the first one builds, the others wait and find it fresh
+            import fcntl
+            with open(os.path.join(EMU_DIR, ".emu_util.lock"), "w") as lock:
+                fcntl.flock(lock, fcntl.LOCK_EX)
+                if stale():
+                    subprocess.check_call([os.path.join(EMU_DIR, "build_emu.sh")])
         _lib = native.Library(EMU_LIB)
     return _lib

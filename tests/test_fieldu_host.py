@@ -2,7 +2,10 @@
 the host with g++: every operation the MSM kernels use (conversions, mul, mul2, add/sub with bias, weak reduction, the
 zero test, Fq2 mul/sqr, XYZZ mixed add / add / doubling incl. the exceptional branches) on all three curves (BLS12-377 with its
 own non-residue); the single-field operations also on the three scalar fields the transform passes compute in.  Operands are
-uniform below p.  tests/test_fieldu_contract.py takes the same operations to the edges of their written preconditions."""
+uniform below p.  tests/test_fieldu_contract.py takes the same operations to the edges of their written preconditions.
+fieldu_curve compares the two forms of the group law with each other, on the host; tests/test_group_law.py holds each function of
+the group law to a big-integer reference, with coordinates at their written bounds and every exceptional case, on the emulator and
+as the device compiles it."""
 import os
 import subprocess
 

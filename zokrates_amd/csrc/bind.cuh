@@ -205,4 +205,109 @@ __global__ void __launch_bounds__(256, MsmTuning<F>::COLD_WPE) k_bind_l_affine(c
     aff_pack(xyzz_to_affine_u(sum[v]), out + v);
 }
 
+// ---- TEST ONLY (zkhip_group_op): one group-law function per kernel, element by element on raw limbs ----
+// Every op calls its function the way a kernel of the product does — the same HOT argument, the same inline or out-of-line variant,
+// the second operand read from global memory where the product reads it from memory — and nothing converts or reduces: what comes
+// back are the un-reduced limbs the function left.  One instantiation per op (core.cuh GroupOp), never a run-time switch over all of
+// them: a kernel holding every formula at once is exactly the large function this code base avoids (ec.cuh xyzz_add_to).
+constexpr uint8_t GOP_FLAG_NEG = 1, GOP_FLAG_A_INF = 2, GOP_FLAG_B_INF = 4;
+template <class F> struct GroupForm { static constexpr int UNSAT = 0; };
+template <class P> struct GroupForm<Fu<P>> { static constexpr int UNSAT = 1; };
+template <class P> struct GroupForm<Fu2<P>> { static constexpr int UNSAT = 1; };
+// the operands flagged infinite become the point at infinity where they lie (an affine operand: its x and y), before the op reads them
+template <class F>
+__global__ void __launch_bounds__(64) k_group_op_mark_inf(Xyzz<F>* a, Xyzz<F>* b, const uint8_t* __restrict__ flags, u64 n) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (flags[i] & GOP_FLAG_A_INF) a[i] = Xyzz<F>::inf();
+    if (flags[i] & GOP_FLAG_B_INF) b[i] = Xyzz<F>::inf();
+}
+// Launch bounds: those of the product kernel that calls the op's function.  A unit's out-of-line routines (xyzz_madd_cold, xyzz_dbl, the
+// Fq2 products, the saturated field's) are compiled once for all their callers, and a caller with another register target moves their
+// registers and frames — and with them the figures of kernels that were there before.  So: the accumulation kernel's target for what
+// only that kernel calls, the fold kernels' for the rest of the unsaturated form, and for the saturated form the fixed-base kernels'
+// (64 work-items, no target: k_group_op_sat).
+template <class F, int OP>
+struct GroupOpBounds {
+    static constexpr bool ACCUM = OP == GOP_MADD_COLD || OP == GOP_MADD_HOT || OP == GOP_DBL_AFFINE_HOT;
+    static constexpr int WPE = ACCUM ? MsmTuning<F>::ACCUM_WPE : MsmTuning<F>::COLD_WPE;
+};
+template <class F, int OP>
+__device__ __forceinline__ void group_op_element(const Xyzz<F>* a, const Xyzz<F>* b, const u32* __restrict__ k, const uint8_t* __restrict__ flags, Xyzz<F>* out, u64 n) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool neg = (flags[i] & GOP_FLAG_NEG) != 0;      // (GOP_MADD_HOT: the digit's sign, a run-time value in k_msm_accum too)
+    const u32* const ki = k + i * GROUP_OP_SCALAR_WORDS;
+    // (operands are taken into registers first, as every caller in the product holds them; xyzz_add_from and xyzz_mul_words read memory)
+    const Xyzz<F> pa = a[i], pb = b[i];
+    const Aff<F> qb{pb.x, pb.y};
+    Xyzz<F> r;
+    if constexpr (OP == GOP_MADD_ACC) {              // k_fixed_base_mul; the body of xyzz_madd_cold
+        r = pa;
+        xyzz_madd_acc<false>(r, qb);
+    } else if constexpr (OP == GOP_MADD_ACC_NEG) {   // the same with the digit's sign applied inside (no kernel does at present)
+        r = pa;
+        xyzz_madd_acc<false>(r, qb, true);
+    } else if constexpr (OP == GOP_MADD_COLD) {      // k_msm_accum's general path
+        r = xyzz_madd_cold(pa, qb);
+    } else if constexpr (OP == GOP_MADD_HOT) {
+        // ec.cuh's two halves of the addition proper with the hot products; the caller's precondition holds (a finite, Pp != 0).  NO kernel
+        // calls them: k_msm_accum has its own inlined copy (kernels_msm.cuh; over G1 with X1 un-reduced below 10p, sub<16> for Pp and no
+        // fe_relax on X3), and that copy is reached through MSMs and proofs only
+        r = pa;
+        F Pp, R;
+        xyzz_madd_begin<true>(r, qb.x, fe_cneg(qb.y, neg), Pp, R);
+        xyzz_madd_finish<true>(r, Pp, R);
+    } else if constexpr (OP == GOP_ADD_ACC) {        // k_msm_fold_final
+        r = pa;
+        xyzz_add_acc(r, pb);
+    } else if constexpr (OP == GOP_ADD_FROM) {       // the fold kernels, k_bind_fft_stage: the second operand where it lies
+        r = pa;
+        xyzz_add_from(r, &b[i]);
+    } else if constexpr (OP == GOP_ADD_FROM_NEG) {   // k_bind_fft_stage's difference
+        r = pa;
+        xyzz_add_from(r, &b[i], true);
+    } else if constexpr (OP == GOP_ADD) {            // k_fixed_base_table (through xyzz_mul_u32), the host
+        r = xyzz_add(pa, pb);
+    } else if constexpr (OP == GOP_ADD_TO) {
+        r = pa;
+        xyzz_add_to(&r, &b[i]);
+    } else if constexpr (OP == GOP_DBL) {            // out of line: xyzz_add_acc's doubling, Setup
+        r = xyzz_dbl(pa);
+    } else if constexpr (OP == GOP_DBL_INL) {        // k_msm_table_levels, k_msm_fold_final_scan
+        r = xyzz_dbl_inl(pa);
+    } else if constexpr (OP == GOP_DBL_ACC) {        // xyzz_mul_words' running point
+        r = pa;
+        xyzz_dbl_acc(r);
+    } else if constexpr (OP == GOP_DBL_AFFINE) {     // xyzz_madd_acc<false>'s doubling
+        r = xyzz_dbl_affine_inl<false>(Aff<F>{pa.x, pa.y});
+    } else if constexpr (OP == GOP_DBL_AFFINE_HOT) { // xyzz_madd_acc<true>'s
+        r = xyzz_dbl_affine_inl<true>(Aff<F>{pa.x, pa.y});
+    } else if constexpr (OP == GOP_NEG_U) {          // k_bind_cmul
+        r = xyzz_neg_u(pa);
+    } else if constexpr (OP == GOP_TO_AFFINE) {      // k_fixed_base_mul, k_fixed_base_table
+        const Aff<F> q = xyzz_to_affine(pa);
+        r = {q.x, q.y, F::zero(), F::zero()};
+    } else if constexpr (OP == GOP_TO_AFFINE_U) {    // k_bind_h_finish, k_bind_l_affine
+        const Aff<F> q = xyzz_to_affine_u(pa);
+        r = {q.x, q.y, F::zero(), F::zero()};
+    } else if constexpr (OP == GOP_MUL_WORDS) {      // k_bind_cmul: point and scalar where they lie
+        r = xyzz_mul_words<F>(&a[i], ki, GROUP_OP_SCALAR_WORDS);
+    } else if constexpr (OP == GOP_MUL_U32) {        // k_fixed_base_table
+        r = xyzz_mul_u32(pa, ki[0]);
+    } else {                                         // GOP_MUL_SMALL: k_msm_fold_final
+        r = xyzz_mul_small(pa, ki[0]);
+    }
+    out[i] = r;
+}
+template <class F, int OP>
+__global__ void __launch_bounds__(256, (GroupOpBounds<F, OP>::WPE)) k_group_op(const Xyzz<F>* a, const Xyzz<F>* b, const u32* __restrict__ k, const uint8_t* __restrict__ flags,
+                                                                               Xyzz<F>* out, u64 n) {
+    group_op_element<F, OP>(a, b, k, flags, out, n);
+}
+template <class F, int OP>
+__global__ void __launch_bounds__(64) k_group_op_sat(const Xyzz<F>* a, const Xyzz<F>* b, const u32* __restrict__ k, const uint8_t* __restrict__ flags, Xyzz<F>* out, u64 n) {
+    group_op_element<F, OP>(a, b, k, flags, out, n);
+}
+
 }  // namespace zk

@@ -904,6 +904,28 @@ template <class F>
 void fixed_base_table(zkhip_ctx* ctx, const Aff<F>* h_pj, int nwin, DBuf& tbl);
 template <class F>
 void fixed_base_mul(zkhip_ctx* ctx, const DBuf& tbl, int nwin, const u32* d_scalars, u64 count, Aff<F>* d_out);
+// TEST ONLY (zkhip_group_op, include/zkhip.h): one group-law function of ec.cuh / bind.cuh / kernels_msm.cuh element by element, in
+// the form a kernel of the product calls it (bind.cuh k_group_op: one instantiation per op).  The ids are the header's.
+enum GroupOp : int {
+    GOP_MADD_ACC = 0, GOP_MADD_COLD, GOP_MADD_HOT, GOP_ADD_ACC, GOP_ADD_FROM, GOP_ADD, GOP_ADD_TO, GOP_DBL, GOP_DBL_INL, GOP_DBL_ACC, GOP_DBL_AFFINE,
+    GOP_DBL_AFFINE_HOT, GOP_NEG_U, GOP_TO_AFFINE, GOP_TO_AFFINE_U, GOP_MUL_WORDS, GOP_MUL_U32, GOP_MUL_SMALL, GOP_MADD_ACC_NEG, GOP_ADD_FROM_NEG, GOP_COUNT
+};
+constexpr int GROUP_OP_SCALAR_WORDS = 8;      // words of `k` per element
+// which ops exist for (group, form): the saturated form has what the fixed-base kernels and the host run; the unsaturated form what the
+// MSM, fold and bind kernels run — the bind kernels over G1 only (they alone subtract: xyzz_add_from with neg), and nothing there uses
+// the exact-zero tests of xyzz_add.  `neg` is a constant of the instantiation, as it is at every call in the product: a kernel that took
+// it at run time changed how the units' shared out-of-line routines were compiled, and with them the frames of the fold kernels.
+constexpr bool group_op_known(int group, int form, int op) {
+    if (group < 1 || group > 2 || form < 0 || form > 1 || op < 0 || op >= GOP_COUNT) return false;
+    const bool sat_only = op == GOP_ADD || op == GOP_ADD_TO || op == GOP_MUL_U32 || op == GOP_TO_AFFINE;
+    if (form == 0) return sat_only || op == GOP_MADD_ACC || op == GOP_DBL;      // (GOP_MADD_ACC_NEG, GOP_ADD_FROM_NEG: form 1)
+    if (sat_only) return false;
+    if (group == 2 && (op == GOP_NEG_U || op == GOP_TO_AFFINE_U || op == GOP_MUL_WORDS || op == GOP_ADD_FROM_NEG)) return false;
+    return true;
+}
+// FS: the group's saturated coordinate field (Fq or Fq2); a, b, out: count x 4 coordinates of raw limbs in the form's layout
+template <class FS>
+void group_op_run(zkhip_ctx* ctx, int form, int op, u64 count, const u32* a, const u32* b, const u32* k, const uint8_t* flags, u32* out);
 
 // the MSM's value from its bucket-set sums: the single sum of a table MSM, else the host Horner step sum_j 2^(c j) S_j
 template <class F>
@@ -3080,6 +3102,7 @@ struct CurveOps {
     void (*msm_g1)(zkhip_ctx*, u64, const uint8_t*, const uint8_t*, uint8_t*);
     void (*msm_g2)(zkhip_ctx*, u64, const uint8_t*, const uint8_t*, uint8_t*);
     void (*field_op)(zkhip_ctx*, int field, int op, u64, const uint8_t*, const uint8_t*, uint8_t*);
+    void (*group_op)(zkhip_ctx*, int group, int form, int op, u64, const u32*, const u32*, const u32*, const uint8_t*, u32*);
     void (*setup)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, u64);
     // GM17 (gm17.cuh)
     void (*gm17_prove)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, uint8_t*, zkhip_timings*);
@@ -3109,6 +3132,11 @@ static void field_op_dispatch(zkhip_ctx* ctx, int field, int op, u64 count, cons
     else if (field == 3) P::template field_op_api<Fq2>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq2* x, Fq2* y) { ZK_LAUNCH((k_field_op_fq2<typename Fq2::Params, true>), g, t, 0, s, x, y, x, count, op); });
     else if (field == 4) P::template field_op_api<Fr>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fr* x, Fr* y) { ZK_LAUNCH((k_field_op_unsat<typename Fr::Params>), g, t, 0, s, x, y, x, count, op); });
     else P::template field_op_api<Fq>(ctx, count, 64, a, b, out, [&](dim3 g, dim3 t, Stream s, Fq* x, Fq* y) { ZK_LAUNCH((k_field_op_unsat<typename Fq::Params>), g, t, 0, s, x, y, x, count, op); });
+}
+template <class C>
+static void group_op_dispatch(zkhip_ctx* ctx, int group, int form, int op, u64 count, const u32* a, const u32* b, const u32* k, const uint8_t* flags, u32* out) {
+    if (group == 1) group_op_run<typename C::Fq>(ctx, form, op, count, a, b, k, flags, out);
+    else group_op_run<typename C::Fq2>(ctx, form, op, count, a, b, k, flags, out);
 }
 template <class C>
 static CurveOps make_curve_ops() {
@@ -3159,6 +3187,7 @@ static CurveOps make_curve_ops() {
     o.msm_g1 = &Prover<C>::template msm_api<typename C::Fq, 2>;
     o.msm_g2 = &Prover<C>::template msm_api<typename C::Fq2, 4>;
     o.field_op = &field_op_dispatch<C>;
+    o.group_op = &group_op_dispatch<C>;
     o.setup = &Setup<C>::run;
     o.gm17_prove = &Gm17<C>::prove;
     o.gm17_prove_batch = &Gm17<C>::prove_batch;

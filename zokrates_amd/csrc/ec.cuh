@@ -84,6 +84,12 @@ template <bool HOT, class F> ZK_HD F ecm_k(const F& a, const F& b) { return ecm<
 
 // Bounds for the unsaturated field (fieldu.cuh): products come out < 2p; the comments "< kp" track the integer values so
 // that every sub<K> has value(b) < K*p and every stored coordinate stays < 8p (X < 3p after fe_relax, Y < 4p, ZZ/ZZZ < 2p).
+// A stored Y is also a SUBTRAHEND, with a subtrahend's top limb (<= (4p)_top - 2, fieldu.cuh:17-24): the mixed additions take R = S2 - Y1
+// against 4p, xyzz_y_of and xyzz_neg_u negate it against 4p, and over Fq2 every doubling squares U = 2Y, whose second component the
+// square negates against 8p (fu2_sqr_inl) — a Y.c1 within 2^(B (N - 1)) of 4p wraps that top limb and the doubling returns another
+// point (tests/test_group_law.py found it on BLS12-377).  "Y < 4p" alone does not exclude such a Y; what the producers leave does:
+// every Y3 is t + 2p - u (or one reduced sum) with t a product of operands < 8p, t < p + 64 p^2 / R' <= 1.38p (BN254; 1.03p for the
+// BLS fields), so Y < 3.4p, with more than half a p to spare below the limit.
 // For the saturated field sub<K> is the plain modular subtraction and fe_relax the identity.
 template <bool HOT = false, class F>
 ZK_HD Xyzz<F> xyzz_dbl_affine_inl(const Aff<F>& p) {
@@ -227,7 +233,9 @@ ZK_HD void xyzz_madd_acc(Xyzz<F>& a, const Aff<F>& p, bool neg = false) {
     a.zz = ecm_k<HOT>(a.zz, PP);
     a.zzz = ecm_k<HOT>(a.zzz, PPP);
     F X3 = fe_relax(fu_x3_numerator(ecs<HOT>(R), PPP, Q));                    // R^2 - PPP - 2Q: < 10p before, < 3p after
-    a.y = ec_mulsub<HOT>(R, fe_sub_k<4>(Q, X3), a.y, PPP);                    // one reduction: < 3p (G1 fused: < 2p)
+    // (one reduction where the sum is fused: < 3p, G1 < 2p.  The cold Fq2 kernels of the two BLS curves — FQ2_INLINE off, HOT off — take
+    // the two products and a sub<2>: t + 2p - u < 4p, the stored bound; tests/test_group_law.py met 3.003p there)
+    a.y = ec_mulsub<HOT>(R, fe_sub_k<4>(Q, X3), a.y, PPP);
     a.x = X3;
 }
 // The common case of a += (+-)p for the accumulation kernel's fast path, cut in two so that the kernel can look at Pp before it

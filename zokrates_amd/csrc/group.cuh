@@ -186,7 +186,44 @@ void bind_l_finish(zkhip_ctx* ctx, const void* d_prod, const u64* d_cptr, const 
         ZK_LAUNCH((k_bind_l_sum_long<F>), dim3((unsigned)n_long), dim3(64), 0, ctx->stream, (const Xyzz<F>*)d_prod, d_cptr, (const AffPacked<F>*)d_l_table, d_long_cols, (Xyzz<F>*)d_sum);
     ZK_LAUNCH((k_bind_l_affine<F>), dim3(blocks_for(m, 256)), dim3(256), 0, ctx->stream, (const Xyzz<F>*)d_sum, m, (AffPacked<F>*)d_out);
 }
-#define ZK_INSTANTIATE_BIND(F)                                                                                          \
+// ---- TEST ONLY: zkhip_group_op (bind.cuh k_group_op) ----
+template <class F, int OP>
+static void group_op_launch(zkhip_ctx* ctx, int op, u64 count, Xyzz<F>* a, Xyzz<F>* b, const u32* k, const uint8_t* flags, Xyzz<F>* out) {
+    if constexpr (OP < GOP_COUNT) {
+        if (op != OP) return group_op_launch<F, OP + 1>(ctx, op, count, a, b, k, flags, out);
+        if constexpr (group_op_known(MsmTuning<F>::IS_EXT ? 2 : 1, GroupForm<F>::UNSAT, OP)) {
+            if constexpr (GroupForm<F>::UNSAT) ZK_LAUNCH((k_group_op<F, OP>), dim3(blocks_for(count, 256)), dim3(256), 0, ctx->stream, a, b, k, flags, out, count);
+            else ZK_LAUNCH((k_group_op_sat<F, OP>), dim3(blocks_for(count, 64)), dim3(64), 0, ctx->stream, a, b, k, flags, out, count);
+        } else
+            require(false, ZKHIP_ERR_BAD_ARG, "this group and form have no such operation");
+    } else {
+        require(false, ZKHIP_ERR_BAD_ARG, "unknown group operation");
+    }
+}
+template <class F>
+static void group_op_form(zkhip_ctx* ctx, int op, u64 count, const u32* a, const u32* b, const u32* k, const uint8_t* flags, u32* out) {
+    if (!count) return;
+    Stream s = ctx->stream;
+    const size_t bytes = count * sizeof(Xyzz<F>), kbytes = count * GROUP_OP_SCALAR_WORDS * sizeof(u32);
+    DBuf da, db, dk, df, dout;
+    da.ensure(bytes); db.ensure(bytes); dk.ensure(kbytes); df.ensure(count); dout.ensure(bytes);
+    dev_h2d(da.p, a, bytes, s);
+    dev_h2d(db.p, b, bytes, s);
+    dev_h2d(dk.p, k, kbytes, s);
+    dev_h2d(df.p, flags, count, s);
+    dev_memset(dout.p, 0, bytes, s);
+    ZK_LAUNCH((k_group_op_mark_inf<F>), dim3(blocks_for(count, 64)), dim3(64), 0, s, ptr<Xyzz<F>>(da), ptr<Xyzz<F>>(db), ptr<uint8_t>(df), count);
+    group_op_launch<F, 0>(ctx, op, count, ptr<Xyzz<F>>(da), ptr<Xyzz<F>>(db), ptr<u32>(dk), ptr<uint8_t>(df), ptr<Xyzz<F>>(dout));
+    dev_d2h(out, dout.p, bytes, s);
+    stream_sync(s);
+}
+template <class FS>
+void group_op_run(zkhip_ctx* ctx, int form, int op, u64 count, const u32* a, const u32* b, const u32* k, const uint8_t* flags, u32* out) {
+    if (form == 0) group_op_form<FS>(ctx, op, count, a, b, k, flags, out);
+    else group_op_form<typename Unsat<FS>::type>(ctx, op, count, a, b, k, flags, out);
+}
+
+#define ZK_INSTANTIATE_BIND(F)                                                                                         \
     template size_t bind_xyzz_bytes<F>();                                                                               \
     template void bind_scale<F>(zkhip_ctx*, const void*, u64, u64, u32, u32, u32, const u32*, const u32*, int, void*);  \
     template void bind_fft<F>(zkhip_ctx*, void*, u64, const u32*, int);                                                 \
@@ -202,6 +239,7 @@ void bind_l_finish(zkhip_ctx* ctx, const void* d_prod, const u64* d_cptr, const 
     template u64 count_infinite<F>(zkhip_ctx*, const void*, u64);                                \
     template void mark_finite<F>(zkhip_ctx*, const void*, u64, u32*);                            \
     template void fixed_base_table<F>(zkhip_ctx*, const Aff<F>*, int, DBuf&);                                           \
-    template void fixed_base_mul<F>(zkhip_ctx*, const DBuf&, int, const u32*, u64, Aff<F>*);
+    template void fixed_base_mul<F>(zkhip_ctx*, const DBuf&, int, const u32*, u64, Aff<F>*);                            \
+    template void group_op_run<F>(zkhip_ctx*, int, int, u64, const u32*, const u32*, const u32*, const uint8_t*, u32*);
 
 }  // namespace zk

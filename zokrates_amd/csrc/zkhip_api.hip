@@ -933,6 +933,16 @@ int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op,
         ops_for(curve)->field_op(ctx, field, op, count, a, b, out);
     });
 }
+int32_t zkhip_group_op(zkhip_ctx* ctx, int32_t curve, int32_t group, int32_t form, int32_t op, uint64_t count, const uint32_t* a, const uint32_t* b,
+                       const uint32_t* k, const uint8_t* flags, uint32_t* out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {
+        require(a && b && k && flags && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        require(group_op_known(group, form, op), ZKHIP_ERR_BAD_ARG, "unknown group, form or operation (or no such operation for this group and form)");
+        require(count <= ((u64)1 << 24), ZKHIP_ERR_BAD_ARG, "count too large");
+        ops_for(curve)->group_op(ctx, group, form, op, count, a, b, k, flags, out);
+    });
+}
 
 int32_t zkhip_setup_g16_size(const zkhip_r1cs* cs, uint64_t* pk_bytes) {
     if (!cs || !pk_bytes) return ZKHIP_ERR_BAD_ARG;

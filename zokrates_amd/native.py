@@ -59,7 +59,7 @@ class Library:
         "zkhip_pk_free", "zkhip_pk_dims", "zkhip_r1cs_load", "zkhip_r1cs_free", "zkhip_prove_g16",
         "zkhip_prove_g16_batch", "zkhip_assignment_upload", "zkhip_assignment_free", "zkhip_prove_g16_resident", "zkhip_prove_g16_resident_batch",
         "zkhip_pk_load_g16_shard", "zkhip_partial_size", "zkhip_prove_g16_partial", "zkhip_combine_g16", "zkhip_ntt", "zkhip_witness_map", "zkhip_msm_g1", "zkhip_msm_g2",
-        "zkhip_field_op", "zkhip_setup_g16_size", "zkhip_setup_g16", "zkhip_describe",
+        "zkhip_field_op", "zkhip_group_op", "zkhip_setup_g16_size", "zkhip_setup_g16", "zkhip_describe",
         "zkhip_pk_load_gm17", "zkhip_prove_gm17", "zkhip_prove_gm17_resident", "zkhip_prove_gm17_resident_batch",
         "zkhip_setup_gm17_size", "zkhip_setup_gm17", "zkhip_pk_load_gm17_shard", "zkhip_prove_gm17_partial", "zkhip_combine_gm17",
         "zkhip_prog_parse", "zkhip_prog_free", "zkhip_prog_dims", "zkhip_prog_matrix", "zkhip_prog_variable_order",
@@ -128,6 +128,7 @@ class Library:
         L.zkhip_msm_g1.restype = i32; L.zkhip_msm_g1.argtypes = [vp, i32, u64, vp, vp, vp]
         L.zkhip_msm_g2.restype = i32; L.zkhip_msm_g2.argtypes = [vp, i32, u64, vp, vp, vp]
         L.zkhip_field_op.restype = i32; L.zkhip_field_op.argtypes = [vp, i32, i32, i32, u64, vp, vp, vp]
+        L.zkhip_group_op.restype = i32; L.zkhip_group_op.argtypes = [vp, i32, i32, i32, i32, u64, vp, vp, vp, vp, vp]
         L.zkhip_setup_g16_size.restype = i32; L.zkhip_setup_g16_size.argtypes = [vp, vp]
         L.zkhip_setup_g16.restype = i32; L.zkhip_setup_g16.argtypes = [vp, vp, vp, vp, vp, vp, u64]
         L.zkhip_describe.restype = i32; L.zkhip_describe.argtypes = [vp, vp, sz]
@@ -328,6 +329,22 @@ class Context:
         code = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "mul_call": 5, "sqr_call": 6, "mulsub": 7, "mul_wide": 8, "sqr_wide": 9, "mulsub_wide": 10,
                 "sub4": 4, "mul_loose": 5, "sqr_loose": 6, "relax8": 7, "x3_numerator": 11, "bf_sub4": 12, "bf_sub8": 13, "bf_add": 14, "mul_neg_lazy": 15}[op]      # (fields 4, 5)
         self._check(self.lib.L.zkhip_field_op(self.h, curve_id, field, code, a.size // nb, _ptr(a), _ptr(b), _ptr(out)))
+        return out
+
+    GROUP_OPS = ["madd_acc", "madd_cold", "madd_hot", "add_acc", "add_from", "add", "add_to", "dbl", "dbl_inl", "dbl_acc", "dbl_affine", "dbl_affine_hot",
+                 "neg_u", "to_affine", "to_affine_u", "mul_words", "mul_u32", "mul_small", "madd_acc_neg", "add_from_neg"]       # (the ids of include/zkhip.h, in order)
+
+    def group_op(self, curve_id, group, form, op, a, b, k, flags):
+        """TESTS ONLY (zkhip_group_op): a, b: uint32 arrays of count x 4 coordinates of raw limbs, k: count x 8 words, flags: count
+        bytes; returns the raw result limbs in the shape of `a`."""
+        a = np.ascontiguousarray(a, dtype=np.uint32); b = np.ascontiguousarray(b, dtype=np.uint32)
+        k = np.ascontiguousarray(k, dtype=np.uint32); flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        count = flags.size
+        if a.shape != b.shape or a.size % max(count, 1) or k.size != 8 * count:
+            raise ValueError("operand shapes")
+        out = np.zeros_like(a)
+        self._check(self.lib.L.zkhip_group_op(self.h, curve_id, group, form, self.GROUP_OPS.index(op) if isinstance(op, str) else op, count,
+                                              _ptr(a), _ptr(b), _ptr(k), _ptr(flags), _ptr(out)))
         return out
 
 
