@@ -94,6 +94,7 @@ typedef struct zkhip_ctx zkhip_ctx;
 typedef struct zkhip_pk zkhip_pk;
 typedef struct zkhip_r1cs zkhip_r1cs;
 typedef struct zkhip_assignment zkhip_assignment;
+typedef struct zkhip_vk zkhip_vk;             /* a verifying key resident on the GPU (zkhip_vk_load_g16 / _gm17) */
 typedef struct zkhip_prog zkhip_prog;         /* a parsed ZoKrates program (the zkhip_prog_* family below) */
 
 /* Per-proof phase timings in milliseconds (HIP events on the library's own streams).  The MSMs run on their own
@@ -487,6 +488,61 @@ int32_t zkhip_field_op(zkhip_ctx* ctx, int32_t curve, int32_t field, int32_t op,
  * every other (group, form, op). */
 int32_t zkhip_group_op(zkhip_ctx* ctx, int32_t curve, int32_t group, int32_t form, int32_t op, uint64_t count,
                        const uint32_t* a, const uint32_t* b, const uint32_t* k, const uint8_t* flags, uint32_t* out);
+
+/* ---- the pairing check on the device (csrc/pairing.cuh) ----
+ * The device counterpart of the host layer's `pairing_product_is_one` (csrc/host/verify.cpp), and the primitive under the check
+ * the reference makes in `<Ark as Backend<T, G16>>::verify` (/root/reference/zokrates_ark/src/groth16.rs:55-87: ark_groth16's
+ * e(A, B) e(-g_ic, gamma) e(-C, delta) e(-alpha, beta) == 1) and in `<Ark as Backend<T, GM17>>::verify` (gm17.rs:69-110: two such
+ * products): ok_out[i] = 1 iff prod_k e(g1[i][k], g2[i][k]) == 1, for count independent items of pairs_per_item (1 .. 8) pairs each.
+ * Deterministic, one verdict per item; no random linear combination.
+ *   g1     : count x pairs_per_item records of 2 x sz(Fq) + 1 bytes: x, y canonical LE and a flag byte (non-zero: the point at
+ *            infinity), the record of A and C in proof_out of zkhip_prove_g16
+ *   g2     : the same with 4 x sz(Fq) + 1 bytes: x.c0 x.c1 y.c0 y.c1 and the flag byte
+ *   ok_out : count bytes, 0 or 1
+ * A pair with a point at infinity contributes 1 (the host verifier's product skips it).  A point that is not on its curve / twist
+ * or not in the r-torsion makes its item's verdict 0 (tested on the device: r P = O by the group law of csrc/ec.cuh; bn128's G1 has
+ * cofactor 1).  A coordinate that is not below the field modulus is the caller's error: ZKHIP_ERR_PARSE, the message names the
+ * lowest such item, and ok_out is not written.  count == 0 is ZKHIP_OK and touches nothing.
+ * The call runs on a stream and in buffers of its own and touches no proof slot: it is allowed while a proof queue is open (to
+ * check collected proofs between submits) and refused, like every other call, while a split proof is pending. */
+int32_t zkhip_pairing_products(zkhip_ctx* ctx, int32_t curve, uint64_t count, uint32_t pairs_per_item,
+                               const uint8_t* g1, const uint8_t* g2, uint8_t* ok_out);
+/* ---- verify on the device: one verdict per proof ----
+ * Replaces `<Ark as Backend<T, G16>>::verify` (/root/reference/zokrates_ark/src/groth16.rs:55-87: ark_groth16::verify_proof) and
+ * `<Ark as Backend<T, GM17>>::verify` (gm17.rs:69-110: ark_gm17::verify_proof) for batches of proofs under one key; for every input
+ * on which the host layer's `verify` answers true or false the verdict is the same, and where it throws the call fails.
+ * zkhip_vk_load_*: `bytes` is ark's VerifyingKey in the `serialize_unchecked` layout — g16: alpha_g1, beta_g2, gamma_g2, delta_g2,
+ * gamma_abc_g1[]; gm17: h_g2, g_alpha_g1, h_beta_g2, g_gamma_g1, h_gamma_g2, query[] — which is the head of a `proving.key`, so a
+ * whole proving key is accepted too.  Every point of the key is tested on the device like a proof point (canonical coordinates, on
+ * its curve / twist, r P = O); a key with a point that fails, a point at infinity or too few bytes is refused with
+ * ZKHIP_ERR_PARSE.  What depends on the key alone is prepared here (the negated points, every point in the kernels' limbs).
+ * zkhip_vk_dims: out[0] = l, the number of public inputs (points of gamma_abc / query less one), out[1] = 0 Groth16, 1 GM17. */
+int32_t zkhip_vk_load_g16(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_vk** out);
+int32_t zkhip_vk_load_gm17(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_vk** out);
+void zkhip_vk_free(zkhip_vk* vk);
+int32_t zkhip_vk_dims(const zkhip_vk* vk, uint64_t out[2]);
+/*   proofs : count records in exactly the proof_out layout of zkhip_prove_g16 / zkhip_prove_gm17 (8 x sz(Fq) + 3 bytes)
+ *   inputs : count x l x 32 B, canonical LE (may be NULL when l == 0)
+ *   ok_out : count bytes, 0 or 1
+ * g_ic = gamma_abc[0] + sum_i input_i gamma_abc[i + 1] is computed per proof on the device, for any l.  A point of a proof that is
+ * off its curve, outside the r-torsion or flagged as the point at infinity makes that proof's verdict 0, as on the host.  A
+ * coordinate that is not below the field modulus or an input that is not below r is the host verifier's Error: ZKHIP_ERR_PARSE,
+ * the message names the lowest such item and the value, and no verdict is written.  A key of the other scheme, of another context,
+ * or a NULL pointer: ZKHIP_ERR_BAD_ARG.  count == 0 is ZKHIP_OK and touches nothing.  Call discipline as zkhip_pairing_products:
+ * allowed while a proof queue is open, refused while a split proof is pending; nothing consults the environment. */
+int32_t zkhip_verify_g16_batch(zkhip_ctx* ctx, const zkhip_vk* vk, uint64_t count, const uint8_t* proofs, const uint8_t* inputs,
+                               uint8_t* ok_out);
+int32_t zkhip_verify_gm17_batch(zkhip_ctx* ctx, const zkhip_vk* vk, uint64_t count, const uint8_t* proofs, const uint8_t* inputs,
+                                uint8_t* ok_out);
+/* TESTS ONLY.  One function of the Fq12 arithmetic of csrc/pairing.cuh per call, item by item, on RAW limbs in the layout of the
+ * pairing kernel (one group of lanes per item, the values in LDS): nothing is converted or reduced on the way in or out.
+ * Fq12 = Fq2[w] / (w^6 - xi); a, b, out: count x 6 coefficients (of w^0 .. w^5) x 2 components (c0, c1) x N limbs, N = 9 limbs of
+ * 29 bits for bn128, 14 of 28 bits for the BLS curves, Montgomery form with respect to 2^(N x bits).  Operands: every limb at most
+ * 2^bits + 8 and every value below 3p, the bound the kernel keeps; results obey the same.
+ * op: 0 a b   1 a^2   2 a times the line whose three values are b's coefficients at the line's positions (w^0, w^1, w^3 on the type D
+ * twists of bn128 and bls12_377; w^0, w^2, w^3 on bls12_381's type M twist; b's other coefficients are not read)   3 1 / a (0 -> 0)
+ * 4 a^p   5 a^(p^6).  b is read for every op. */
+int32_t zkhip_tower_op(zkhip_ctx* ctx, int32_t curve, int32_t op, uint64_t count, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
 /* ---- "next" row N3: setup ----
  * Replaces `Groth16::<E>::circuit_specific_setup` at /root/reference/zokrates_ark/src/groth16.rs:95

@@ -25,6 +25,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "zkhip.h"
@@ -69,6 +70,36 @@ struct VerificationKey {
 // messages, ops/verify.rs:95-107), a coordinate or input is not canonical, the input count does not fit the key (the reference
 // panics through `unwrap` there).
 bool verify(const VerificationKey& vk, const Proof& proof);
+// The same check on the device, for batches (Hip::load_verification_key, Hip::verify_batch below; csrc/pairing.cuh).  The host
+// `verify` stays and stays the default.  What crosses the C ABI, made from the hex strings with the host verifier's strictness:
+// the key in ark's `serialize_unchecked` byte layout (every coordinate "0x" + exactly the field's width, else Error; a coordinate
+// that is not below the modulus is refused where the key is loaded), a proof as the 8 x sz(Fq) + 3 byte record of zkhip_prove_g16 / _gm17, its inputs as 32-byte little-endian words
+// (defined inline at the end of this header, with the two Hip methods: a program that links the host layer without them pays nothing)
+std::vector<uint8_t> verification_key_bytes(const VerificationKey& vk);
+std::vector<uint8_t> proof_record(const Proof& proof);
+std::vector<uint8_t> proof_inputs(const Proof& proof);
+// a verifying key resident on the GPU (zkhip_vk): made by Hip::load_verification_key, freed with the object
+class DeviceVerificationKey {
+  public:
+    DeviceVerificationKey() = default;
+    DeviceVerificationKey(DeviceVerificationKey&& o) noexcept { *this = std::move(o); }
+    DeviceVerificationKey& operator=(DeviceVerificationKey&& o) noexcept {
+        std::swap(vk_, o.vk_); std::swap(scheme_, o.scheme_); std::swap(curve_, o.curve_); std::swap(inputs_, o.inputs_);
+        return *this;
+    }
+    DeviceVerificationKey(const DeviceVerificationKey&) = delete;
+    DeviceVerificationKey& operator=(const DeviceVerificationKey&) = delete;
+    ~DeviceVerificationKey();
+    const std::string& scheme() const { return scheme_; }
+    const std::string& curve() const { return curve_; }
+    uint64_t inputs() const { return inputs_; }
+
+  private:
+    friend class Hip;
+    zkhip_vk* vk_ = nullptr;
+    std::string scheme_, curve_;
+    uint64_t inputs_ = 0;
+};
 // the text of `verification.key` for the key at the head of an ark proving key (ProvingKey { vk, .. }); Error if the bytes are too short
 std::string verification_key_json(Scheme scheme, int32_t curve, const uint8_t* proving_key, size_t len);
 // prod_i e(g1_i, g2_i) == 1 in the target group (the Solidity verifier's `pairing` precompile call, solidity.rs:  pairingProd*)
@@ -284,6 +315,12 @@ class Hip {
     Queue open_queue(Scheme scheme, const System& system, const Key& key);
     std::string describe() const;
 
+    // Backend::verify on the device (zkhip_vk_load_*, zkhip_verify_*_batch): the key's points are tested and prepared once; then one
+    // verdict per proof, the host `verify`'s for every proof on which it answers; where it throws for a proof (tags that differ from
+    // the key's, an input count that does not fit it, a coordinate or input that is not canonical) this throws, naming the proof
+    DeviceVerificationKey load_verification_key(const VerificationKey& vk);
+    std::vector<bool> verify_batch(const DeviceVerificationKey& vk, const std::vector<Proof>& proofs);
+
   private:
     friend class Queue;
     zkhip_ctx* ctx_ = nullptr;
@@ -293,4 +330,111 @@ class Hip {
     void check(int32_t rc) const;
 };
 
+// ---------------- verification on the device: what crosses the C ABI, and the two Hip methods ----------------
+namespace detail {      // not part of the interface: the spelling of points and fields on either side of the C ABI
+inline size_t fq_bytes_of(const std::string& curve) {
+    if (curve == "bn128") return 32;
+    if (curve == "bls12_381" || curve == "bls12_377") return 48;
+    throw Error(ZKHIP_ERR_BAD_ARG, "verify: curve " + curve + " is not supported (bn128, bls12_381, bls12_377)");
+}
+// "0x" + exactly 2 nb hex digits, big-endian -> nb bytes, little-endian, appended
+inline void hex_to_le(const std::string& s, size_t nb, std::vector<uint8_t>& out) {
+    if (s.size() != 2 + 2 * nb || s[0] != '0' || s[1] != 'x')
+        throw Error(ZKHIP_ERR_PARSE, "verify: a coordinate must be \"0x\" followed by " + std::to_string(2 * nb) + " hex digits, got \"" + s + "\"");
+    const size_t at = out.size();
+    out.resize(at + nb, 0);
+    for (size_t i = 2; i < s.size(); ++i) {
+        const char c = s[i];
+        const int h = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (h < 0) throw Error(ZKHIP_ERR_PARSE, "verify: bad hex digit in \"" + s + "\"");
+        const size_t nib = s.size() - 1 - i;
+        out[at + nib / 2] |= (uint8_t)(h << (4 * (nib % 2)));
+    }
+}
+inline void g1_le(const G1Affine& a, size_t nb, std::vector<uint8_t>& out) { hex_to_le(a.x, nb, out); hex_to_le(a.y, nb, out); }
+inline void g2_le(const G2Affine& a, size_t nb, std::vector<uint8_t>& out) {
+    hex_to_le(a.x[0], nb, out); hex_to_le(a.x[1], nb, out); hex_to_le(a.y[0], nb, out); hex_to_le(a.y[1], nb, out);
+}
+}  // namespace detail
+inline std::vector<uint8_t> verification_key_bytes(const VerificationKey& vk) {
+    const size_t nb = detail::fq_bytes_of(vk.curve);
+    const bool g16 = vk.scheme == "g16";
+    if (!g16 && vk.scheme != "gm17") throw Error(ZKHIP_ERR_BAD_ARG, "verify: scheme " + vk.scheme + " is not supported (g16, gm17)");
+    std::vector<uint8_t> out;
+    if (g16) {
+        detail::g1_le(vk.g1.at("alpha"), nb, out); detail::g2_le(vk.g2.at("beta"), nb, out); detail::g2_le(vk.g2.at("gamma"), nb, out); detail::g2_le(vk.g2.at("delta"), nb, out);
+    } else {
+        detail::g2_le(vk.g2.at("h"), nb, out); detail::g1_le(vk.g1.at("g_alpha"), nb, out); detail::g2_le(vk.g2.at("h_beta"), nb, out); detail::g1_le(vk.g1.at("g_gamma"), nb, out);
+        detail::g2_le(vk.g2.at("h_gamma"), nb, out);
+    }
+    const uint64_t n = vk.query.size();
+    for (int i = 0; i < 8; ++i) out.push_back((uint8_t)(n >> (8 * i)));
+    for (const auto& q : vk.query) detail::g1_le(q, nb, out);
+    return out;
+}
+inline std::vector<uint8_t> proof_record(const Proof& proof) {
+    const size_t nb = detail::fq_bytes_of(proof.curve);
+    std::vector<uint8_t> out;
+    detail::g1_le(proof.proof.a, nb, out); detail::g2_le(proof.proof.b, nb, out); detail::g1_le(proof.proof.c, nb, out);
+    out.resize(out.size() + 3, 0);          // (a point at infinity has no spelling in proof.json)
+    return out;
+}
+inline std::vector<uint8_t> proof_inputs(const Proof& proof) {
+    std::vector<uint8_t> out;
+    for (const std::string& s : proof.inputs) {
+        size_t i = 0;
+        while (s.compare(i, 2, "0x") == 0) i += 2;
+        if (i == s.size()) throw Error(ZKHIP_ERR_PARSE, "verify: empty input \"" + s + "\"");
+        while (i + 1 < s.size() && s[i] == '0') ++i;
+        if (s.size() - i > 64) throw Error(ZKHIP_ERR_PARSE, "verify: input " + s + " is not below the scalar field modulus");
+        detail::hex_to_le("0x" + std::string(64 - (s.size() - i), '0') + s.substr(i), 32, out);
+    }
+    return out;
+}
+
+inline DeviceVerificationKey::~DeviceVerificationKey() { if (vk_) zkhip_vk_free(vk_); }
+namespace detail {
+inline int32_t curve_id_of(const std::string& curve) {
+    if (curve == "bn128") return ZKHIP_CURVE_BN128;
+    if (curve == "bls12_381") return ZKHIP_CURVE_BLS12_381;
+    if (curve == "bls12_377") return ZKHIP_CURVE_BLS12_377;
+    throw Error(ZKHIP_ERR_BAD_ARG, "verify: curve " + curve + " is not supported (bn128, bls12_381, bls12_377)");
+}
+}  // namespace detail
+inline DeviceVerificationKey Hip::load_verification_key(const VerificationKey& vk) {
+    const std::vector<uint8_t> bytes = verification_key_bytes(vk);
+    DeviceVerificationKey out;
+    out.scheme_ = vk.scheme;
+    out.curve_ = vk.curve;
+    check((vk.scheme == "gm17" ? zkhip_vk_load_gm17 : zkhip_vk_load_g16)(ctx_, detail::curve_id_of(vk.curve), bytes.data(), bytes.size(), &out.vk_));
+    uint64_t dims[2];
+    check(zkhip_vk_dims(out.vk_, dims));
+    out.inputs_ = dims[0];
+    return out;
+}
+inline std::vector<bool> Hip::verify_batch(const DeviceVerificationKey& vk, const std::vector<Proof>& proofs) {
+    if (!vk.vk_) throw Error(ZKHIP_ERR_BAD_ARG, "verify_batch: no verification key loaded");
+    std::vector<uint8_t> recs, inputs;
+    for (size_t i = 0; i < proofs.size(); ++i) {
+        const Proof& p = proofs[i];
+        const std::string at = "proof " + std::to_string(i) + ": ";
+        if (p.curve != vk.curve_)
+            throw Error(ZKHIP_ERR_BAD_ARG, at + "Expected the curve of the proof and the verification key to be equal, found " + p.curve + " != " + vk.curve_);
+        if (p.scheme != vk.scheme_)
+            throw Error(ZKHIP_ERR_BAD_ARG, at + "Expected the scheme of the proof and the verification key to be equal, found " + p.scheme + " != " + vk.scheme_);
+        if (p.inputs.size() != vk.inputs_)
+            throw Error(ZKHIP_ERR_BAD_ARG, at + "verify: " + std::to_string(p.inputs.size()) + " public inputs for a verification key made for " + std::to_string(vk.inputs_));
+        try {
+            const std::vector<uint8_t> r = proof_record(p), in = proof_inputs(p);
+            recs.insert(recs.end(), r.begin(), r.end());
+            inputs.insert(inputs.end(), in.begin(), in.end());
+        } catch (const Error& e) {
+            throw Error(e.code, at + e.what());
+        }
+    }
+    std::vector<uint8_t> ok(proofs.size(), 0);
+    const auto call = vk.scheme_ == "gm17" ? zkhip_verify_gm17_batch : zkhip_verify_g16_batch;
+    check(call(ctx_, vk.vk_, proofs.size(), recs.data(), inputs.empty() ? nullptr : inputs.data(), ok.data()));
+    return std::vector<bool>(ok.begin(), ok.end());
+}
 }  // namespace zokrates_hip

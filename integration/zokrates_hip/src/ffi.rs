@@ -10,6 +10,7 @@ use std::os::raw::c_char;
 #[repr(C)] pub struct zkhip_assignment { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_queue { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_wplan { _p: [u8; 0] }
+#[repr(C)] pub struct zkhip_vk { _p: [u8; 0] }
 /// zkhip_queue_submit*: as many proofs in flight as the queue holds; collect one first
 pub const ZKHIP_ERR_BUSY: i32 = -6;
 /// 16 floats: h2d, matvec, ntt, msm_h, msm_z, finish, total, accum_g1, accum_g2, kernel_ntt, 6 reserved (milliseconds)
@@ -134,4 +135,15 @@ extern "C" {
     pub fn zkhip_multi_pk_load_g16_replicas(m: *mut zkhip_multi, curve: i32, bytes: *const u8, len: usize) -> i32;
     pub fn zkhip_prove_g16_multi_batch(m: *mut zkhip_multi, count: u32, z: *const u8, rs: *const u8, proofs_out: *mut u8,
         timings: *mut zkhip_timings) -> i32;
+    // verify on the device: one verdict per proof (a verifying key is the head of a proving key; proofs are the records the prove calls write)
+    pub fn zkhip_vk_load_g16(ctx: *mut zkhip_ctx, curve: i32, bytes: *const u8, len: usize, out: *mut *mut zkhip_vk) -> i32;
+    pub fn zkhip_vk_load_gm17(ctx: *mut zkhip_ctx, curve: i32, bytes: *const u8, len: usize, out: *mut *mut zkhip_vk) -> i32;
+    pub fn zkhip_vk_free(vk: *mut zkhip_vk);
+    pub fn zkhip_vk_dims(vk: *const zkhip_vk, out: *mut u64) -> i32;
+    pub fn zkhip_verify_g16_batch(ctx: *mut zkhip_ctx, vk: *const zkhip_vk, count: u64, proofs: *const u8, inputs: *const u8,
+        ok_out: *mut u8) -> i32;
+    pub fn zkhip_verify_gm17_batch(ctx: *mut zkhip_ctx, vk: *const zkhip_vk, count: u64, proofs: *const u8, inputs: *const u8,
+        ok_out: *mut u8) -> i32;
+    pub fn zkhip_pairing_products(ctx: *mut zkhip_ctx, curve: i32, count: u64, pairs_per_item: u32, g1: *const u8, g2: *const u8,
+        ok_out: *mut u8) -> i32;
 }

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libzkhip.so")
 UNITS = ["bls381_g1", "bls377_g1", "bn254_g2", "bls377_g2", "bls381_g2", "bn254_g1", "curve_bn254", "curve_bls381", "curve_bls377", "zkhip_api", "ingest"]   # slowest first
-HEADERS = ["core.cuh", "devrt.h", "ec.cuh", "field.cuh", "fieldu.cuh", "kernels_msm.cuh", "kernels_ntt.cuh", "setup.cuh", "gm17.cuh", "group.cuh", "bind.cuh", "ingest.h", "ntt_shard.h", "zpack.cuh", "wingest.cuh", "wplan.h"]
+HEADERS = ["core.cuh", "devrt.h", "ec.cuh", "field.cuh", "fieldu.cuh", "kernels_msm.cuh", "kernels_ntt.cuh", "setup.cuh", "gm17.cuh", "group.cuh", "bind.cuh", "ingest.h", "ntt_shard.h", "zpack.cuh", "wingest.cuh", "wplan.h", "pairing.cuh", os.path.join("host", "pairing_numbers.h")]
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -95,7 +95,7 @@ def build_cli(force=False, verbose=False):
     """The compiled host side (include/zkhip_backend.hpp, csrc/host/backend.cpp) and its `generate-proof` executable: plain C++17
     over the C ABI, linked against the in-tree libzkhip.so (found next to the executable through $ORIGIN)."""
     srcs = [os.path.join(CSRC, "host", f) for f in ("backend.cpp", "verify.cpp", "cli_main.cpp")]
-    deps = srcs + [os.path.join(HERE, "..", "include", h) for h in ("zkhip.h", "zkhip_backend.hpp")] + [os.path.join(CSRC, h) for h in ("field.cuh", "fieldu.cuh", "ec.cuh")] + [LIB]
+    deps = srcs + [os.path.join(HERE, "..", "include", h) for h in ("zkhip.h", "zkhip_backend.hpp")] + [os.path.join(CSRC, h) for h in ("field.cuh", "fieldu.cuh", "ec.cuh", os.path.join("host", "pairing_numbers.h"))] + [LIB]
     if not force and not _newer(CLI, deps):
         return CLI
     cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-pthread"] + srcs + ["-L" + HERE, "-lzkhip", "-Wl,-rpath,$ORIGIN", "-Wl,--allow-shlib-undefined", "-o", CLI]

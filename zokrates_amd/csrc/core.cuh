@@ -249,6 +249,9 @@ struct zkhip_ctx {
     zkhip_queue* queue = nullptr; // the open proof queue of this context (zkhip_queue_open .. zkhip_queue_close): the context is pending
     DBuf tmp;
     DBuf wraw, wowner;        // the bytes of the witness file being ordered and the entry that owns each column (Prover::ingest_z); kept between calls
+    Stream verify_stream = 0; // the pairing checks (pairing.cuh): a stream and buffers of their own, so that they may run while a proof queue is open
+    bool verify_made = false;
+    DBuf vfy[11];
     DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed, zkhip_queue_submit_packed); kept between calls
     std::vector<std::unique_ptr<NttPlanBase>> plans;
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
@@ -3047,6 +3050,7 @@ struct Prover {
 
 #include "setup.cuh"
 #include "gm17.cuh"
+#include "pairing.cuh"
 
 // ------------------------------------------------------------------ per-curve entry points
 namespace zk {
@@ -3104,6 +3108,12 @@ struct CurveOps {
     void (*field_op)(zkhip_ctx*, int field, int op, u64, const uint8_t*, const uint8_t*, uint8_t*);
     void (*group_op)(zkhip_ctx*, int group, int form, int op, u64, const u32*, const u32*, const u32*, const uint8_t*, u32*);
     void (*setup)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, u64);
+    // the pairing check on the device (pairing.cuh)
+    void (*pairing_products)(zkhip_ctx*, u64 count, u32 pairs_per_item, const uint8_t* g1, const uint8_t* g2, uint8_t* ok_out);
+    void (*tower_op)(zkhip_ctx*, int op, u64 count, const u32*, const u32*, u32*);
+    void (*vk_load)(zkhip_ctx*, int scheme, const uint8_t*, size_t, zkhip_vk*);
+    void (*verify)(zkhip_ctx*, const zkhip_vk*, u64 count, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok_out);
+    u32 tower_limbs;          // limbs of one Fq element in the unsaturated form
     // GM17 (gm17.cuh)
     void (*gm17_prove)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, const uint8_t*, const void*, const uint8_t*, uint8_t*, zkhip_timings*);
     void (*gm17_prove_batch)(zkhip_ctx*, const zkhip_pk*, const zkhip_r1cs*, u32, const uint8_t*, void* const*, const uint8_t*, uint8_t*,
@@ -3189,6 +3199,11 @@ static CurveOps make_curve_ops() {
     o.field_op = &field_op_dispatch<C>;
     o.group_op = &group_op_dispatch<C>;
     o.setup = &Setup<C>::run;
+    o.pairing_products = &PairingDev<C>::products;
+    o.tower_op = &PairingDev<C>::tower_op;
+    o.vk_load = &PairingDev<C>::vk_load;
+    o.verify = &PairingDev<C>::verify;
+    o.tower_limbs = (u32)Fu<typename C::Fq::Params>::N;
     o.gm17_prove = &Gm17<C>::prove;
     o.gm17_prove_batch = &Gm17<C>::prove_batch;
     o.gm17_setup = &Gm17<C>::setup;

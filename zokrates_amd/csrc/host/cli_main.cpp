@@ -1,7 +1,7 @@
 // zkhip-cli — `zokrates generate-proof` for the hip backend, as a native executable over zkhip_backend.hpp.
 //
 //   zkhip-cli generate-proof -i out -w witness -p proving.key -j proof.json [-s g16|gm17] [--entropy TEXT]
-//                            [--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--compact-witness] [--device-witness]
+//                            [--key-cache DIR] [--device N] [--timings] [--verify [--device-verify]] [--check] [--compact-witness] [--device-witness]
 //
 // Mirrors /root/reference/zokrates_cli/src/ops/generate_proof.rs:95-202: the compiled program (`out`), the witness and the
 // proving key are read from files, the proof is written as JSON, one proof per process; `--entropy` seeds the RNG as
@@ -70,9 +70,9 @@ std::pair<int, int> cpu_and_node() {
 }
 int usage() {
     fprintf(stderr, "usage: zkhip-cli generate-proof -i <out> -w <witness> -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] "
-                    "[--key-cache DIR] [--device N] [--timings] [--verify] [--check] [--compact-witness] [--device-witness] [--full-tables]\n"
+                    "[--key-cache DIR] [--device N] [--timings] [--verify [--device-verify]] [--check] [--compact-witness] [--device-witness] [--full-tables]\n"
                     "       zkhip-cli setup -i <out> -p <proving.key> -v <verification.key> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
-                    "       zkhip-cli verify [-v <verification.key>] [-j <proof.json>]\n"
+                    "       zkhip-cli verify [-v <verification.key>] [-j <proof.json>] [--device] [--timings [--repeat N]]\n"
                     "       zkhip-cli print-proof [-j <proof.json>] [-f remix|json]\n");
     return 2;
 }
@@ -128,19 +128,50 @@ static std::string slurp(const std::string& path) {
 // come from the two files and must agree; "Performing verification..." then PASSED or FAILED, exit status 0 for both; no GPU)
 int cmd_verify(int argc, char** argv) {
     std::string vk_path = "verification.key", proof_path = "proof.json";
+    bool on_device = false, timings = false;
+    int repeat = 1;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(2); } return argv[++i]; };
         if (a == "-v" || a == "--verification-key-path") vk_path = val();
         else if (a == "-j" || a == "--proof-path") proof_path = val();
         else if (a == "-b" || a == "--backend") val();          // accepted and ignored: there is one verifier here
+        else if (a == "--device") on_device = true;             // the pairing check on the GPU (Hip::verify_batch): the same text and status
+        else if (a == "--timings") timings = true;              // a last line `timings {"verify_ms": [..]}`: the check alone, once per --repeat
+        else if (a == "--repeat") repeat = std::max(1, atoi(val().c_str()));
         else return usage();
     }
     try {
         const VerificationKey vk = VerificationKey::from_json(slurp(vk_path));
         const Proof proof = Proof::from_json(slurp(proof_path));
         printf("Performing verification...\n");
-        printf("%s\n", verify(vk, proof) ? "PASSED" : "FAILED");
+        bool ok = false;
+        std::vector<double> ms;
+        if (on_device) {
+            if (proof.curve != vk.curve)
+                throw Error(ZKHIP_ERR_BAD_ARG, "Expected the curve of the proof and the verification key to be equal, found " + proof.curve + " != " + vk.curve);
+            if (proof.scheme != vk.scheme)
+                throw Error(ZKHIP_ERR_BAD_ARG, "Expected the scheme of the proof and the verification key to be equal, found " + proof.scheme + " != " + vk.scheme);
+            Hip hip(0);
+            const DeviceVerificationKey dvk = hip.load_verification_key(vk);
+            for (int k = 0; k < repeat; ++k) {
+                const auto t0 = std::chrono::steady_clock::now();
+                ok = hip.verify_batch(dvk, {proof})[0];
+                ms.push_back(ms_since(t0));
+            }
+        } else {
+            for (int k = 0; k < repeat; ++k) {
+                const auto t0 = std::chrono::steady_clock::now();
+                ok = verify(vk, proof);
+                ms.push_back(ms_since(t0));
+            }
+        }
+        printf("%s\n", ok ? "PASSED" : "FAILED");
+        if (timings) {
+            std::string list;
+            for (double v : ms) { char buf[32]; snprintf(buf, sizeof buf, "%s%.3f", list.empty() ? "" : ", ", v); list += buf; }
+            printf("timings {\"verify_ms\": [%s]}\n", list.c_str());
+        }
         return 0;
     } catch (const std::exception& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -192,13 +223,14 @@ int main(int argc, char** argv) {
     if (argc >= 2 && strcmp(argv[1], "pairing-check") == 0) return cmd_pairing_check(argc, argv);
     if (argc < 2 || strcmp(argv[1], "generate-proof") != 0) return usage();
     std::string input = "out", witness_path = "witness", pk_path = "proving.key", proof_path = "proof.json", scheme_s = "g16", entropy, cache_dir;
-    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false, device_witness = false;
+    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false, device_witness = false, device_verify = false;
     int device = 0;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(2); } return argv[++i]; };
         if (a == "-i" || a == "--input") input = val();
         else if (a == "--verify") self_check = true;
+        else if (a == "--device-verify") device_verify = true;   // with --verify: that check on the GPU (Hip::verify_batch) instead of the host CPU
         else if (a == "--check") check_first = true;                 // the witness against the constraints, on the device, before proving
         else if (a == "--compact-witness") compact = true;           // the witness packed on the host and widened on the device when that halves it
         else if (a == "--device-witness") device_witness = true;     // the witness file's bytes tested, ordered and checked on the device (the same proof.json)
@@ -365,7 +397,14 @@ int main(int argc, char** argv) {
             head.resize(fixed + 8 + count * 2 * fq);
             if (count && !kf.read((char*)head.data() + fixed + 8, (std::streamsize)(count * 2 * fq))) throw Error(ZKHIP_ERR_PARSE, "proving key too short for its verification key");
             const VerificationKey vk = VerificationKey::from_json(verification_key_json(scheme, curve, head.data(), head.size()));
-            if (!verify(vk, proof)) {
+            bool verified;
+            if (device_verify) {
+                const DeviceVerificationKey dvk = hip.load_verification_key(vk);
+                verified = hip.verify_batch(dvk, {proof})[0];
+            } else {
+                verified = verify(vk, proof);
+            }
+            if (!verified) {
                 remove(proof_path.c_str());
                 throw Error(ZKHIP_ERR_UNSATISFIED, "the proof does not verify against the key of " + pk_path +
                                                        (check_first ? " (a key for another program: the witness satisfies this one)"

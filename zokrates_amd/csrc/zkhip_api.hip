@@ -86,6 +86,35 @@ static int32_t guarded(zkhip_ctx* ctx, Fn&& fn, bool while_pending = false) {
     }
 }
 
+// The pairing checks work on a stream and in buffers of their own and touch no proof slot: an open proof queue does not refuse
+// them (checking collected proofs between submits is what they are for), a pending split proof does, as it refuses every call; and
+// a call that fails leaves the proofs in flight as they are (no release_slots: nothing of theirs is this call's)
+template <class Fn>
+static int32_t guarded_verify(zkhip_ctx* ctx, Fn&& fn) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    if (split_pending(ctx)) {
+        ctx->err = SPLIT_PENDING_MSG;
+        return ZKHIP_ERR_BAD_ARG;
+    }
+    try {
+        dev_set(ctx->device);
+        fn();
+        return ZKHIP_OK;
+    } catch (const ApiError& e) {
+        ctx->err = e.msg;
+        return e.code;
+    } catch (const DevError& e) {
+        ctx->err = e.msg;
+        return ZKHIP_ERR_DEVICE;
+    } catch (const std::bad_alloc&) {
+        ctx->err = "out of host memory";
+        return ZKHIP_ERR_NOMEM;
+    } catch (...) {
+        ctx->err = "unexpected internal error";
+        return ZKHIP_ERR_DEVICE;
+    }
+}
+
 template <class Fn>
 static int32_t guarded_host(Fn&& fn) {
     try {
@@ -375,6 +404,7 @@ void zkhip_ctx_free(zkhip_ctx* ctx) {
     if (ctx->ntt_lone_made) stream_destroy(ctx->ntt_lone_stream);
     if (ctx->out_made) stream_destroy(ctx->out_stream);
     if (ctx->ntt_made) stream_destroy(ctx->ntt_stream);
+    if (ctx->verify_made) stream_destroy(ctx->verify_stream);
     stream_destroy(ctx->stream);
     delete ctx;
 }
@@ -941,6 +971,64 @@ int32_t zkhip_group_op(zkhip_ctx* ctx, int32_t curve, int32_t group, int32_t for
         require(group_op_known(group, form, op), ZKHIP_ERR_BAD_ARG, "unknown group, form or operation (or no such operation for this group and form)");
         require(count <= ((u64)1 << 24), ZKHIP_ERR_BAD_ARG, "count too large");
         ops_for(curve)->group_op(ctx, group, form, op, count, a, b, k, flags, out);
+    });
+}
+
+int32_t zkhip_pairing_products(zkhip_ctx* ctx, int32_t curve, uint64_t count, uint32_t pairs_per_item, const uint8_t* g1, const uint8_t* g2, uint8_t* ok_out) {
+    return guarded_verify(ctx, [&] {
+        const CurveOps* ops = ops_for(curve);
+        if (count == 0) return;
+        require(g1 && g2 && ok_out, ZKHIP_ERR_BAD_ARG, "null argument");
+        require(pairs_per_item >= 1 && pairs_per_item <= PAIR_MAX_PAIRS, ZKHIP_ERR_BAD_ARG, "pairs_per_item must be 1 .. 8 (one lane of an item's group per pair)");
+        require(count <= ((u64)1 << 24), ZKHIP_ERR_BAD_ARG, "count too large");
+        ops->pairing_products(ctx, count, pairs_per_item, g1, g2, ok_out);
+    });
+}
+static int32_t vk_load(zkhip_ctx* ctx, int32_t curve, int scheme, const uint8_t* bytes, size_t len, zkhip_vk** out) {
+    return guarded_verify(ctx, [&] {
+        require(bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        std::unique_ptr<zkhip_vk> vk(new zkhip_vk());
+        vk->curve = curve;
+        vk->ctx = ctx;
+        ops_for(curve)->vk_load(ctx, scheme, bytes, len, vk.get());
+        *out = vk.release();
+    });
+}
+int32_t zkhip_vk_load_g16(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_vk** out) { return vk_load(ctx, curve, 0, bytes, len, out); }
+int32_t zkhip_vk_load_gm17(zkhip_ctx* ctx, int32_t curve, const uint8_t* bytes, size_t len, zkhip_vk** out) { return vk_load(ctx, curve, 1, bytes, len, out); }
+void zkhip_vk_free(zkhip_vk* vk) { delete vk; }
+int32_t zkhip_vk_dims(const zkhip_vk* vk, uint64_t out[2]) {
+    if (!vk || !out) return ZKHIP_ERR_BAD_ARG;
+    out[0] = vk->nq - 1;
+    out[1] = (uint64_t)vk->scheme;
+    return ZKHIP_OK;
+}
+static int32_t verify_batch(zkhip_ctx* ctx, const zkhip_vk* vk, int scheme, uint64_t count, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok_out) {
+    return guarded_verify(ctx, [&] {
+        require(vk, ZKHIP_ERR_BAD_ARG, "null argument");
+        require(vk->ctx == ctx, ZKHIP_ERR_BAD_ARG, "the verifying key belongs to another context");
+        require(vk->scheme == scheme, ZKHIP_ERR_BAD_ARG, scheme ? "a Groth16 verifying key was handed to the GM17 call" : "a GM17 verifying key was handed to the Groth16 call");
+        if (count == 0) return;
+        require(proofs && ok_out && (inputs || vk->nq == 1), ZKHIP_ERR_BAD_ARG, "null argument");
+        require(count <= ((u64)1 << 22) && count * vk->nq <= ((u64)1 << 28), ZKHIP_ERR_BAD_ARG, "count too large");
+        ops_for(vk->curve)->verify(ctx, vk, count, proofs, inputs, ok_out);
+    });
+}
+int32_t zkhip_verify_g16_batch(zkhip_ctx* ctx, const zkhip_vk* vk, uint64_t count, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok_out) {
+    return verify_batch(ctx, vk, 0, count, proofs, inputs, ok_out);
+}
+int32_t zkhip_verify_gm17_batch(zkhip_ctx* ctx, const zkhip_vk* vk, uint64_t count, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok_out) {
+    return verify_batch(ctx, vk, 1, count, proofs, inputs, ok_out);
+}
+int32_t zkhip_tower_op(zkhip_ctx* ctx, int32_t curve, int32_t op, uint64_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+    return guarded_verify(ctx, [&] {
+        const CurveOps* ops = ops_for(curve);
+        require(op >= 0 && op < TOWER_OPS, ZKHIP_ERR_BAD_ARG, "unknown tower operation");
+        if (count == 0) return;
+        require(a && b && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        require(count <= ((u64)1 << 20), ZKHIP_ERR_BAD_ARG, "count too large");
+        ops->tower_op(ctx, op, count, a, b, out);
     });
 }
 

@@ -78,6 +78,8 @@ class Library:
         "zkhip_queue_close",
         "zkhip_multi_ntt", "zkhip_multi_witness_map", "zkhip_multi_transform_shard", "zkhip_multi_last_shard",
         "zkhip_wplan_create", "zkhip_wplan_free", "zkhip_assignment_upload_witness", "zkhip_queue_submit_witness", "zkhip_queue_collect_inputs",
+        "zkhip_pairing_products", "zkhip_tower_op", "zkhip_vk_load_g16", "zkhip_vk_load_gm17", "zkhip_vk_free", "zkhip_vk_dims",
+        "zkhip_verify_g16_batch", "zkhip_verify_gm17_batch",
     ]
 
     def __init__(self, path=None):
@@ -129,6 +131,14 @@ class Library:
         L.zkhip_msm_g2.restype = i32; L.zkhip_msm_g2.argtypes = [vp, i32, u64, vp, vp, vp]
         L.zkhip_field_op.restype = i32; L.zkhip_field_op.argtypes = [vp, i32, i32, i32, u64, vp, vp, vp]
         L.zkhip_group_op.restype = i32; L.zkhip_group_op.argtypes = [vp, i32, i32, i32, i32, u64, vp, vp, vp, vp, vp]
+        L.zkhip_pairing_products.restype = i32; L.zkhip_pairing_products.argtypes = [vp, i32, u64, u32, vp, vp, vp]
+        L.zkhip_tower_op.restype = i32; L.zkhip_tower_op.argtypes = [vp, i32, i32, u64, vp, vp, vp]
+        L.zkhip_vk_load_g16.restype = i32; L.zkhip_vk_load_g16.argtypes = [vp, i32, vp, sz, pp]
+        L.zkhip_vk_load_gm17.restype = i32; L.zkhip_vk_load_gm17.argtypes = [vp, i32, vp, sz, pp]
+        L.zkhip_vk_free.restype = None; L.zkhip_vk_free.argtypes = [vp]
+        L.zkhip_vk_dims.restype = i32; L.zkhip_vk_dims.argtypes = [vp, vp]
+        L.zkhip_verify_g16_batch.restype = i32; L.zkhip_verify_g16_batch.argtypes = [vp, vp, u64, vp, vp, vp]
+        L.zkhip_verify_gm17_batch.restype = i32; L.zkhip_verify_gm17_batch.argtypes = [vp, vp, u64, vp, vp, vp]
         L.zkhip_setup_g16_size.restype = i32; L.zkhip_setup_g16_size.argtypes = [vp, vp]
         L.zkhip_setup_g16.restype = i32; L.zkhip_setup_g16.argtypes = [vp, vp, vp, vp, vp, vp, u64]
         L.zkhip_describe.restype = i32; L.zkhip_describe.argtypes = [vp, vp, sz]
@@ -347,6 +357,32 @@ class Context:
                                               _ptr(a), _ptr(b), _ptr(k), _ptr(flags), _ptr(out)))
         return out
 
+    def pairing_products(self, curve_id, pairs_per_item, g1, g2):
+        """zkhip_pairing_products: g1 / g2 are the point records of a proof (canonical little-endian coordinates and a flag byte, non-zero =
+        the point at infinity), count x pairs_per_item of each; returns count bytes, 1 where the product of the item's pairings is 1.
+        `ok` starts as 0xff so that a caller can see a call that wrote nothing."""
+        fq = FQ_BYTES[curve_id]
+        g1 = _u8(g1); g2 = _u8(g2)
+        n = g1.size // (2 * fq + 1)
+        if pairs_per_item < 1 or g1.size != n * (2 * fq + 1) or g2.size != n * (4 * fq + 1) or n % pairs_per_item:
+            raise ValueError("operand shapes")
+        ok = np.full(n // pairs_per_item, 0xff, dtype=np.uint8)
+        self.last_ok = ok
+        self._check(self.lib.L.zkhip_pairing_products(self.h, curve_id, n // pairs_per_item, pairs_per_item, _ptr(g1), _ptr(g2), _ptr(ok)))
+        return ok
+
+    last_ok = None      # the verdict buffer of the last pairing_products / verify_*_batch call, also where the call failed (tests: 0xff = not written)
+    TOWER_OPS = ["mul", "sqr", "mul_line", "inv", "frobenius", "conj6"]       # (the ids of include/zkhip.h, in order)
+
+    def tower_op(self, curve_id, op, a, b):
+        """TESTS ONLY (zkhip_tower_op): a, b: uint32 arrays of count x 6 x 2 x N raw limbs; returns the raw result limbs in the shape of `a`."""
+        a = np.ascontiguousarray(a, dtype=np.uint32); b = np.ascontiguousarray(b, dtype=np.uint32)
+        if a.shape != b.shape or a.ndim != 4 or a.shape[1:3] != (6, 2):
+            raise ValueError("operand shapes")
+        out = np.zeros_like(a)
+        self._check(self.lib.L.zkhip_tower_op(self.h, curve_id, self.TOWER_OPS.index(op) if isinstance(op, str) else op, a.shape[0], _ptr(a), _ptr(b), _ptr(out)))
+        return out
+
 
 class ProvingKey:
     """`zkhip_pk`: an ark `proving.key` resident on the GPU in MSM-ready layout."""
@@ -422,6 +458,55 @@ class ProvingKey:
             self.close()
         except Exception:
             pass
+
+
+class VerificationKey:
+    """`zkhip_vk`: ark's VerifyingKey (the head of a `proving.key`, so the whole key's bytes serve), admitted and resident on the GPU."""
+
+    def __init__(self, ctx, curve_id, data, scheme="g16"):
+        self.ctx, self.curve_id, self.scheme = ctx, curve_id, scheme
+        data = _u8(data)
+        self.h = C.c_void_p()
+        load = ctx.lib.L.zkhip_vk_load_gm17 if scheme == "gm17" else ctx.lib.L.zkhip_vk_load_g16
+        ctx._check(load(ctx.h, curve_id, _ptr(data), data.size, C.byref(self.h)))
+        d = np.zeros(2, dtype=np.uint64)
+        ctx._check(ctx.lib.L.zkhip_vk_dims(self.h, _ptr(d)))
+        self.l = int(d[0])
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.zkhip_vk_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _verify_batch(fn, ctx, vk, proofs, inputs):
+    nb = FQ_BYTES[vk.curve_id]
+    proofs = _u8(b"".join(proofs) if isinstance(proofs, (list, tuple)) else proofs)
+    count = proofs.size // (8 * nb + 3)
+    inputs = _u8(inputs, count * vk.l * 32)
+    if proofs.size != count * (8 * nb + 3):
+        raise ValueError("proof records")
+    ok = np.full(count, 0xff, dtype=np.uint8)
+    ctx.last_ok = ok
+    ctx._check(fn(ctx.h, vk.h, count, _ptr(proofs), _ptr(inputs) if inputs.size else None, _ptr(ok)))
+    return ok
+
+
+def verify_g16_batch(ctx, vk, proofs, inputs):
+    """`zkhip_verify_g16_batch`: proofs = the records zkhip_prove_g16 writes (bytes or a list of them), inputs = count x l x 32 B
+    canonical little-endian; returns count bytes of 0 / 1 (the buffer starts as 0xff: a failed call leaves it so)."""
+    return _verify_batch(ctx.lib.L.zkhip_verify_g16_batch, ctx, vk, proofs, inputs)
+
+
+def verify_gm17_batch(ctx, vk, proofs, inputs):
+    """`zkhip_verify_gm17_batch`: as verify_g16_batch for GM17 proofs and keys."""
+    return _verify_batch(ctx.lib.L.zkhip_verify_gm17_batch, ctx, vk, proofs, inputs)
 
 
 class ConstraintSystem:
