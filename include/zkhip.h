@@ -732,6 +732,13 @@ int32_t zkhip_prove_g16_split_end(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhi
                                   zkhip_timings* timings);
 int32_t zkhip_prove_g16_split_abort(zkhip_ctx* ctx);
 int32_t zkhip_r1cs_fingerprint(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, uint64_t out[2]);
+/* How the sparse mat-vec (K1) of a proof over `r1cs` is launched — read-only, no device work; for tests and tools that have to
+ * know which path their data takes.  lanes[k]: work-items that share a row of A, B, C in a launch over all three matrices (1, 2,
+ * 4, 8 or 16: the largest power of two <= half the average length of the matrix's rows of at most 32 terms, so 16 needs
+ * every row to have exactly 32).  n_long: rows of 33 to 512 terms (a wavefront each); n_huge: rows of more than 512 terms (a
+ * workgroup each), over the three matrices together.  A launch over fewer matrices (a bound key: A and B; one half of a split
+ * proof: one of them) uses the same width for those it runs. */
+int32_t zkhip_r1cs_matvec_shape(const zkhip_r1cs* r1cs, int32_t lanes[3], uint64_t* n_long, uint64_t* n_huge);
 int32_t zkhip_pk_is_bound(const zkhip_pk* pk, const zkhip_r1cs* r1cs);
 
 /* ---- "next" row N1: ZoKrates' own input files (host only: no context, no device work) ----

@@ -36,6 +36,25 @@ def test_binding_covers_the_header():
     assert sorted(native.Library.SYMBOLS) == declared_functions()
 
 
+def test_matvec_shape_query_is_declared_bound_and_refuses_null():
+    """zkhip_r1cs_matvec_shape (what tests/test_matvec_widths.py asserts its widths through) is in the header and in the binding, and
+    answers ZKHIP_ERR_BAD_ARG, not a crash, for a null handle or a null result."""
+    import ctypes as C
+    from emu_util import emu_library
+    assert "zkhip_r1cs_matvec_shape" in declared_functions() and "zkhip_r1cs_matvec_shape" in native.Library.SYMBOLS
+    fn = emu_library().L.zkhip_r1cs_matvec_shape
+    lanes, a, b = (C.c_int32 * 3)(), C.c_uint64(), C.c_uint64()
+    assert fn(None, lanes, C.byref(a), C.byref(b)) == -1
+    ctx = native.Context(0, emu_library())
+    rp = [0, 1]
+    one = (1).to_bytes(32, "little")
+    cs = native.ConstraintSystem(ctx, 0, 1, 1, 1, [(rp, [0], one), (rp, [1], one), (rp, [1], one)])
+    assert fn(cs.h, None, C.byref(a), C.byref(b)) == -1 and fn(cs.h, lanes, None, C.byref(b)) == -1 and fn(cs.h, lanes, C.byref(a), None) == -1
+    assert cs.matvec_shape() == ((1, 1, 1), 0, 0)
+    cs.close()
+    ctx.close()
+
+
 def test_no_cpu_fallback(lib_path):
     """On a machine without a GPU the product library refuses to create a context (ZKHIP_ERR_DEVICE)."""
     lib = native.Library(lib_path)

@@ -1060,6 +1060,11 @@ struct zkhip_r1cs {
     u64 fp[2] = {0, 0};   // PkLoader::r1cs_fingerprint, computed when first asked for
     bool fp_made = false;
 };
+// lanes per row of k_matvec for a launch over the matrices [mat0, mat0 + nmat) (a matrix outside the launch counts as 1):
+// what Prover::matvec launches with and what zkhip_r1cs_matvec_shape reports
+static inline void matvec_lanes(const zkhip_r1cs* cs, int g[3], int nmat = 3, int mat0 = 0) {
+    for (int k = 0; k < 3; ++k) g[k] = (k >= mat0 && k < mat0 + nmat) ? matvec_group(cs->nnz_short[k], cs->n) : 1;
+}
 // the matrices of a resident constraint system back in host memory (setup, N3: key generation walks them on the host; the
 // prover never needs them there, so zkhip_r1cs_load keeps no host copy).  Values come back as they are resident:
 // saturated Montgomery form.
@@ -1891,7 +1896,7 @@ struct Prover {
     // (`mat0`: the first matrix of the launch — a member of a multi-GPU proof that transforms b only runs mat0 = 1, nmat = 1)
     static void matvec(zkhip_ctx* ctx, const zkhip_r1cs* cs, const Fr* zmont, Fr* a, Fr* b, Fr* c, u64 n, u64 l, u64 N, int nmat = 3, int mat0 = 0) {
         int g[3];
-        for (int k = 0; k < 3; ++k) g[k] = (k >= mat0 && k < mat0 + nmat) ? matvec_group(cs->nnz_short[k], cs->n) : 1;
+        matvec_lanes(cs, g, nmat, mat0);
         ZK_LAUNCH((k_matvec<Fr>), dim3(blocks_for(N, 256 / gmax_rows(g)), nmat), dim3(256), 0, ctx->ws, csr(cs, 0), csr(cs, 1), csr(cs, 2), zmont, a, b, c, n,
                   l, N, g[0], g[1], g[2], cs->l + cs->w, mat0);
         if (cs->n_huge)

@@ -199,8 +199,9 @@ struct CsrDev {
 };
 // grid.y = 3 (A, B, C).  out_m[i] = <M_i, z> for i < n; A additionally gets z[j] at n + j (j < l)
 // ("input consistency" rows); everything up to N is zero-filled.
-// A row is shared by G consecutive work-items (G = gA/gB/gC, a power of two <= 64 chosen from the matrix's average row
-// length): compiler-made circuits have combinations of tens to hundreds of terms (every partial Poseidon round, every
+// A row is shared by G consecutive work-items (G = gA/gB/gC, one of 1, 2, 4, 8, 16, chosen by matvec_group from the average
+// length of the matrix's rows of at most MATVEC_LONG terms; 16 only when every row has exactly 32 terms; 32 and 64 cannot
+// occur, because the long rows are left out of that average): compiler-made circuits have combinations of tens to hundreds of terms (every partial Poseidon round, every
 // SHA-256 word sum), which one work-item per row would walk serially with a dependent random gather per term.  The G
 // partial sums meet in an LDS tree.  G = 1 is the plain one-row-per-work-item kernel.
 // Rows of more than MATVEC_LONG terms are left to k_matvec_long (a wavefront per row): the reference's optimizer inlines every
@@ -335,11 +336,15 @@ __global__ void __launch_bounds__(256) k_r1cs_check(const Fe<P>* __restrict__ a,
         atomicAdd(&verdict[1], (unsigned long long)__builtin_popcountll(failing));
     }
 }
-// lanes per row for a matrix with `nnz` entries in `n` rows: the largest power of two <= half the average row length
+// lanes per row for a matrix with `nnz` entries in its rows of at most MATVEC_LONG terms, `n` rows in all: the largest power of
+// two <= half the average.  That average is at most MATVEC_LONG = 32 (reached only when every row has exactly 32 terms), so the
+// result is one of 1, 2, 4, 8, 16; the bound of the loop says so and changes no result.
+static constexpr int MATVEC_MAX_LANES = 16;
+static_assert((u64)MATVEC_MAX_LANES * 4 > MATVEC_LONG, "the average row length never asks for more lanes than MATVEC_MAX_LANES");
 static inline int matvec_group(u64 nnz, u64 n) {
     const u64 avg = n ? nnz / n : 0;
     int g = 1;
-    while (g < 64 && (u64)g * 4 <= avg) g *= 2;
+    while (g < MATVEC_MAX_LANES && (u64)g * 4 <= avg) g *= 2;
     return g;
 }
 

@@ -562,6 +562,15 @@ int32_t zkhip_r1cs_fingerprint(zkhip_ctx* ctx, const zkhip_r1cs* r1cs, uint64_t 
         out[0] = fp[0]; out[1] = fp[1];
     });
 }
+int32_t zkhip_r1cs_matvec_shape(const zkhip_r1cs* r1cs, int32_t lanes[3], uint64_t* n_long, uint64_t* n_huge) {
+    if (!r1cs || !lanes || !n_long || !n_huge) return ZKHIP_ERR_BAD_ARG;
+    int g[3];
+    matvec_lanes(r1cs, g);
+    for (int k = 0; k < 3; ++k) lanes[k] = g[k];
+    *n_long = r1cs->n_long - r1cs->n_huge;      // (the list of long rows begins with the huge ones)
+    *n_huge = r1cs->n_huge;
+    return ZKHIP_OK;
+}
 int32_t zkhip_pk_is_bound(const zkhip_pk* pk, const zkhip_r1cs* r1cs) {
     if (!pk || !r1cs) return 0;
     return pk->bound_uid != 0 && pk->bound_uid == r1cs->uid ? 1 : 0;

@@ -66,6 +66,7 @@ class Library:
         "zkhip_prog_r1cs_load", "zkhip_prog_assignment", "zkhip_prog_write_bound", "zkhip_prog_write",
         "zkhip_pk_export_size", "zkhip_pk_export", "zkhip_pk_import",
         "zkhip_pk_bind_r1cs", "zkhip_pk_unbind", "zkhip_pk_is_bound", "zkhip_pk_bind_r1cs_shard", "zkhip_r1cs_fingerprint",
+        "zkhip_r1cs_matvec_shape",
         "zkhip_ctx_tune", "zkhip_init", "zkhip_ctx_clock_probe", "zkhip_multi_bind", "zkhip_multi_unbind",
         "zkhip_multi_transform_split", "zkhip_multi_last_split", "zkhip_prove_g16_split_begin", "zkhip_prove_g16_split_end", "zkhip_prove_g16_split_abort",
         "zkhip_ctx_create_multi", "zkhip_multi_free", "zkhip_multi_size", "zkhip_multi_ctx", "zkhip_multi_last_error", "zkhip_multi_r1cs_load",
@@ -159,6 +160,7 @@ class Library:
         L.zkhip_pk_is_bound.restype = i32; L.zkhip_pk_is_bound.argtypes = [vp, vp]
         L.zkhip_pk_bind_r1cs_shard.restype = i32; L.zkhip_pk_bind_r1cs_shard.argtypes = [vp, vp, vp, vp, sz]
         L.zkhip_r1cs_fingerprint.restype = i32; L.zkhip_r1cs_fingerprint.argtypes = [vp, vp, vp]
+        L.zkhip_r1cs_matvec_shape.restype = i32; L.zkhip_r1cs_matvec_shape.argtypes = [vp, vp, vp, vp]
         L.zkhip_init.restype = i32; L.zkhip_init.argtypes = [i32]
         L.zkhip_ctx_clock_probe.restype = i32; L.zkhip_ctx_clock_probe.argtypes = [vp, u32, vp]
         L.zkhip_multi_bind.restype = i32; L.zkhip_multi_bind.argtypes = [vp, vp, sz]
@@ -534,6 +536,16 @@ class ConstraintSystem:
         out = np.zeros(2, dtype=np.uint64)
         self.ctx._check(self.ctx.lib.L.zkhip_r1cs_fingerprint(self.ctx.h, self.h, _ptr(out)))
         return int(out[0]), int(out[1])
+
+    def matvec_shape(self):
+        """`zkhip_r1cs_matvec_shape`: ((lanes per row of A, B, C), rows left to k_matvec_long, rows left to k_matvec_huge) as a
+        proof over this system launches its mat-vec."""
+        lanes = np.zeros(3, dtype=np.int32)
+        n_long, n_huge = C.c_uint64(), C.c_uint64()
+        rc = self.ctx.lib.L.zkhip_r1cs_matvec_shape(self.h, _ptr(lanes), C.byref(n_long), C.byref(n_huge))
+        if rc != 0:
+            raise ZkhipError(rc, "zkhip_r1cs_matvec_shape")
+        return tuple(int(g) for g in lanes), int(n_long.value), int(n_huge.value)
 
     def check(self, z):
         """`zkhip_r1cs_check`: Az o Bz == Cz on the device for a host assignment (uint8[m*32]) or a resident `Assignment`.
