@@ -6,9 +6,10 @@ proof's MSMs (msm_shape over resident tables: a function of the key's size) and 
 module holds
 
   * the SHAPE MODEL: msm_shape (table mode and ad-hoc mode) and the split and geometry of get_plan, restated in plain Python from
-    csrc/core.cuh.  Where the library reports what it chose — the header of a key image (zkhip_pk_export) carries c_z, c_h and the
-    transform split — the check functions assert the model against it; the ad-hoc width is reported nowhere and the model stands
-    alone there, as `adhoc_window` always did;
+    csrc/core.cuh and csrc/ntt_geom.h.  Where the library reports what it chose — the header of a key image (zkhip_pk_export)
+    carries c_z, c_h and the transform split — the check functions assert the model against it, and
+    tests/test_size_ladder.py::test_the_model_of_the_plan_geometry_against_the_library holds ntt_plan to csrc/ntt_geom.h key by key;
+    the ad-hoc width is reported nowhere and the model stands alone there, as `adhoc_window` always did;
   * the RUNG LISTS of the transforms, the proofs and the ad-hoc MSM, and what the model says each rung reaches (`coverage`);
   * the CHECK FUNCTIONS, byte-exact against oracle.cpu (BN254, BLS12-381), tests/bls377_ref.py (BLS12-377) or a closed form.  Nothing
     compares the device with itself or with the emulator, and nothing has a tolerance.
@@ -91,7 +92,7 @@ NTT_SINGLE_MAX_LOG, NTT_MAX_SUBLOG, NTT_COLS = 10, 11, 2          # the defaults
 
 
 def ntt_plan(logN, single_max=NTT_SINGLE_MAX_LOG, sub=NTT_MAX_SUBLOG, ccols=NTT_COLS):
-    """The split and launch geometry of get_plan for a domain of 2^logN."""
+    """The split and launch geometry of get_plan (csrc/ntt_geom.h: ntt_geom) for a domain of 2^logN."""
     assert 0 <= logN <= 3 * sub
     if logN <= single_max and logN <= sub:
         log1, log2, log3 = 0, logN, 0

@@ -25,6 +25,10 @@ A rung needs three closed forms (the batch of three over two assignments) and, f
 L = 13 for Groth16 and 9 s for GM17, 12 s and 17 s at L = 14.  The top rung of that curve is therefore L = 13, where the reference of
 a CASE (not of a single proof: that would be L = 16 and a case of 40 s) stays at about ten seconds; the two schemes are cases of
 their own."""
+import json
+import os
+import subprocess
+
 import pytest
 
 import size_ladder as sl
@@ -123,6 +127,30 @@ def test_the_model_of_the_plan_geometry():
     assert p["smem_cols"] == 9 * 2 * (2048 + 64 + 1) * 4
     p = sl.ntt_plan(23)
     assert (p["log1"], p["log2"], p["log3"], p["split"]) == (7, 8, 8, 7 | (8 << 8))
+
+
+def test_the_model_of_the_plan_geometry_against_the_library(tmp_path):
+    """size_ladder.ntt_plan against the library's own arithmetic (csrc/ntt_geom.h, from which get_plan and every pass launcher take
+    their numbers), key by key, at every domain size under every setting of ntt_max_sublog (2 .. 11), ntt_single_max_log (0 .. 11)
+    and ntt_cols (1, 2).  tests/host/ntt_geom.cpp — a stand-alone program on the CPU, under ASan + UBSan — holds the header to the
+    rules written out on their own and prints the plan of every case."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "ntt_geom")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DZK_EMU", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-I", os.path.join(here, "..", "zokrates_amd", "csrc"),
+                           os.path.join(here, "host", "ntt_geom.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and " 0 failures" in out.stderr, out.stderr
+    seen = set()
+    for line in out.stdout.splitlines():
+        got = json.loads(line)
+        case = (got.pop("single_max"), got.pop("sub"), got.pop("ccols"), got["logN"])
+        seen.add(case)
+        want = sl.ntt_plan(case[3], single_max=case[0], sub=case[1], ccols=case[2])
+        assert sorted(got) == sorted(want), (case, sorted(got), sorted(want))
+        for key in want:
+            assert got[key] == want[key], (case, key, got[key], want[key])
+    assert seen == {(sm, sub, cc, lg) for sub in range(2, 12) for lg in range(0, min(3 * sub, 47) + 1) for sm in range(0, 12) for cc in (1, 2)}
 
 
 # ------------------------------------------------------------------ (b) transforms at every size

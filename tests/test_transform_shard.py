@@ -324,6 +324,29 @@ def test_gpu_ntt_three_pass(lib, G):
 
 
 @gpu
+@pytest.mark.parametrize("logn,G,plan", [(3, 2, TWO_PASS), (5, 4, TWO_PASS), (9, 8, THREE_PASS_3)], ids=["2x4-G2", "4x8-G4", "8x8x8-G8"])
+def test_gpu_ntt_whole_and_sharded_where_the_tile_binds(lib, logn, G, plan):
+    """One set of pass launchers runs the whole domain (zkhip_ntt on one context) and the strips and ranges of G members
+    (zkhip_multi_ntt): both against cpu.ntt, byte for byte, in all four directions, at the plans where a strip is narrower than the
+    plan's cols tile and a range has fewer rows than its rows tile — 2 x 4 over 2 members (G = N1 = Nb / 2: one row per range, two
+    columns per strip), 4 x 8 over 4, and 8 x 8 x 8 over 8.  A launcher that gave a strip the whole plan's tile would run off its end."""
+    p = ntt_plan(logn, **plan)
+    N1, Nb = 1 << p["log1"], 1 << (p["log2"] + p["log3"])
+    assert shardable(logn, G, plan) and p["passes"] == (3 if plan is THREE_PASS_3 else 2)
+    assert Nb // G < p["C_cols"] and (N1 // G) * Nb >> (p["log3"] or p["log2"]) < p["R_rows"]          # both tiles bind
+    a, want = ntt_reference(0, logn)
+    multi = members(lib, G, plan)
+    try:
+        ctx = multi.member_context(0)
+        for d in DIRS:
+            assert ctx.ntt(0, a, d).tobytes() == want[d], ("whole", logn, d)
+            assert multi.ntt(0, a, d).tobytes() == want[d], ("sharded", G, logn, d)
+            assert multi.last_shard() == G
+    finally:
+        multi.close()
+
+
+@gpu
 def test_gpu_ntt_2e20_eight_members(lib):
     ntt_against_member0(lib, 0, 8, 20, DIRS)
 

@@ -21,7 +21,7 @@
 
 #include "../../include/zkhip.h"
 #include "devrt.h"
-#include "ntt_shard.h"
+#include "ntt_geom.h"
 #include "ec.cuh"
 #include "kernels_msm.cuh"
 #include "kernels_ntt.cuh"
@@ -380,332 +380,9 @@ static inline void lds_opt_in(zkhip_ctx* ctx, const void* kernel) {
 #endif
 }
 
+#include "ntt_host.cuh"
+
 namespace zk {
-
-// ------------------------------------------------------------------ NTT plan
-template <class C>
-struct NttPlan : NttPlanBase {
-    typedef typename C::Fr Fr;
-    typedef Fu<typename Fr::Params> FrU;   // the passes' working form (kernels_ntt.cuh)
-    int log1, log2, log3;    // N = N1 * N2 * N3: cols pass over N1, (three passes, log3 > 0: cols pass over N2 inside every N2 x N3 block,) rows pass over the last factor
-    u64 N;
-    u32 N1, N2, N3, M;       // M = max(N1, N2, N3): root tables hold w_M^j, j < M; N3 = 1 for one or two passes
-    u64 Nb;                  // N2 * N3: the block of one outer index
-    int split() const { return log1 | (log3 << 8); }   // what the sigma order depends on besides N (zkhip_pk::ntt_log1, key images)
-    // roots: 9-limb R'-form; tw (inter-pass twiddles, the inverse ones times 1/N... see get_plan), s_coset (g^i / N, sigma
-    // order), s_cosetinv_canon (g^-i / N as plain integers: the Montgomery exit): packed, N entries each
-    DBuf roots_fwd, roots_inv, tw_fwd, tw_inv, s_coset, s_cosetinv_canon;
-    DBuf s_cexit;            // zinv / N as plain integers, N entries: exit factor of the transform that turns c's evaluations into
-                             // its share zinv * c_i of the quotient's coefficients (canonical integers)
-    DBuf tw2_fwd, tw2_inv;   // three passes: the twiddles inside a block, w_Nb^(k2 * j3), Nb entries
-    DBuf plan1[2], plan2[2], plan3[2];   // twiddle plans of the N1-, N2- and N3-point sub-NTTs, [0] forward, [1] inverse (kernels_ntt.cuh)
-    u32 plen1 = 0, plen2 = 0, plen3 = 0;
-    Fr omega, omega_inv, n_inv, g, g_inv, zinv;   // saturated Montgomery form (host code, setup)
-    Fr zinv_rp;                                   // zinv in R'-form (k_quotient)
-    Fr k_to_rp, k_mont_to_rp;                     // canonical integer -> R'-form, saturated Montgomery -> R'-form (fe_mul by these)
-    int C_cols, R_rows, threads_cols, threads_rows;
-    size_t smem_cols, smem_rows;
-    int C_mid = 1, threads_mid = 64;   // the middle pass of three: columns per workgroup, work-items
-    size_t smem_mid = 0;
-};
-
-template <class Fr>
-static Fr host_root_of_unity(int two_adicity, u64 generator, int logN) {
-    // GENERATOR^((r-1) >> S), then squared down to order 2^logN   (App. A.4)
-    u32 e[Fr::N];
-    u64 bw = 1;
-    for (int i = 0; i < Fr::N; ++i) {
-        u64 t = (u64)Fr::Params::mod(i) - bw;
-        e[i] = (u32)t;
-        bw = t >> 63;
-    }
-    for (int s = 0; s < two_adicity; ++s)
-        for (int i = 0; i < Fr::N; ++i) e[i] = (e[i] >> 1) | (i + 1 < Fr::N ? e[i + 1] << 31 : 0);
-    Fr root = fe_pow(fe_from_u64<typename Fr::Params>(generator), e, Fr::N);
-    for (int i = logN; i < two_adicity; ++i) root = fe_sqr(root);
-    return root;
-}
-
-static constexpr int NTT_MAX_SUBLOG = 11;   // 2^11 x 32 B = 64 KiB per staged sequence
-
-template <class C>
-static NttPlan<C>* get_plan(zkhip_ctx* ctx, int logN) {
-    typedef typename C::Fr Fr;
-    for (auto& p : ctx->plans)
-        if (p->curve == C::ID && p->logN == logN) return (NttPlan<C>*)p.get();
-    const int sub = ctx->ntt_max_sublog;
-    require(logN >= 0 && logN <= 3 * sub && logN <= C::TWO_ADICITY, ZKHIP_ERR_BAD_ARG,
-            "domain size unsupported (log2 N must not exceed the field's two-adicity: 28 for bn128, 32 for bls12_381, 47 for bls12_377)");
-    auto* pl = new NttPlan<C>();
-    ctx->plans.emplace_back(pl);
-    pl->curve = C::ID;
-    pl->logN = logN;
-    pl->N = (u64)1 << logN;
-    // one pass up to 2^ntt_single_max, two passes (N1 x N2) up to 2^(2 sub), three (N1 x N2 x N3) beyond: the reference's
-    // radix-2 domain goes up to the field's two-adicity (ark-poly Radix2EvaluationDomain), so does this one
-    if (logN <= ctx->ntt_single_max && logN <= sub) { pl->log1 = 0; pl->log2 = logN; pl->log3 = 0; }
-    else if (logN <= 2 * sub) { pl->log1 = logN / 2; pl->log2 = logN - pl->log1; pl->log3 = 0; }
-    else { pl->log1 = logN / 3; pl->log2 = (logN - pl->log1) / 2; pl->log3 = logN - pl->log1 - pl->log2; }
-    pl->N1 = 1u << pl->log1;
-    pl->N2 = 1u << pl->log2;
-    pl->N3 = 1u << pl->log3;
-    pl->Nb = (u64)pl->N2 * pl->N3;
-    pl->M = std::max(pl->N1, std::max(pl->N2, pl->N3));
-    pl->omega = host_root_of_unity<Fr>(C::TWO_ADICITY, C::GENERATOR, logN);
-    pl->omega_inv = fe_inv(pl->omega);
-    pl->n_inv = fe_inv(fe_from_u64<typename Fr::Params>(pl->N));
-    pl->g = fe_from_u64<typename Fr::Params>(C::GENERATOR);
-    pl->g_inv = fe_inv(pl->g);
-    pl->zinv = fe_inv(fe_sub(fe_pow_u64(pl->g, pl->N), Fr::one()));
-    Stream s = ctx->stream;
-    const unsigned T = 256;
-    // R' = 2^(29*9) as a canonical integer mod p: Fr::one() is the integer 2^256 mod p, doubled 5 more times
-    Fr rp = Fr::one();
-    for (int i = 32 * Fr::N; i < Fu<typename Fr::Params>::B * Fu<typename Fr::Params>::N; ++i) rp = fe_add(rp, rp);
-    pl->k_mont_to_rp = rp;                    // fe_mul(x R, R') = x R'
-    pl->k_to_rp = fe_to_mont(rp);             // fe_mul(x, R' R) = x R'
-    pl->zinv_rp = fe_mul(pl->zinv, rp);
-    typedef typename NttPlan<C>::FrU FrU;
-    auto to_rp = [&](DBuf& buf, u64 count) {  // saturated Montgomery table -> packed R'-form, in place
-        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(count, T)), dim3(T), 0, s, ptr<Fr>(buf), ptr<Fr>(buf), count, rp);
-    };
-    // sub-NTT roots: w_M^j, j < M (the radix-4 butterflies use w^pos, w^2pos, w^3pos), as 9-limb R'-form values
-    const Fr wM = fe_pow_u64(pl->omega, pl->N / pl->M);
-    const u64 nroots = std::max<u64>(pl->M, 1);
-    ctx->tmp.ensure(nroots * sizeof(Fr));
-    for (int inv = 0; inv < 2; ++inv) {
-        DBuf& dst = inv ? pl->roots_inv : pl->roots_fwd;
-        dst.ensure(nroots * sizeof(FrU));
-        ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(nroots, T)), dim3(T), 0, s, ptr<Fr>(ctx->tmp), inv ? fe_inv(wM) : wM, Fr::one(), nroots, 0u, 0u, 0, 1u);
-        to_rp(ctx->tmp, nroots);
-        ZK_LAUNCH((k_unpack_table<typename Fr::Params>), dim3(blocks_for(nroots, T)), dim3(T), 0, s, ptr<Fr>(ctx->tmp), ptr<FrU>(dst), nroots);
-    }
-    // the sub-NTTs' twiddle plans, gathered from the root tables
-    {
-        std::vector<u32> src;
-        DBuf d_src;
-        for (int which = 0; which < 3; ++which) {
-            if (which == 2 && pl->log3 == 0) break;
-            const int lg = which == 0 ? pl->log1 : which == 1 ? pl->log2 : pl->log3;
-            const u32 plen = ntt_plan_len(lg);
-            (which == 0 ? pl->plen1 : which == 1 ? pl->plen2 : pl->plen3) = plen;
-            ntt_plan_exponents(lg, src);
-            d_src.ensure(src.size() * 4);
-            dev_h2d(d_src.p, src.data(), src.size() * 4, s);
-            for (int inv = 0; inv < 2; ++inv) {
-                DBuf& dst = which == 0 ? pl->plan1[inv] : which == 1 ? pl->plan2[inv] : pl->plan3[inv];
-                dst.ensure((size_t)plen * NTT_PLAN_STRIDE * 4);
-                ZK_LAUNCH((k_ntt_plan_gather<typename Fr::Params>), dim3(blocks_for(plen, T)), dim3(T), 0, s, ptr<FrU>(inv ? pl->roots_inv : pl->roots_fwd),
-                          (int)(pl->M >> lg), ptr<u32>(d_src), plen, ptr<u32>(dst));
-            }
-            stream_sync(s);   // src is reused
-        }
-    }
-    if (pl->log1 > 0) {
-        // between the pass over N1 and what follows: w_N^(k1 * j), j < Nb the position inside the block of k1
-        pl->tw_fwd.ensure(pl->N * sizeof(Fr));
-        pl->tw_inv.ensure(pl->N * sizeof(Fr));
-        ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->N, T)), dim3(T), 0, s, ptr<Fr>(pl->tw_fwd), pl->omega, Fr::one(), pl->N, pl->N1, (u32)pl->Nb, 1, 1u);
-        ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->N, T)), dim3(T), 0, s, ptr<Fr>(pl->tw_inv), pl->omega_inv, Fr::one(), pl->N, pl->N1, (u32)pl->Nb, 1, 1u);
-        to_rp(pl->tw_fwd, pl->N);
-        to_rp(pl->tw_inv, pl->N);
-    }
-    if (pl->log3 > 0) {
-        // inside a block: w_Nb^(k2 * j3), the two-pass rule once more (w_Nb = w_N^N1)
-        const Fr wb = fe_pow_u64(pl->omega, pl->N1), wb_inv = fe_pow_u64(pl->omega_inv, pl->N1);
-        pl->tw2_fwd.ensure(pl->Nb * sizeof(Fr));
-        pl->tw2_inv.ensure(pl->Nb * sizeof(Fr));
-        ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->Nb, T)), dim3(T), 0, s, ptr<Fr>(pl->tw2_fwd), wb, Fr::one(), pl->Nb, pl->N2, pl->N3, 1, 1u);
-        ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->Nb, T)), dim3(T), 0, s, ptr<Fr>(pl->tw2_inv), wb_inv, Fr::one(), pl->Nb, pl->N2, pl->N3, 1, 1u);
-        to_rp(pl->tw2_fwd, pl->Nb);
-        to_rp(pl->tw2_inv, pl->Nb);
-    }
-    pl->s_coset.ensure(pl->N * sizeof(Fr));
-    pl->s_cosetinv_canon.ensure(pl->N * sizeof(Fr));
-    ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->N, T)), dim3(T), 0, s, ptr<Fr>(pl->s_coset), pl->g, pl->n_inv, pl->N, pl->N1, pl->N2, 2, pl->N3);
-    to_rp(pl->s_coset, pl->N);
-    // plain integers: multiplying an R'-form value by them (R' Montgomery product) leaves the plain value
-    ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->N, T)), dim3(T), 0, s, ptr<Fr>(pl->s_cosetinv_canon), pl->g_inv, fe_from_mont(pl->n_inv), pl->N,
-              pl->N1, pl->N2, 2, pl->N3);
-    pl->s_cexit.ensure(pl->N * sizeof(Fr));
-    ZK_LAUNCH((k_pow_table<Fr>), dim3(blocks_for(pl->N, T)), dim3(T), 0, s, ptr<Fr>(pl->s_cexit), Fr::one(), fe_from_mont(fe_mul(pl->n_inv, pl->zinv)), pl->N,
-              0u, 0u, 0, 1u);
-    // launch geometry.  A workgroup stages `tile` elements as nine limb planes (36 B + padding per element): tiles of
-    // 1024 elements (38 KiB) let four workgroups share a CU, so that one loads while another computes; a cols tile
-    // needs >= 2 columns for 64-byte rows in HBM.
-    const u32 last = pl->log3 > 0 ? pl->N3 : pl->N2;                        // length of the rows pass's sequences
-    const u64 nrows = pl->N / last;
-    const u32 tile_rows = std::max<u32>(last, (u32)std::min<u64>(pl->N, 1024));
-    u32 R = pl->log1 == 0 ? 1 : (u32)std::max<u64>(1, std::min<u64>(nrows, tile_rows / last));
-    pl->R_rows = (int)R;
-    const u32 ccols = (u32)ctx->ntt_cols;
-    auto cols_per_wg = [&](u64 ncols, u32 n) { return (int)std::max<u64>(1, std::min<u64>(ncols, std::max<u32>(ccols, 1024 / std::max<u32>(n, 1)))); };
-    pl->C_cols = cols_per_wg(pl->Nb, pl->N1);
-    require(pl->Nb % (u64)pl->C_cols == 0 && nrows % R == 0, ZKHIP_ERR_BAD_ARG, "internal: NTT tile does not divide the domain");
-    auto smem_for = [](u32 nseq, u32 n) { return (size_t)9 * nseq * ntt_seq_stride((int)n) * 4; };
-    pl->smem_cols = smem_for(pl->C_cols, pl->N1);
-    pl->smem_rows = smem_for(R, last);
-    auto pick_threads = [](u64 butterflies) { return (int)std::min<u64>(512, std::max<u64>(64, (butterflies + 63) / 64 * 64)); };
-    pl->threads_cols = pick_threads((u64)pl->C_cols * pl->N1 / 4);
-    pl->threads_rows = pick_threads((u64)R * last / 4);
-    if (pl->log3 > 0) {
-        pl->C_mid = cols_per_wg(pl->N3, pl->N2);
-        require(pl->N3 % (u32)pl->C_mid == 0, ZKHIP_ERR_BAD_ARG, "internal: NTT tile does not divide the domain");
-        pl->smem_mid = smem_for(pl->C_mid, pl->N2);
-        pl->threads_mid = pick_threads((u64)pl->C_mid * pl->N2 / 4);
-        require(pl->N1 <= 65535, ZKHIP_ERR_BAD_ARG, "internal: NTT batch exceeds the grid");
-    }
-    lds_opt_in(ctx, (const void*)k_ntt_cols<typename Fr::Params>);
-    lds_opt_in(ctx, (const void*)k_ntt_rows<typename Fr::Params>);
-    stream_sync(s);
-    return pl;
-}
-
-// `nvec` vectors of N elements, vec_stride elements apart, go through one launch (grid.y)
-// the pass over N1: columns of the N1 x Nb matrix
-template <class C>
-static void ntt_cols(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool inverse, const typename C::Fr* post, int nvec = 1, u64 vec_stride = 0,
-                     int canon = 0, const typename C::Fr* minus = nullptr) {
-    typedef typename C::Fr Fr;
-    ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3((unsigned)(pl->Nb / pl->C_cols), nvec), dim3(pl->threads_cols), pl->smem_cols, ctx->ws, data, vec_stride,
-              pl->log1, (u32)pl->Nb, pl->C_cols, ptr<u32>(pl->plan1[inverse ? 1 : 0]), pl->plen1, post, canon, minus, (u64)0, ~(u64)0, ctx->ntt_fuse_first);
-}
-// three passes only — the pass over N2: columns of the N2 x N3 matrix of every outer index (grid.z).  `post_mask`: Nb - 1 for
-// the per-block twiddles, all ones for a table as long as the vector.
-template <class C>
-static void ntt_mid(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool inverse, const typename C::Fr* post, u64 post_mask, int nvec, u64 vec_stride) {
-    typedef typename C::Fr Fr;
-    ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3(pl->N3 / pl->C_mid, nvec, pl->N1), dim3(pl->threads_mid), pl->smem_mid, ctx->ws, data, vec_stride,
-              pl->log2, pl->N3, pl->C_mid, ptr<u32>(pl->plan2[inverse ? 1 : 0]), pl->plen2, post, 0, (const Fr*)nullptr, pl->Nb, post_mask, ctx->ntt_fuse_first);
-}
-// the pass over the last factor: contiguous sequences
-template <class C>
-static void ntt_rows(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool inverse, const typename C::Fr* post, int nvec = 1, u64 vec_stride = 0,
-                     int canon = 0, const typename C::Fr* minus = nullptr, u64 post_mask = ~(u64)0) {
-    typedef typename C::Fr Fr;
-    const bool three = pl->log3 > 0;
-    const int lg = three ? pl->log3 : pl->log2;
-    ZK_LAUNCH((k_ntt_rows<typename Fr::Params>), dim3((unsigned)((pl->N >> lg) / pl->R_rows), nvec), dim3(pl->threads_rows), pl->smem_rows, ctx->ws, data, vec_stride,
-              lg, pl->R_rows, ptr<u32>((three ? pl->plan3 : pl->plan2)[inverse ? 1 : 0]), three ? pl->plen3 : pl->plen2, post, canon, minus, post_mask,
-              ctx->ntt_fuse_first);
-}
-// natural order in -> sigma order out
-template <class C>
-static void ntt_kind_a(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool inverse, const typename C::Fr* final_post, int nvec = 1,
-                       u64 vec_stride = 0, int canon = 0, const typename C::Fr* final_minus = nullptr) {
-    typedef typename C::Fr Fr;
-    if (pl->log1 > 0) ntt_cols<C>(ctx, pl, data, inverse, inverse ? ptr<Fr>(pl->tw_inv) : ptr<Fr>(pl->tw_fwd), nvec, vec_stride);
-    if (pl->log3 > 0) ntt_mid<C>(ctx, pl, data, inverse, inverse ? ptr<Fr>(pl->tw2_inv) : ptr<Fr>(pl->tw2_fwd), pl->Nb - 1, nvec, vec_stride);
-    ntt_rows<C>(ctx, pl, data, inverse, final_post, nvec, vec_stride, canon, final_minus);
-}
-// sigma order in -> natural order out
-template <class C>
-static void ntt_kind_b(zkhip_ctx* ctx, NttPlan<C>* pl, typename C::Fr* data, bool inverse, const typename C::Fr* final_post, int nvec = 1,
-                       u64 vec_stride = 0, int canon = 0) {
-    typedef typename C::Fr Fr;
-    if (pl->log3 > 0) {
-        ntt_rows<C>(ctx, pl, data, inverse, inverse ? ptr<Fr>(pl->tw2_inv) : ptr<Fr>(pl->tw2_fwd), nvec, vec_stride, 0, nullptr, pl->Nb - 1);
-        ntt_mid<C>(ctx, pl, data, inverse, inverse ? ptr<Fr>(pl->tw_inv) : ptr<Fr>(pl->tw_fwd), ~(u64)0, nvec, vec_stride);
-        ntt_cols<C>(ctx, pl, data, inverse, final_post, nvec, vec_stride, canon);
-    } else if (pl->log1 > 0) {
-        ntt_rows<C>(ctx, pl, data, inverse, inverse ? ptr<Fr>(pl->tw_inv) : ptr<Fr>(pl->tw_fwd), nvec, vec_stride);
-        ntt_cols<C>(ctx, pl, data, inverse, final_post, nvec, vec_stride, canon);
-    } else {
-        ntt_rows<C>(ctx, pl, data, inverse, final_post, nvec, vec_stride, canon);
-    }
-}
-
-// ------------------------------------------------------------------ transforms sharded across the members of a zkhip_multi
-// (ntt_shard.h: member k runs the outer pass on its strip of columns and every other pass on its range of rows, one all-to-all
-// between them.)  The passes are the plan's kernels over a strip or a range of the full-length vector: a pointer offset, a smaller
-// grid, a tile that fits — columns per workgroup <= the strip's width, rows per workgroup <= the rows of the range; `post` and
-// `minus` tables as long as the vector move with the data, tables per block (post_mask = Nb - 1) stay: a range starts on a
-// multiple of Nb.
-template <class C>
-static bool shard_ok(const NttPlan<C>* pl, size_t G) { return ntt_shardable(pl->log1, pl->N1, pl->Nb, G); }
-static inline size_t ntt_smem_for(u32 nseq, u32 n) { return (size_t)9 * nseq * ntt_seq_stride((int)n) * 4; }
-static inline int ntt_threads_for(u64 butterflies) { return (int)std::min<u64>(512, std::max<u64>(64, (butterflies + 63) / 64 * 64)); }
-template <class C>
-static void shard_cols(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, typename C::Fr* data, bool inverse, const typename C::Fr* post, int nvec,
-                       u64 vec_stride, int canon = 0) {
-    typedef typename C::Fr Fr;
-    const int Cw = (int)std::min<u32>((u32)pl->C_cols, g.W);
-    const u64 off = g.strip_origin(k);
-    ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3((unsigned)(g.W / (u32)Cw), nvec), dim3(ntt_threads_for((u64)Cw * pl->N1 / 4)), ntt_smem_for((u32)Cw, pl->N1),
-              ctx->ws, data + off, vec_stride, pl->log1, (u32)pl->Nb, Cw, ptr<u32>(pl->plan1[inverse ? 1 : 0]), pl->plen1, post ? post + off : post, canon,
-              (const Fr*)nullptr, (u64)0, ~(u64)0, ctx->ntt_fuse_first);
-}
-template <class C>
-static void shard_mid(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, typename C::Fr* data, bool inverse, const typename C::Fr* post, u64 post_mask,
-                      int nvec, u64 vec_stride) {
-    typedef typename C::Fr Fr;
-    const u64 off = g.range_origin(k);
-    ZK_LAUNCH((k_ntt_cols<typename Fr::Params>), dim3(pl->N3 / pl->C_mid, nvec, g.rows), dim3(pl->threads_mid), pl->smem_mid, ctx->ws, data + off, vec_stride,
-              pl->log2, pl->N3, pl->C_mid, ptr<u32>(pl->plan2[inverse ? 1 : 0]), pl->plen2, (post && post_mask == ~(u64)0) ? post + off : post, 0, (const Fr*)nullptr,
-              pl->Nb, post_mask, ctx->ntt_fuse_first);
-}
-template <class C>
-static void shard_rows(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, typename C::Fr* data, bool inverse, const typename C::Fr* post, int nvec,
-                       u64 vec_stride, int canon = 0, const typename C::Fr* minus = nullptr, u64 post_mask = ~(u64)0) {
-    typedef typename C::Fr Fr;
-    const bool three = pl->log3 > 0;
-    const int lg = three ? pl->log3 : pl->log2;
-    const u64 off = g.range_origin(k), nrows = g.range_len() >> lg;
-    const u32 R = (u32)std::min<u64>((u64)pl->R_rows, nrows), last = 1u << lg;
-    ZK_LAUNCH((k_ntt_rows<typename Fr::Params>), dim3((unsigned)(nrows / R), nvec), dim3(ntt_threads_for((u64)R * last / 4)), ntt_smem_for(R, last), ctx->ws,
-              data + off, vec_stride, lg, (int)R, ptr<u32>((three ? pl->plan3 : pl->plan2)[inverse ? 1 : 0]), three ? pl->plen3 : pl->plen2,
-              (post && post_mask == ~(u64)0) ? post + off : post, canon, minus ? minus + off : minus, post_mask, ctx->ntt_fuse_first);
-}
-// the staging of member `ctx` for exchanges of up to `nvec` vectors, its two events
-static inline void shard_state(zkhip_ctx* ctx, const ShardGeom& g, u32 nvec) {
-    const size_t bytes = (size_t)g.staging_len(nvec) * 32;
-    ctx->shard.send[0].ensure(bytes);
-    ctx->shard.send[1].ensure(bytes);
-    ctx->shard.recv.ensure(bytes);
-    for (Event& e : ctx->shard.packed)
-        if (!e) e = event_create();
-}
-static inline ShardMove shard_move_args(const ShardGeom& g, u32 k, u64 vec_stride, bool by_row, bool own) {
-    ShardMove a;
-    a.vec_stride = vec_stride;
-    a.nb = g.Nb;
-    a.G = g.G;
-    a.me = k;
-    a.rows = g.rows;
-    a.log_w = ilog2_floor(g.W);
-    a.by_row = by_row ? 1 : 0;
-    a.own = own ? 1 : 0;
-    return a;
-}
-static inline unsigned shard_move_blocks(const ShardGeom& g) { return (unsigned)std::min<u64>(1024, std::max<u64>(1, (2 * g.block + 255) / 256)); }
-// first half of an exchange: this member's G - 1 foreign blocks of `nvec` vectors into the staging set of this turn, `packed` behind
-template <class C>
-static void shard_pack(zkhip_ctx* ctx, const ShardGeom& g, u32 k, const typename C::Fr* data, u32 nvec, u64 vec_stride, bool by_row) {
-    typedef typename C::Fr Fr;
-    zkhip_ctx::Shard& sh = ctx->shard;
-    const unsigned set = sh.turn & 1u;
-    ZK_LAUNCH((k_ntt_shard_pack<typename Fr::Params>), dim3(shard_move_blocks(g), nvec, g.G), dim3(256), 0, ctx->ws, data, ptr<Fr>(sh.send[set]),
-              shard_move_args(g, k, vec_stride, by_row, false));
-    event_record(sh.packed[set], ctx->ws);
-}
-// second half, entered only when EVERY member has packed (the caller's two phases): the blocks the peers packed for this member
-// travel into its staging behind their `packed` events, one launch scatters them
-template <class C>
-static void shard_fetch(zkhip_ctx* ctx, const ShardGeom& g, u32 k, typename C::Fr* data, u32 nvec, u64 vec_stride, bool by_row, zkhip_ctx* const* members) {
-    typedef typename C::Fr Fr;
-    zkhip_ctx::Shard& sh = ctx->shard;
-    const unsigned set = sh.turn & 1u;
-    for (u32 j = 0; j < g.G; ++j) {
-        if (j == k) continue;
-        event_sync(members[j]->shard.packed[set]);      // (the peer's stream, possibly on another device: waited for on the host, as split_fetch does)
-        for (u32 v = 0; v < nvec; ++v)
-            dev_copy_between(ptr<Fr>(sh.recv) + g.slot_origin(v, j), ctx->device, ptr<Fr>(members[j]->shard.send[set]) + g.slot_origin(v, k), members[j]->device,
-                             (size_t)g.block * sizeof(Fr), ctx->ws);
-    }
-    ZK_LAUNCH((k_ntt_shard_unpack<typename Fr::Params>), dim3(shard_move_blocks(g), nvec, g.G), dim3(256), 0, ctx->ws, data, ptr<Fr>(sh.recv),
-              shard_move_args(g, k, vec_stride, by_row, false));
-    ++sh.turn;
-}
 
 // ------------------------------------------------------------------ MSM driver
 struct MsmShape {
@@ -1886,6 +1563,7 @@ struct Prover {
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
     typedef SlotSums<C> Lay;
+    typedef Transforms<C> Tr;
     static constexpr int FQB = Fq::BYTES;
 
     static CsrDev csr(const zkhip_r1cs* cs, int k) { return CsrDev{ptr<u64>(cs->rp[k]), ptr<u32>(cs->col[k]), cs->val[k].p}; }
@@ -1926,31 +1604,19 @@ struct Prover {
             Fr* v = a + (u64)half * N;
             matvec(ctx, cs, ptr<Fr>(ctx->cur->zmont), a, b, c, cs->n, cs->l, N, 1, half);
             event_record(ctx->cur->ntt_b, s);
-            ntt_kind_a<C>(ctx, pl, v, true, ptr<Fr>(pl->s_coset), 1, 0);
-            ntt_kind_b<C>(ctx, pl, v, false, nullptr, 1, 0);
+            Tr::ntt_kind_a(ctx, pl, v, true, ptr<Fr>(pl->s_coset), 1, 0);
+            Tr::ntt_kind_b(ctx, pl, v, false, nullptr, 1, 0);
             event_record(ctx->cur->ntt_e, s);
             return;
         }
         matvec(ctx, cs, ptr<Fr>(ctx->cur->zmont), a, b, c, cs->n, cs->l, N, (bound && !check) ? 2 : 3);
         if (check) enqueue_check(*ctx->cur, a, b, c, cs->n, s);
         event_record(ctx->cur->ntt_b, s);
-        if (bound) {
-            ntt_kind_a<C>(ctx, pl, a, true, ptr<Fr>(pl->s_coset), 2, N);    // a, b: ifft, then * g^i
-            ntt_kind_b<C>(ctx, pl, a, false, nullptr, 2, N);                 // a, b: evaluations on g<w>, natural order
-            // (a plain-integer factor takes an R'-form product out of the Montgomery domain: canonical integers, the MSM's digits)
-            ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, s, a, b, fe_from_mont(pl->zinv), a, N);
-            event_record(ctx->cur->ntt_e, s);
-            return;
-        }
-        // SIX transforms (the reference's witness_map runs seven): a and b go to the coset and back as a product; c only needs
-        // its coefficients — ((ab - c)/Z)'s coefficients are coset_ifft(ab / Z) - c_coeffs / Z, because the coset transform pair is
-        // the identity on the c term — so c takes ONE inverse transform whose exit factor carries 1/(N Z) and leaves canonical
-        // integers, and the last transform subtracts them where it stores h.  Same h, bit for bit.
-        ntt_kind_a<C>(ctx, pl, a, true, ptr<Fr>(pl->s_coset), 2, N);    // a, b: ifft, then * g^i   (coset shift)
-        ntt_kind_a<C>(ctx, pl, c, true, ptr<Fr>(pl->s_cexit), 1, 0, 1);  // c: ifft * 1/(N Z), canonical integers, sigma order
-        ntt_kind_b<C>(ctx, pl, a, false, nullptr, 2, N);                 // a, b: evaluations on g<w>
-        ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, s, a, b, pl->zinv_rp, a, N);
-        ntt_kind_a<C>(ctx, pl, a, true, ptr<Fr>(pl->s_cosetinv_canon), 1, 0, 1, c);   // coset_ifft, canonical, minus c's share
+        // SIX transforms (the reference's witness_map runs seven; FOUR over a bound key): ntt_quotient, a and b through every pass together.
+        // Same h, bit for bit.
+        Tr::ntt_quotient(ctx, pl, a, 2, c, bound, [&](const Fr& zinv) {
+            ZK_LAUNCH((k_quotient<typename Fr::Params>), dim3(blocks_for(N, 256)), dim3(256), 0, s, a, b, zinv, a, N);
+        });
         event_record(ctx->cur->ntt_e, s);
     }
 
@@ -1983,12 +1649,6 @@ struct Prover {
                  (unsigned long long)cs->n, (unsigned long long)u.n_bad);
         throw ApiError{ZKHIP_ERR_UNSATISFIED, msg};
     }
-    // canonical integer -> R'-form factor (NttPlan::k_to_rp) without a plan: the stand-alone check transforms nothing
-    static Fr k_to_rp() {
-        Fr rp = Fr::one();
-        for (int i = 32 * Fr::N; i < Fu<typename Fr::Params>::B * Fu<typename Fr::Params>::N; ++i) rp = fe_add(rp, rp);
-        return fe_to_mont(rp);
-    }
     // zkhip_r1cs_check: the three mat-vecs over rows [0, n) and the test, nothing else; out = {lowest failing row or ~0, failing rows}
     static void r1cs_check(zkhip_ctx* ctx, const zkhip_r1cs* cs, const uint8_t* z_host, const void* z_dev, u64 out[2]) {
         ProofSlot& sl = *ctx->cur;
@@ -1997,7 +1657,8 @@ struct Prover {
         const u64 m = cs->l + cs->w, n = cs->n;
         const Fr* z = stage_z(ctx, sl, m, m + 2, z_host, z_dev, true, true);
         sl.zmont.ensure(m * 32);
-        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, s, z, ptr<Fr>(sl.zmont), m, k_to_rp());
+        // canonical integer -> R'-form (NttPlan::k_to_rp, without a plan: the stand-alone check transforms nothing)
+        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(m, 256)), dim3(256), 0, s, z, ptr<Fr>(sl.zmont), m, fe_to_mont(rp_factor<Fr>()));
         sl.vc.ensure(3 * std::max<u64>(n, 1) * sizeof(Fr));
         Fr *ra = ptr<Fr>(sl.vc), *rb = ra + n, *rc = rb + n;
         if (n) matvec(ctx, cs, ptr<Fr>(sl.zmont), ra, rb, rc, n, 0, n);
@@ -2580,7 +2241,7 @@ struct Prover {
     static int can_shard(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, u32 G, u32 k) {
         if (pk->scheme != 0 || is_bound(pk, cs)) return -1;
         const NttPlan<C>* pl = get_plan<C>(ctx, pk->logN);
-        return (shard_ok(pl, G) && pk->h_lo == (u64)k * (pl->N / G) && pk->h_n == pl->N / G) ? pl->split() : -1;
+        return (Tr::shard_ok(pl, G) && pk->h_lo == (u64)k * (pl->N / G) && pk->h_n == pl->N / G) ? pl->split() : -1;
     }
     static void shard_begin(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* cs, const uint8_t* z_host, const uint8_t* r, const uint8_t* s_, u32 G, u32 k) {
         ProofSlot& sl = ctx->slots[0];
@@ -2825,42 +2486,6 @@ struct Prover {
     static Aff<Fq> from_mont_point(const Aff<Fq>& p) { return {fe_from_mont(p.x), fe_from_mont(p.y)}; }
     static Aff<Fq2> from_mont_point(const Aff<Fq2>& p) { return {fe_from_mont(p.x), fe_from_mont(p.y)}; }
 
-    static void ntt_api(zkhip_ctx* ctx, u32 log_n, int dir, uint8_t* data) {
-        NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n);
-        Stream s = ctx->stream;
-        ctx->ws = s;
-        const u64 N = pl->N;
-        const unsigned T = 256, B = blocks_for(N, T);
-        ctx->cur->va.ensure(N * sizeof(Fr));
-        ctx->cur->vb.ensure(N * sizeof(Fr));
-        ctx->cur->vc.ensure(N * sizeof(Fr));
-        Fr *a = ptr<Fr>(ctx->cur->va), *b = ptr<Fr>(ctx->cur->vb), *t = ptr<Fr>(ctx->cur->vc);
-        dev_h2d(a, data, N * 32, s);
-        ZK_LAUNCH((k_mul_const<Fr>), dim3(B), dim3(T), 0, s, a, a, N, pl->k_to_rp);   // canonical -> R'-form
-        const bool inverse = dir == 1 || dir == 3;
-        if (dir == 2) {   // coset_fft: x_i * g^i first (a saturated-Montgomery factor keeps the R'-form)
-            ZK_LAUNCH((k_pow_table<Fr>), dim3(B), dim3(T), 0, s, t, pl->g, Fr::one(), N, 0u, 0u, 0);
-            ZK_LAUNCH((k_mul_table<Fr>), dim3(B), dim3(T), 0, s, a, t, a, N);
-        }
-        ntt_kind_a<C>(ctx, pl, a, inverse, nullptr, 1, 0, 1);
-        ZK_LAUNCH((k_sigma_permute<Fr>), dim3(B), dim3(T), 0, s, a, b, N, pl->N1, pl->N2, 1, pl->N3);
-        if (inverse) {    // * 1/N (and g^-i for coset_ifft)
-            ZK_LAUNCH((k_pow_table<Fr>), dim3(B), dim3(T), 0, s, t, dir == 3 ? pl->g_inv : Fr::one(), pl->n_inv, N, 0u, 0u, 0);
-            ZK_LAUNCH((k_mul_table<Fr>), dim3(B), dim3(T), 0, s, b, t, b, N);
-        }
-        ZK_LAUNCH((k_from_rp<Fr>), dim3(B), dim3(T), 0, s, b, b, N);
-        dev_d2h(data, b, N * 32, s);
-        stream_sync(s);
-        // A stand-alone transform of a very large domain leaves 8 N x 32 bytes behind (five factor tables of its plan, three work
-        // vectors: 69 GiB at 2^28) that nothing else will use at that size: given back at once.  A prover at such a domain keeps its
-        // plan (it is rebuilt in about a second if a transform of this kind evicted it).
-        if (log_n > 24) {
-            ctx->cur->va.release(); ctx->cur->vb.release(); ctx->cur->vc.release();
-            for (size_t k = 0; k < ctx->plans.size(); ++k)
-                if (ctx->plans[k].get() == pl) { ctx->plans.erase(ctx->plans.begin() + (long)k); break; }
-        }
-    }
-
     static void witness_map_api(zkhip_ctx* ctx, const zkhip_r1cs* cs, const uint8_t* z, uint8_t* h_out) {
         ctx->ws = ctx->stream;
         NttPlan<C>* pl = get_plan<C>(ctx, cs->logN);
@@ -2876,70 +2501,14 @@ struct Prover {
         stream_sync(ctx->stream);
     }
 
-    // ---- the same two calls over the members of a zkhip_multi, the domain sharded (ntt_shard.h).  Every step below is one member's
-    // part; the caller (zkhip_api.hip) runs a step on every member before the next on any, because a member fetches what its
-    // peers packed in the step before.
-    // (the plan's split if this member's plan shards over G members, else -1: the members must agree on it)
-    static int ntt_shardable_api(zkhip_ctx* ctx, u32 log_n, u32 G) { const NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n); return shard_ok(pl, G) ? pl->split() : -1; }
-    // zkhip_multi_ntt, first step: the member's strip of the input, the outer pass, its blocks packed
-    static void shard_ntt_begin(zkhip_ctx* ctx, u32 G, u32 k, u32 log_n, int dir, const uint8_t* data) {
-        NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n);
-        require(shard_ok(pl, G), ZKHIP_ERR_BAD_ARG, "internal: this transform does not shard");
-        const ShardGeom g = ntt_shard_geom(pl->N1, pl->Nb, G);
-        Stream s = ctx->stream;
-        ctx->ws = s;
-        ctx->cur->va.ensure(pl->N * sizeof(Fr));
-        shard_state(ctx, g, 1);
-        zkhip_ctx::Shard& sh = ctx->shard;
-        Fr* a = ptr<Fr>(ctx->cur->va);
-        // the strip arrives as the G blocks of its column of blocks, rows back to back: the layout of the staging
-        const u64 n = g.range_len();           // (a strip holds as many elements as a range)
-        sh.host.resize(n * 32);
-        for (u32 r = 0; r < pl->N1; ++r) memcpy(sh.host.data() + (size_t)r * g.W * 32, data + ((size_t)r * pl->Nb + g.strip_origin(k)) * 32, (size_t)g.W * 32);
-        dev_h2d(sh.recv.p, sh.host.data(), n * 32, s);
-        ZK_LAUNCH((k_mul_const<Fr>), dim3(blocks_for(n, 256)), dim3(256), 0, s, ptr<Fr>(sh.recv), ptr<Fr>(sh.recv), n, pl->k_to_rp);   // canonical -> R'-form
-        ZK_LAUNCH((k_ntt_shard_unpack<typename Fr::Params>), dim3(shard_move_blocks(g), 1, G), dim3(256), 0, s, a, ptr<Fr>(sh.recv), shard_move_args(g, k, 0, true, true));
-        if (dir == 2)     // coset_fft: x_i * g^i first
-            ZK_LAUNCH((k_shard_strip_pow<Fr>), dim3(blocks_for(n, 256)), dim3(256), 0, s, a + g.strip_origin(k), pl->g, pl->N1, ilog2_floor(g.W), pl->Nb, g.strip_origin(k));
-        const bool inverse = dir == 1 || dir == 3;
-        shard_cols<C>(ctx, pl, g, k, a, inverse, inverse ? ptr<Fr>(pl->tw_inv) : ptr<Fr>(pl->tw_fwd), 1, 0);
-        shard_pack<C>(ctx, g, k, a, 1, 0, true);
-    }
-    // second step: the peers' blocks, the passes over the member's range, and its part of the output in natural order
-    static void shard_ntt_end(zkhip_ctx* ctx, u32 G, u32 k, u32 log_n, int dir, uint8_t* data, zkhip_ctx* const* members) {
-        NttPlan<C>* pl = get_plan<C>(ctx, (int)log_n);
-        const ShardGeom g = ntt_shard_geom(pl->N1, pl->Nb, G);
-        Stream s = ctx->stream;
-        ctx->ws = s;
-        Fr* a = ptr<Fr>(ctx->cur->va);
-        const bool inverse = dir == 1 || dir == 3;
-        shard_fetch<C>(ctx, g, k, a, 1, 0, false, members);
-        if (pl->log3 > 0) shard_mid<C>(ctx, pl, g, k, a, inverse, inverse ? ptr<Fr>(pl->tw2_inv) : ptr<Fr>(pl->tw2_fwd), pl->Nb - 1, 1, 0);
-        shard_rows<C>(ctx, pl, g, k, a, inverse, nullptr, 1, 0, 1);
-        range_out(ctx, pl, g, k, a, inverse ? 2 : 1, dir == 3 ? pl->g_inv : Fr::one(), pl->n_inv, data);
-    }
-    // a member's range (sigma order) to the natural positions of the host vector `out` it holds: permuted (and scaled) on the device
-    // into runs of g.rows elements, one run per inner index
-    static void range_out(zkhip_ctx* ctx, NttPlan<C>* pl, const ShardGeom& g, u32 k, const Fr* vec, int mode, const Fr& base, const Fr& scale, uint8_t* out) {
-        zkhip_ctx::Shard& sh = ctx->shard;
-        Stream s = ctx->ws;
-        const u64 n = g.range_len();
-        sh.out.ensure(n * sizeof(Fr));
-        ZK_LAUNCH((k_shard_range_out<Fr>), dim3(blocks_for(n, 256)), dim3(256), 0, s, vec + g.range_origin(k), ptr<Fr>(sh.out), g.rows, pl->Nb, pl->N1, pl->N2, pl->N3,
-                  k * g.rows, mode, base, scale);
-        sh.host.resize(n * 32);
-        dev_d2h(sh.host.data(), sh.out.p, n * 32, s);
-        stream_sync(s);
-        for (u64 inner = 0; inner < pl->Nb; ++inner)
-            memcpy(out + (inner * pl->N1 + (u64)k * g.rows) * 32, sh.host.data() + inner * g.rows * 32, (size_t)g.rows * 32);
-    }
     // The witness map of `witness_map` (unbound: six transforms) in four steps around three all-to-alls; a, b, c in the slot's va,
     // on ctx->ws.  Step 0 ends with a, b, c packed behind their inverse transforms' outer pass; 1: their ranges (a, b leave with
     // s_coset, c with s_cexit as canonical integers), the coset transform's passes over the range, a and b packed; 2: its outer pass,
     // the quotient on the strip, the last transform's outer pass, one vector packed; 3: its range, canonical, minus c's share — the
-    // member's h coefficients are positions [k N/G, (k+1) N/G) of va, sigma order.
+    // member's h coefficients are positions [k N/G, (k+1) N/G) of va, sigma order.  (Every step is one member's part; the caller runs a
+    // step on every member before the next on any: ntt_host.cuh, shard_ntt_begin.)
     static void shard_witness_map(zkhip_ctx* ctx, const zkhip_r1cs* cs, NttPlan<C>* pl, u32 G, u32 k, int step, zkhip_ctx* const* members, bool check = false) {
-        require(shard_ok(pl, G), ZKHIP_ERR_BAD_ARG, "internal: this transform does not shard");
+        require(Tr::shard_ok(pl, G), ZKHIP_ERR_BAD_ARG, "internal: this transform does not shard");
         const ShardGeom g = ntt_shard_geom(pl->N1, pl->Nb, G);
         Stream s = ctx->ws;
         const u64 N = pl->N;
@@ -2948,40 +2517,40 @@ struct Prover {
         if (step == 0) {
             ctx->cur->va.ensure(3 * N * sizeof(Fr));
             a = ptr<Fr>(ctx->cur->va); b = a + N; c = b + N;
-            shard_state(ctx, g, 3);
+            Tr::shard_state(ctx, g, 3);
             matvec(ctx, cs, ptr<Fr>(ctx->cur->zmont), a, b, c, cs->n, cs->l, N, 3);
             if (check) enqueue_check(*ctx->cur, a, b, c, cs->n, s);
             event_record(ctx->cur->ntt_b, s);
-            shard_cols<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw_inv), 3, N);
-            shard_pack<C>(ctx, g, k, a, 3, N, true);
+            Tr::ntt_cols(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw_inv), 3, N);
+            Tr::shard_pack(ctx, g, k, a, 3, N, true);
         } else if (step == 1) {
-            shard_fetch<C>(ctx, g, k, a, 3, N, false, members);
-            if (three) shard_mid<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw2_inv), pl->Nb - 1, 3, N);
-            shard_rows<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->s_coset), 2, N);
-            shard_rows<C>(ctx, pl, g, k, c, true, ptr<Fr>(pl->s_cexit), 1, 0, 1);
+            Tr::shard_fetch(ctx, g, k, a, 3, N, false, members);
+            if (three) Tr::ntt_mid(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw2_inv), pl->Nb - 1, 3, N);
+            Tr::ntt_rows(ctx, pl, g, k, a, true, ptr<Fr>(pl->s_coset), 2, N);
+            Tr::ntt_rows(ctx, pl, g, k, c, true, ptr<Fr>(pl->s_cexit), 1, 0, 1);
             if (three) {
-                shard_rows<C>(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw2_fwd), 2, N, 0, nullptr, pl->Nb - 1);
-                shard_mid<C>(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw_fwd), ~(u64)0, 2, N);
+                Tr::ntt_rows(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw2_fwd), 2, N, 0, nullptr, pl->Nb - 1);
+                Tr::ntt_mid(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw_fwd), ~(u64)0, 2, N);
             } else {
-                shard_rows<C>(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw_fwd), 2, N);
+                Tr::ntt_rows(ctx, pl, g, k, a, false, ptr<Fr>(pl->tw_fwd), 2, N);
             }
-            shard_pack<C>(ctx, g, k, a, 2, N, false);
+            Tr::shard_pack(ctx, g, k, a, 2, N, false);
         } else if (step == 2) {
-            shard_fetch<C>(ctx, g, k, a, 2, N, true, members);
-            shard_cols<C>(ctx, pl, g, k, a, false, nullptr, 2, N);
+            Tr::shard_fetch(ctx, g, k, a, 2, N, true, members);
+            Tr::ntt_cols(ctx, pl, g, k, a, false, nullptr, 2, N);
             const u64 off = g.strip_origin(k);
             ZK_LAUNCH((k_quotient_strip<typename Fr::Params>), dim3(blocks_for(g.range_len(), 256)), dim3(256), 0, s, a + off, b + off, pl->zinv_rp, a + off, pl->N1,
                       ilog2_floor(g.W), pl->Nb);
-            shard_cols<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw_inv), 1, 0);
-            shard_pack<C>(ctx, g, k, a, 1, 0, true);
+            Tr::ntt_cols(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw_inv), 1, 0);
+            Tr::shard_pack(ctx, g, k, a, 1, 0, true);
         } else {
-            shard_fetch<C>(ctx, g, k, a, 1, 0, false, members);
-            if (three) shard_mid<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw2_inv), pl->Nb - 1, 1, 0);
-            shard_rows<C>(ctx, pl, g, k, a, true, ptr<Fr>(pl->s_cosetinv_canon), 1, 0, 1, c);
+            Tr::shard_fetch(ctx, g, k, a, 1, 0, false, members);
+            if (three) Tr::ntt_mid(ctx, pl, g, k, a, true, ptr<Fr>(pl->tw2_inv), pl->Nb - 1, 1, 0);
+            Tr::ntt_rows(ctx, pl, g, k, a, true, ptr<Fr>(pl->s_cosetinv_canon), 1, 0, 1, c);
             event_record(ctx->cur->ntt_e, s);
         }
     }
-    static int witness_map_shardable_api(zkhip_ctx* ctx, const zkhip_r1cs* cs, u32 G) { return ntt_shardable_api(ctx, (u32)cs->logN, G); }
+    static int witness_map_shardable_api(zkhip_ctx* ctx, const zkhip_r1cs* cs, u32 G) { return Tr::ntt_shardable_api(ctx, (u32)cs->logN, G); }
     // zkhip_multi_witness_map: step 0 stages the assignment first, step 3 hands the member's part of h out (h_out: N x 32 B, natural order)
     static void shard_witness_map_api(zkhip_ctx* ctx, const zkhip_r1cs* cs, const uint8_t* z, uint8_t* h_out, u32 G, u32 k, int step, zkhip_ctx* const* members) {
         ctx->ws = ctx->stream;
@@ -2993,7 +2562,7 @@ struct Prover {
             stage_scalars(ctx, pl, ctx->cur->scalars.p, m, zero, zero);
         }
         shard_witness_map(ctx, cs, pl, G, k, step, members);
-        if (step == 3) range_out(ctx, pl, ntt_shard_geom(pl->N1, pl->Nb, G), k, ptr<Fr>(ctx->cur->va), 0, Fr::one(), Fr::one(), h_out);
+        if (step == 3) Tr::range_out(ctx, pl, ntt_shard_geom(pl->N1, pl->Nb, G), k, ptr<Fr>(ctx->cur->va), 0, Fr::one(), Fr::one(), h_out);
     }
 
     // zkhip_field_op: count x (a op b) over elements F, canonical integers in and out, in workgroups of T; `launch` runs the kernel
@@ -3187,11 +2756,11 @@ static CurveOps make_curve_ops() {
     o.assignment_upload_packed = &Prover<C>::assignment_upload_packed;
     o.assignment_upload_witness = &Prover<C>::assignment_upload_witness;
     o.r1cs_check = &Prover<C>::r1cs_check;
-    o.ntt = &Prover<C>::ntt_api;
+    o.ntt = &Transforms<C>::ntt_api;
     o.witness_map = &Prover<C>::witness_map_api;
-    o.ntt_shardable = &Prover<C>::ntt_shardable_api;
-    o.shard_ntt_begin = &Prover<C>::shard_ntt_begin;
-    o.shard_ntt_end = &Prover<C>::shard_ntt_end;
+    o.ntt_shardable = &Transforms<C>::ntt_shardable_api;
+    o.shard_ntt_begin = &Transforms<C>::shard_ntt_begin;
+    o.shard_ntt_end = &Transforms<C>::shard_ntt_end;
     o.witness_map_shardable = &Prover<C>::witness_map_shardable_api;
     o.shard_witness_map = &Prover<C>::shard_witness_map_api;
     o.can_shard = &Prover<C>::can_shard;

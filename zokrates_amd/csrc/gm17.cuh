@@ -164,21 +164,12 @@ struct Gm17 {
         stream_wait_event(wn, sl.ev[1]);
         ctx->ws = wn;
         event_record(sl.ntt_b, wn);
-        if (bound) {
-            // TWO transforms: U to its coefficients and on to the coset; U^2 / Z(g) there, as canonical integers in NATURAL order (a
-            // plain-integer factor takes the R'-form product out of the Montgomery domain), pairs with G' = the coset inverse transform
-            // applied to g_gamma2_z_t once (PkLoader::bind) — and W's share rides on the c_query_1 lane's bases
-            ntt_kind_a<C>(ctx, pl, sa, true, ptr<Fr>(pl->s_coset), 1, 0);
-            ntt_kind_b<C>(ctx, pl, sa, false, nullptr, 1, 0);
-            ZK_LAUNCH((k_sap_quotient<typename Fr::Params>), dim3(blocks_for(D, 256)), dim3(256), 0, wn, sa, fe_from_mont(pl->zinv), sa, D);
-        } else {
-            // four transforms (ark-gm17's witness_map runs five): W only needs its coefficients, as c in the Groth16 prover
-            ntt_kind_a<C>(ctx, pl, sa, true, ptr<Fr>(pl->s_coset), 1, 0);
-            ntt_kind_a<C>(ctx, pl, sc, true, ptr<Fr>(pl->s_cexit), 1, 0, 1);
-            ntt_kind_b<C>(ctx, pl, sa, false, nullptr, 1, 0);
-            ZK_LAUNCH((k_sap_quotient<typename Fr::Params>), dim3(blocks_for(D, 256)), dim3(256), 0, wn, sa, pl->zinv_rp, sa, D);
-            ntt_kind_a<C>(ctx, pl, sa, true, ptr<Fr>(pl->s_cosetinv_canon), 1, 0, 1, sc);
-        }
+        // four transforms (ark-gm17's witness_map runs five): W only needs its coefficients, as c in the Groth16 prover.  A bound key:
+        // TWO — U^2 / Z(g) in NATURAL order pairs with G' = the coset inverse transform applied to g_gamma2_z_t once (PkLoader::bind),
+        // and W's share rides on the c_query_1 lane's bases
+        Transforms<C>::ntt_quotient(ctx, pl, sa, 1, sc, bound, [&](const Fr& zinv) {
+            ZK_LAUNCH((k_sap_quotient<typename Fr::Params>), dim3(blocks_for(D, 256)), dim3(256), 0, wn, sa, zinv, sa, D);
+        });
         ctx->ws = ctx->stream;
         event_record(sl.ntt_e, wn);
 

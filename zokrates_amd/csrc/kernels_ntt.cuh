@@ -25,6 +25,7 @@
 
 #include "devrt.h"
 #include "fieldu.cuh"
+#include "ntt_geom.h"
 
 namespace zk {
 
@@ -352,8 +353,8 @@ static inline int matvec_group(u64 nnz, u64 n) {
 // An element is nine 29-bit limbs; limb l of slot s lives at lds[l * PL + s] (nine planes), so consecutive work-items
 // touch consecutive 4-byte words of a plane.  Slots are padded by one per 32 elements (the radix-4 butterflies of the
 // late rounds stride by 4, 16, 64 elements) and every sequence starts SS slots after the previous one.
+// (ntt_seq_stride: ntt_geom.h, where the host sizes the tiles)
 static __device__ __forceinline__ int ntt_slot(int e) { return e + (e >> 5); }
-static inline int ntt_seq_stride(int n) { return n + (n >> 5) + 1; }
 template <class P>
 __device__ __forceinline__ Fu<P> lds_get_u(const u32* lds, int PL, int slot) {
     Fu<P> r;

@@ -8,6 +8,8 @@
 //   block (r, c) rows of R_r x columns of S_c: N1/G rows of Nb/G contiguous elements, Nb apart
 // Between the two an all-to-all moves every block (r, c), r != c, once: natural -> sigma (kind A) from member c to member r,
 // sigma -> natural (kind B) from member r to member c.  A block keeps its position in the full-length vector of its receiver.
+// Every pass is the plan's kernel over a strip or a range (ntt_geom.h: ntt_pass_shape).  The whole domain is the span G = 1: one
+// strip of all Nb columns, one range of all N1 outer indices, origins 0, nothing to exchange — what a single context runs.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -36,7 +38,7 @@ struct ShardGeom {
 inline bool ntt_shardable(int log1, uint32_t N1, uint64_t Nb, uint64_t G) {
     return G >= 2 && (G & (G - 1)) == 0 && log1 > 0 && G <= N1 && 2 * G <= Nb;
 }
-// (only for a shardable transform)
+// (for a shardable transform, or G = 1: the whole domain as one span)
 inline ShardGeom ntt_shard_geom(uint32_t N1, uint64_t Nb, uint32_t G) {
     ShardGeom g;
     g.G = G;
