@@ -6,10 +6,11 @@ proof's MSMs (msm_shape over resident tables: a function of the key's size) and 
 module holds
 
   * the SHAPE MODEL: msm_shape (table mode and ad-hoc mode) and the split and geometry of get_plan, restated in plain Python from
-    csrc/core.cuh and csrc/ntt_geom.h.  Where the library reports what it chose — the header of a key image (zkhip_pk_export)
+    csrc/msm_geom.h and csrc/ntt_geom.h.  Where the library reports what it chose — the header of a key image (zkhip_pk_export)
     carries c_z, c_h and the transform split — the check functions assert the model against it, and
-    tests/test_size_ladder.py::test_the_model_of_the_plan_geometry_against_the_library holds ntt_plan to csrc/ntt_geom.h key by key;
-    the ad-hoc width is reported nowhere and the model stands alone there, as `adhoc_window` always did;
+    tests/test_size_ladder.py::test_the_model_of_the_plan_geometry_against_the_library holds ntt_plan to csrc/ntt_geom.h and
+    ::test_the_model_of_the_msm_shape_against_the_library msm_shape to csrc/msm_geom.h, key by key (the ad-hoc width included, which
+    the library reports nowhere else);
   * the RUNG LISTS of the transforms, the proofs and the ad-hoc MSM, and what the model says each rung reaches (`coverage`);
   * the CHECK FUNCTIONS, byte-exact against oracle.cpu (BN254, BLS12-381), tests/bls377_ref.py (BLS12-377) or a closed form.  Nothing
     compares the device with itself or with the emulator, and nothing has a tolerance.
@@ -34,7 +35,7 @@ CURVES = {0: BN254, 1: BLS12_381, 2: ref.CURVE}
 BITS = {0: 254, 1: 255, 2: 253}                     # Fr::Params::BITS
 
 # ------------------------------------------------------------------ the shape model: msm_shape
-MSM_COARSE_BITS = 8                                 # kernels_msm.cuh: keys per coarse bin = 2^8
+MSM_COARSE_BITS = 8                                 # msm_geom.h: keys per coarse bin = 2^8
 MSM_SORT_MAX_KH = 1 << 15                           # counters of one sort workgroup's histogram
 MSM_AUTO_MAX_C, MSM_ADHOC_MAX_C = 17, 16
 

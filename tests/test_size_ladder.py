@@ -153,6 +153,33 @@ def test_the_model_of_the_plan_geometry_against_the_library(tmp_path):
     assert seen == {(sm, sub, cc, lg) for sub in range(2, 12) for lg in range(0, min(3 * sub, 47) + 1) for sm in range(0, 12) for cc in (1, 2)}
 
 
+def test_the_model_of_the_msm_shape_against_the_library(tmp_path):
+    """size_ladder.msm_shape against the library's own arithmetic (csrc/msm_geom.h, from which msm_prepare and msm_run_tables take
+    every size, grid and stride), key by key: the scalar widths of the three curves, with and without tables, n = 1, 2, 3 and
+    2^k - 1, 2^k, 2^k + 1 up to 2^26, no forced width and every forced one.  tests/host/msm_geom.cpp — a stand-alone program on the
+    CPU, under ASan + UBSan — holds the header to the rules written out on their own (the sort, the accumulation and the fold under
+    every knob, the choice of bucket sets against the two loops it replaced) and prints the shape of every case."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "msm_geom")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DZK_EMU", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-I", os.path.join(here, "..", "zokrates_amd", "csrc"),
+                           os.path.join(here, "host", "msm_geom.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and " 0 failures" in out.stderr, out.stderr
+    seen = set()
+    for line in out.stdout.splitlines():
+        got = json.loads(line)
+        case = (got.pop("n"), got.pop("bits"), got.pop("table"), got.pop("force_c"))
+        seen.add(case)
+        want = sl.msm_shape(case[0], case[1], case[2], force_c=case[3])
+        assert sorted(got) == sorted(want), (case, sorted(got), sorted(want))
+        for key in want:
+            assert got[key] == want[key], (case, key, got[key], want[key])
+    ns = {1, 2, 3} | {(1 << k) + d for k in range(2, 27) for d in (-1, 0, 1)}
+    assert seen == {(n, bits, table, c) for n in ns for bits in sl.BITS.values() for table in (False, True) for c in [0] + list(range(2, 18))}
+    assert "%d cases, 0 failures" % len(seen) in out.stderr, out.stderr
+
+
 # ------------------------------------------------------------------ (b) transforms at every size
 NTT_RUNGS = [(cid, lg) for cid in (0, 1) for lg in sl.NTT_LOGS] + [(2, lg) for lg in sl.NTT_LOGS_377]
 NTT_TUNED = [(cid, name) for cid in (0, 1) for name in sl.NTT_TUNED]

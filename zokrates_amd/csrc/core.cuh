@@ -22,6 +22,7 @@
 #include "../../include/zkhip.h"
 #include "devrt.h"
 #include "ntt_geom.h"
+#include "msm_geom.h"
 #include "ec.cuh"
 #include "kernels_msm.cuh"
 #include "kernels_ntt.cuh"
@@ -205,23 +206,11 @@ struct zkhip_ctx {
     Stream ws = 0;            // the stream the mat-vec / NTT helpers launch on right now (ntt_stream inside a proof, else `stream`)
     bool serial = false;      // ZKHIP_SERIAL=1: every MSM on the main stream (debugging / per-kernel timing)
     bool g2_first = true;     // the G2 lane's stream at high priority (see slot_init)
-    int cus = 256;            // compute units of the device: sizes the accumulation launch (one slice per resident work-item)
     // tunables (zkhip_ctx_tune; the environment variables ZKHIP_SERIAL, ZKHIP_MSM_C, ZKHIP_MSM_WAVES and
     // ZKHIP_NTT_SINGLE_MAX_LOG give their initial values, read ONCE when the context is created)
-    int msm_c_env = 0;        // window width of the tables built / ad-hoc MSMs run from now on (0 = automatic)
+    MsmKnobs msm;             // the MSM's tunables and the device's compute units (msm_geom.h)
     int b_sort_mode = 0;      // the thinned list (zkhip_pk::thin_mask): 0 when a tenth of a family's bases are at infinity, 1 always, 2 never
-    int skip_inf_mode = 0;    // which accumulation kernel meets bases at infinity how: 0 per table (MsmShape::skip_inf), 1 lanes always sit them out, 2 always the vote
-    int msm_sets = 0;         // bucket sets of the tables built from now on: 1 = every window multiple, 2 = every second ... (0 = what fits the device)
-    int msm_waves = 0;        // accumulation waves per SIMD (0 = per point type)
-    u32 msm_lanes = 0;        // slices of the sorted list (0 = one per resident work-item)
-    u32 msm_min_slice = 8;    // finest cut of the sorted list
-    bool heavy_runs = true;   // k_msm_heavy_reduce before the fold (ZKHIP_MSM_HEAVY_RUNS=0: the row's workgroup sums a heavy bucket alone)
-    int fold_hg = 32;         // shares a column of rows is cut into in k_msm_fold_cols (a power of two <= 256; ZKHIP_FOLD_HG): 128 rows = 4 serial additions +
-                              // 5 tree levels instead of 16 + 3 at 8 (the fold is a chain of dependent additions: Poseidon BLS12-381 8.95 -> 7.85 ms single)
-    bool fold_scan = true;    // scan form of the last fold step (else double-and-add)
     bool fuse_z = true;       // A, B1 and L of a proof (one sorted list) as ONE slicing / accumulation / fold launch each
-    int msm_fused_waves = 0;  // accumulation waves per SIMD of that launch (0 = per point type)
-    int msm_g1_waves = 0, msm_g2_waves = 0;   // slices per SIMD lane of a single-table G1 / G2 accumulation (0 = per point type)
     int z_gate = 1;           // which accumulations over z wait for the witness map of their proof: 0 none, 1 the G1 lanes, 2 all
     int g2_head_start = 1;    // a LONE proof over a curve whose G2 accumulation runs one wave per SIMD: its G1 lanes also wait for the end of
                               // that accumulation — 0 never, 1 over a bound key, 2 always (ZKHIP_G2_HEAD_START; Prover::enqueue)
@@ -236,7 +225,6 @@ struct zkhip_ctx {
     Stream ntt_lone_stream = 0;              // the witness map of a LONE proof ("n" of the plan), where the plan gives it a pipe of its own choosing
     bool ntt_lone_made = false;
     int ntt_fuse_first = 1;   // the first butterfly round of a pass done on the elements as they are fetched (kernels_ntt.cuh ntt_first_round; ZKHIP_NTT_FUSE_FIRST=0: every round through LDS)
-    u32 sort_wgs = 256;       // workgroups of a counting-sort pass (chunks x windows): fewer = longer runs per (workgroup, bucket)
     int tenants = 1;          // contexts of one zkhip_multi that share this context's device (their keys are sized for a share of its memory)
     int nslots = 3;           // proofs in flight in the batch calls (<= ZK_NSLOTS; measured 2 / 3 / 4: 72.0 / 76.0 / 74.8 proofs/s)
     bool checked = false;     // zkhip_ctx_set_checked: the single-GPU prove calls test Az o Bz == Cz on the device and refuse a proof that fails
@@ -381,190 +369,15 @@ static inline void lds_opt_in(zkhip_ctx* ctx, const void* kernel) {
 }
 
 #include "ntt_host.cuh"
+#include "msm_host.cuh"
 
 namespace zk {
 
-// ------------------------------------------------------------------ MSM driver
-struct MsmShape {
-    u64 n;
-    int c, W;
-    u32 K;          // buckets per set = 2^(c-1)
-    u32 sets;       // bucket sets: 1 when the bases carry every window multiple (all windows share one set), W without a table, in
-                    // between for keys too large for W levels (window j: bucket set j % sets, table level j / sets)
-    u32 levels;     // table levels the sorted entries refer to: ceil(W / sets) (1 without a table)
-    u32 nkeys;      // sets * K
-    u32 Lw, H;      // fold geometry: K = H rows of Lw buckets
-    static constexpr u32 ndig = 2;   // digits of the fold: column and row of the bucket index
-    int level_bits() const { return c * (int)sets; }   // level t of a table holds 2^(level_bits t) P
-    bool skip_inf = true;   // which accumulation kernel: lanes sit out bases at infinity (tables that hold many: kernels_msm.cuh
-                            // k_msm_accum SKIP_INF), or the rare one goes through the general code (tables that hold next to none)
-    u32 nsums() const { return ndig * sets; }   // the fold leaves one sum per digit and bucket set: msm_combine adds them
-};
 static inline int env_int(const char* name, int lo, int hi, int dflt) {
     if (const char* e = getenv(name)) { int v = atoi(e); if (v >= lo && v <= hi) return v; }
     return dflt;
 }
-static constexpr int MSM_MAX_C = 17;         // widest window: 2^16 buckets, which the sort takes in two halves of MSM_SORT_MAX_KH counters
-static constexpr int MSM_AUTO_MAX_C = 17;    // widest window chosen automatically (resident tables)
-static constexpr int MSM_ADHOC_MAX_C = 16;   // ... and without a table (a bucket set per window: the fold grows with every bucket)
-static constexpr u32 MSM_SORT_MAX_KH = 1u << 15;   // counters of one sort workgroup's LDS histogram (128 KiB)
-// `table`: the bases carry precomputed window multiples 2^(c j) P (resident keys); otherwise one bucket set per window.
-static inline MsmShape msm_shape(const zkhip_ctx* ctx, u64 n, int scalar_bits, bool table, int force_c = 0, int force_sets = 0) {
-    MsmShape s;
-    s.n = n;
-    const int lg = ilog2_floor(std::max<u64>(n, 1));
-    if (table) {
-        // one fold per MSM whatever c is, so c only trades additions (n * W) against buckets (2^(c-1)): the fewest windows the
-        // widest admissible width gives (a few points per bucket at least), and of the widths with that many windows the
-        // narrowest — 254-bit scalars: 15 windows of 17 bits instead of 16 of 16 (6 % fewer additions in all five MSMs for twice
-        // the buckets); 255-bit scalars need 16 windows either way and stay at 16 bits
-        const int cmax = std::max(2, std::min(MSM_AUTO_MAX_C, lg + 1));
-        const int Wmin = (scalar_bits + 1 + cmax - 1) / cmax;
-        s.c = cmax;
-        while (s.c > 2 && (scalar_bits + 1 + (s.c - 1) - 1) / (s.c - 1) == Wmin) --s.c;
-    } else {
-        // Window width: about log2(n) - 5 (measured optimum at 2^20: 15), but never one that leaves the top window
-        // with only a few significant bits — its handful of buckets would each receive a large share of all points
-        // (same-address atomics in the sort, one bucket spread over thousands of slices).
-        const int want = std::max(2, std::min(MSM_ADHOC_MAX_C, lg - 5));
-        s.c = want;
-        for (int d = 0; d <= 14; ++d) {
-            bool found = false;
-            for (int cand : {want + d, want - d}) {
-                if (cand < 2 || cand > MSM_ADHOC_MAX_C) continue;
-                const int W = (scalar_bits + 1 + cand - 1) / cand;
-                const int top_bits = scalar_bits + 1 - (W - 1) * cand;
-                if (top_bits >= cand || (n >> (top_bits - 1)) <= 4096) { s.c = cand; found = true; break; }   // <= 4096 points per top bucket
-            }
-            if (found) break;
-        }
-    }
-    if (ctx && ctx->msm_c_env) s.c = ctx->msm_c_env;
-    if (force_c) s.c = force_c;
-    s.c = std::min(s.c, MSM_MAX_C);
-    s.W = (scalar_bits + 1 + s.c - 1) / s.c;
-    s.K = 1u << (s.c - 1);
-    s.sets = table ? (u32)std::max(1, std::min(force_sets ? force_sets : 1, s.W)) : (u32)s.W;
-    s.levels = ((u32)s.W + s.sets - 1) / s.sets;
-    s.nkeys = s.sets * s.K;
-    s.Lw = std::min<u32>(s.K, 256);
-    s.H = s.K / s.Lw;
-    return s;
-}
-
-static inline MsmShape with_inf(MsmShape sh, bool many) { sh.skip_inf = many; return sh; }
-// Device memory the window-multiple tables of a key may take: 60 % of what is free now, less what the proofs themselves will
-// allocate later beside them — per proof slot the digits and sorted lists of up to three sorts, the transform vectors, scalars, and
-// the partial / bucket arrays of five MSMs — and the transient of the table construction (msm_table_levels: < 1 GiB).  Several
-// contexts sharing one device each see the same "free" figure: the margin is what keeps the first batch prove from failing where
-// the key load succeeded.
-static inline u64 msm_table_budget(const zkhip_ctx* ctx, u64 z_n, u64 h_n, u64 N, int W, u32 K) {
-    size_t free_b = 0, total_b = 0;
-    dev_mem_info(&free_b, &total_b);
-    const u64 per_slot = (2 * z_n + h_n) * (u64)W * 16 + 4 * N * 32 + (z_n + 2) * 64 + 6 * ((u64)K + (1u << 19)) * 288 + ((u64)1 << 29);
-    const u64 later = (u64)std::max(1, ctx->nslots) * per_slot + ((u64)1 << 30);
-    const u64 budget = (u64)((ctx->tenants > 1 ? 0.5 : 0.6) * (double)free_b) / (u64)std::max(1, ctx->tenants);
-    return budget > later ? budget - later : 0;
-}
-// exclusive scan of nk counters (cnt -> off, off[nk] = their sum, also left in *grand)
-static inline void scan_u32(Stream s, const DBuf& cnt, DBuf& off, u64 nk, DBuf& chunk_sum, DBuf& grand) {
-    const u32 nchunks = (u32)((nk + SCAN_CHUNK - 1) / SCAN_CHUNK);
-    off.ensure((nk + 1) * 4);
-    chunk_sum.ensure((size_t)nchunks * 4);
-    grand.ensure(4);
-    ZK_LAUNCH(k_scan_local, dim3(nchunks), dim3(SCAN_THREADS), 0, s, ptr<u32>(cnt), ptr<u32>(off), ptr<u32>(chunk_sum), nk);
-    ZK_LAUNCH(k_scan_chunks, dim3(1), dim3(SCAN_THREADS), 0, s, ptr<u32>(chunk_sum), nchunks, ptr<u32>(grand));
-    ZK_LAUNCH(k_scan_add, dim3(blocks_for(nk + 1, 256)), dim3(256), 0, s, ptr<u32>(off), ptr<u32>(chunk_sum), nk, ptr<u32>(grand));
-}
-// digits + counting sort on the main stream; leaves so.off / so.sorted describing every bucket's point list.
-// level_stride: distance between two levels of the base tables this sort will be paired with (table mode), else 0.
-// `keep`: bitmap of the scalars that take part (null: all); `wm_of`: a sort of the SAME scalars (same shape) whose digits are reused
-static inline void msm_prepare(zkhip_ctx* ctx, Stream s, MsmSort& so, const u32* d_scalars, const MsmShape& sh, u64 level_stride,
-                               const u32* keep = nullptr, const MsmSort* wm_of = nullptr) {
-    const u64 nk = sh.nkeys;
-    require(sh.n * (u64)sh.W < ((u64)1 << 32) - sh.nkeys, ZKHIP_ERR_BAD_ARG, "MSM too large for 32-bit sort offsets");
-    require(level_stride * (u64)sh.levels < ((u64)1 << 31) && sh.n < ((u64)1 << 31), ZKHIP_ERR_BAD_ARG, "MSM too large for 31-bit table indices");
-    if (!wm_of) so.dig.ensure(sh.n * (u64)sh.W * 4);
-    so.sorted.ensure(sh.n * sh.W * 4);
-    const unsigned T = 256;
-    // one workgroup per (chunk of scalars, window): chunks several times larger than a window's bucket count keep the
-    // global atomics (one per touched bucket per workgroup) well below one per digit
-    // (a window of more than 16 bits has more buckets than one histogram holds: its workgroups come in `halves`, each reading the
-    // chunk's digits and keeping the ones of its own range of buckets)
-    const u32 kh = std::min(sh.K, MSM_SORT_MAX_KH), halves = sh.K / kh;
-    const u64 want_chunks = halves > 1 ? std::max<u64>(1, ctx->sort_wgs / (sh.W * halves)) : std::max<u64>(1, (ctx->sort_wgs + sh.W - 1) / sh.W);
-    const u64 max_chunks = std::max<u64>(1, sh.n / (2 * (u64)kh));
-    const u64 sort_chunks = std::min(want_chunks, max_chunks);
-    const u64 chunk = (sh.n + sort_chunks - 1) / sort_chunks;
-    const size_t hist_bytes = (size_t)kh * 4;
-    const bool two_level = sh.K >= (1u << MSM_COARSE_BITS) && sh.K <= (1u << 16);
-    const u32 nbins = (u32)(nk >> MSM_COARSE_BITS);
-    so.cnt.ensure(nk * 4);
-    so.cursor.ensure(nk * 4);
-    if (two_level) {
-        so.ccur.ensure((size_t)nbins * 4);
-        so.tile_off.ensure(((size_t)nbins + 1) * 4);
-    }
-    // the counters of the passes below start from zero: cleared by the digit kernel on its way (a sort that borrows another's digits:
-    // by a launch of its own)
-    const MsmZero zero{{ptr<u32>(so.cnt), ptr<u32>(so.cursor), two_level ? ptr<u32>(so.ccur) : nullptr}, {(u32)nk, (u32)nk, two_level ? nbins : 0u}};
-    if (!wm_of) ZK_LAUNCH(k_msm_digits, dim3(blocks_for(sh.n, T)), dim3(T), 0, s, d_scalars, sh.n, sh.c, sh.W, ptr<u32>(so.dig), zero);
-    else ZK_LAUNCH(k_msm_zero, dim3(blocks_for(nk, T)), dim3(T), 0, s, zero);
-    const u32* wm = wm_of ? ptr<u32>(wm_of->dig) : ptr<u32>(so.dig);
-    lds_opt_in(ctx, (const void*)k_msm_count);
-    lds_opt_in(ctx, (const void*)k_msm_place);
-    ZK_LAUNCH(k_msm_count, dim3((unsigned)sort_chunks, sh.W, halves), dim3(ZK_SORT_THREADS), hist_bytes, s, wm, sh.n, sh.c, sh.W, chunk, sh.sets, kh,
-              ptr<u32>(so.cnt), keep);
-    if (nk <= SCAN_ONE_MAX) {
-        so.off.ensure((nk + 1) * 4);
-        ZK_LAUNCH(k_scan_one, dim3(1), dim3(SCAN_ONE_THREADS), 0, s, ptr<u32>(so.cnt), ptr<u32>(so.off), (u32)nk, two_level ? ptr<u32>(so.tile_off) : (u32*)nullptr, nbins);
-    } else {
-        scan_u32(s, so.cnt, so.off, nk, so.chunk_sum, so.grand);
-        if (two_level) ZK_LAUNCH(k_msm_tile_offsets, dim3(1), dim3(MSM_TILE_SCAN_THREADS), 0, s, ptr<u32>(so.off), nbins, ptr<u32>(so.tile_off));
-    }
-    if (two_level) {
-        const u64 total_max = sh.n * (u64)sh.W;
-        so.pairs.ensure(std::max<u64>(total_max, 1) * 8);
-        // ~1024 workgroups of the coarse pass (1 KiB of LDS each: they share CUs with anything), chunks of at least 4096 scalars
-        const u64 c_chunks = std::max<u64>(1, std::min<u64>((1024 + sh.W - 1) / sh.W, (sh.n + 4095) / 4096));
-        const u64 c_chunk = (sh.n + c_chunks - 1) / c_chunks;
-        ZK_LAUNCH(k_msm_part_coarse, dim3((unsigned)c_chunks, sh.W), dim3(256), 0, s, wm, sh.n, sh.c, sh.W, c_chunk, sh.sets, level_stride, ptr<u32>(so.off),
-                  ptr<u32>(so.ccur), (unsigned long long*)so.pairs.p, keep);
-        const u64 max_tiles = total_max / MSM_FINE_TILE + nbins;
-        ZK_LAUNCH(k_msm_part_fine, dim3((unsigned)max_tiles), dim3(256), 0, s, (const unsigned long long*)so.pairs.p, ptr<u32>(so.off), ptr<u32>(so.tile_off), nbins,
-                  ptr<u32>(so.cursor), ptr<u32>(so.sorted));
-    } else {
-        ZK_LAUNCH(k_msm_place, dim3((unsigned)sort_chunks, sh.W, halves), dim3(ZK_SORT_THREADS), hist_bytes, s, wm, sh.n, sh.c, sh.W, chunk, sh.sets, kh,
-                  level_stride, ptr<u32>(so.off), ptr<u32>(so.cursor), ptr<u32>(so.sorted), keep);
-    }
-    event_record(so.ready, s);
-}
-
-// bucket accumulation + fold for one base table; the bucket sets' weighted sums land in d_window_sums[0..nsums()), two per set.
-// Defined in group.cuh and instantiated once per (curve, group) in its own translation unit (bn254_g1.hip, ...):
-// the elliptic-curve kernels are by far the most expensive code to compile.
-// Runs on lane.stream after so.ready; lane.done is recorded behind the last kernel.
-// `d_table` holds packed affine points (AffPacked, level-major when it carries window multiples); the sums come back in
-// the saturated Montgomery form.
-// `h_window_sums` (may be null): the pinned host mirror of d_window_sums — the lane copies its sums out itself, behind its fold and
-// before `done`, so that the host can take each MSM's result as it arrives (Prover::finish) instead of all of them after the last
-template <class F>
-void msm_run(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void* d_table, const MsmShape& sh, Xyzz<F>* d_window_sums,
-             Event ev_begin, Event ev_end, Event accum_after = nullptr, Xyzz<F>* h_window_sums = nullptr);
-template <class F>
-void msm_run_tables(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void* const* d_tables, int nt, const MsmShape& sh, Xyzz<F>* d_window_sums,
-                    u32 sum_stride, Event ev_begin, Event ev_end, Event accum_after, Xyzz<F>* h_window_sums = nullptr);
-// affine points, saturated Montgomery form -> packed working form of the MSM kernels (level 0 of a table); on ctx->stream
-template <class F>
-void points_to_packed(zkhip_ctx* ctx, const Aff<F>* d_in, void* d_out, u64 n);
-// levels 1 .. L-1 (2^(bits j) P) behind a level 0 of `count` points; synchronises ctx->stream
-template <class F>
-void msm_table_levels(zkhip_ctx* ctx, void* d_table, u64 count, int bits, int L);
-template <class F>
-u64 count_infinite(zkhip_ctx* ctx, const void* d_table, u64 count);
-template <class F>
-void mark_finite(zkhip_ctx* ctx, const void* d_table, u64 count, u32* d_bitmap);
-template <class F> static constexpr size_t packed_point_bytes() { return sizeof(AffPacked<typename Unsat<F>::type>); }
+// ------------------------------------------------------------------ per-group launchers (group.cuh; the MSM's: msm_host.cuh)
 // binding a key to a constraint system (bind.cuh: the kernels; group.cuh: these launchers, instantiated for G1 only).  `x`: two
 // vectors of N XYZZ points (bind_xyzz_bytes each); everything on ctx->stream.
 template <class F>
@@ -606,23 +419,6 @@ constexpr bool group_op_known(int group, int form, int op) {
 // FS: the group's saturated coordinate field (Fq or Fq2); a, b, out: count x 4 coordinates of raw limbs in the form's layout
 template <class FS>
 void group_op_run(zkhip_ctx* ctx, int form, int op, u64 count, const u32* a, const u32* b, const u32* k, const uint8_t* flags, u32* out);
-
-// the MSM's value from its bucket-set sums: the single sum of a table MSM, else the host Horner step sum_j 2^(c j) S_j
-template <class F>
-static Xyzz<F> msm_combine(const Xyzz<F>* ws, const MsmShape& sh) {
-    auto set_sum = [&](int j) {                      // one sum per fold digit
-        Xyzz<F> t = ws[sh.ndig * j];
-        for (u32 d = 1; d < sh.ndig; ++d) t = xyzz_add(t, ws[sh.ndig * j + d]);
-        return t;
-    };
-    if (sh.sets == 1) return set_sum(0);
-    Xyzz<F> acc = Xyzz<F>::inf();
-    for (int j = (int)sh.sets - 1; j >= 0; --j) {
-        for (int i = 0; i < sh.c; ++i) acc = xyzz_dbl(acc);
-        acc = xyzz_add(acc, set_sum(j));
-    }
-    return acc;
-}
 
 // ------------------------------------------------------------------ byte codecs (host)
 template <class F>
@@ -796,7 +592,7 @@ struct SlotSums {
     // (a sharded key covers only its index range of the bases; the shapes are recomputed from the key's own (c, sets): a key whose
     // numbers this build cannot run is refused, never paired with a sort of another window width)
     SlotSums(const zkhip_ctx* ctx, const zkhip_pk* pk)
-        : shz(msm_shape(ctx, pk->z_n, C::Fr::Params::BITS, true, pk->c_z, pk->s_z)), shh(msm_shape(ctx, pk->h_n, C::Fr::Params::BITS, true, pk->c_h, pk->s_h)) {
+        : shz(msm_shape(&ctx->msm,pk->z_n, C::Fr::Params::BITS, true, pk->c_z, pk->s_z)), shh(msm_shape(&ctx->msm,pk->h_n, C::Fr::Params::BITS, true, pk->c_h, pk->s_h)) {
         require(shz.c == pk->c_z && shh.c == pk->c_h && (int)shz.sets == pk->s_z && (int)shh.sets == pk->s_h, ZKHIP_ERR_BAD_ARG,
                 "the key's tables were built for a window width this build cannot sort: reload the key");
         Wmax = (int)std::max(shz.nsums(), shh.nsums());
@@ -1069,21 +865,18 @@ struct PkLoader {
         u64 nominal_z, nominal_h;
         range_of(me, pk->rank, pk->world, pk->z_lo, pk->z_n, nominal_z);
         range_of(hdom, pk->rank, pk->world, pk->h_lo, pk->h_n, nominal_h);
-        auto shape_z = [&](int sets) { return msm_shape(ctx, nominal_z, C::Fr::Params::BITS, true, 0, sets); };
-        auto shape_h = [&](int sets) { return msm_shape(ctx, nominal_h, C::Fr::Params::BITS, true, 0, sets); };
+        auto shape_z = [&](int sets) { return msm_shape(&ctx->msm,nominal_z, C::Fr::Params::BITS, true, 0, sets); };
+        auto shape_h = [&](int sets) { return msm_shape(&ctx->msm,nominal_h, C::Fr::Params::BITS, true, 0, sets); };
         // Every window multiple of every base (one bucket set, one fold per MSM) while that fits the device: a 2^20 key is 6 GiB,
         // 2^24 96 GiB.  Beyond — or when ZKHIP_TUNE_MSM_SETS says so — the tables keep every 2nd, 4th, ... multiple and the MSMs
         // fold as many bucket sets (the reference has no size limit below the field's two-adicity; this is how it is met).
-        int sets = ctx->msm_sets;
+        // (one count for both, doubled until it has passed the windows of the MSMs over z: one bucket set per window there)
+        int sets = ctx->msm.msm_sets;
         if (!sets) {
             const MsmShape one = shape_z(0);
             const u64 budget = msm_table_budget(ctx, pk->z_n, pk->h_n, hdom, one.W, one.K);
-            sets = 1;
-            for (;;) {
-                const MsmShape a = shape_z(sets);
-                if (tables_need(pk, a, shape_h(sets)) <= budget || (int)a.sets < sets) break;      // (a.sets < sets: already one bucket set per window)
-                sets *= 2;
-            }
+            const int no_cap = 1 << 30;
+            sets = msm_pick_sets({1, 1}, {no_cap, no_cap}, {one.W + 1, 0}, budget, [&](MsmSets s) { return tables_need(pk, shape_z(s.z), shape_h(s.h)); }).z;
         }
         const MsmShape shz = shape_z(sets), shh = shape_h(sets);
         pk->c_z = shz.c;
@@ -1459,8 +1252,8 @@ struct PkLoader {
         pk->c_z = h.c_z; pk->c_h = h.c_h; pk->rank = h.rank; pk->world = h.world;
         pk->z_lo = h.z_lo; pk->z_n = h.z_n; pk->h_lo = h.h_lo; pk->h_n = h.h_n;
         pk->ntt_log1 = h.ntt_split;
-        auto shape_z = [&](int sets) { return msm_shape(ctx, h.z_n, C::Fr::Params::BITS, true, h.c_z, sets); };
-        auto shape_h = [&](int sets) { return msm_shape(ctx, h.h_n, C::Fr::Params::BITS, true, h.c_h, sets); };
+        auto shape_z = [&](int sets) { return msm_shape(&ctx->msm,h.z_n, C::Fr::Params::BITS, true, h.c_z, sets); };
+        auto shape_h = [&](int sets) { return msm_shape(&ctx->msm,h.h_n, C::Fr::Params::BITS, true, h.c_h, sets); };
         // the index ranges must lie inside the key and the five base arrays must have exactly the size the ranges imply:
         // the kernels trust these numbers
         bool sizes_ok = h.m + 2 < ((u64)1 << 31) && h.z_lo <= h.m + 2 && h.z_n <= h.m + 2 - h.z_lo && h.h_lo <= h.N && h.h_n <= h.N - h.h_lo &&
@@ -1480,12 +1273,12 @@ struct PkLoader {
         // bucket sets instead of an allocation failure) — each MSM clamped to its own number of windows
         {
             const int W_z = shape_z(1).W, W_h = shape_h(1).W;
-            if (ctx->msm_sets) s_z = std::min(ctx->msm_sets, W_z), s_h = std::min(ctx->msm_sets, W_h);
+            const int fixed = ctx->msm.msm_sets;
             const u64 budget = msm_table_budget(ctx, h.z_n, h.h_n, h.N, W_z, shape_z(1).K);
-            while (!ctx->msm_sets) {
-                if (tables_need(pk, shape_z(s_z), shape_h(s_h)) <= budget || (s_z >= W_z && s_h >= W_h)) break;
-                s_z = std::min(2 * s_z, W_z);
-                s_h = std::min(2 * s_h, W_h);
+            if (fixed) s_z = std::min(fixed, W_z), s_h = std::min(fixed, W_h);
+            else {
+                const MsmSets s = msm_pick_sets({s_z, s_h}, {W_z, W_h}, {W_z, W_h}, budget, [&](MsmSets t) { return tables_need(pk, shape_z(t.z), shape_h(t.h)); });
+                s_z = s.z, s_h = s.h;
             }
         }
         // (c, sets) must be a shape this context's sort can run
@@ -2457,7 +2250,7 @@ struct Prover {
         ctx->cur->scalars.ensure(n * 32);
         dev_h2d(ctx->cur->scalars.p, scalars, n * 32, s);
         // ad-hoc bases: no table of window multiples (building one costs ~15x the MSM itself), one bucket set per window
-        const MsmShape sh = msm_shape(ctx, n, Fr::Params::BITS, false);
+        const MsmShape sh = msm_shape(&ctx->msm,n, Fr::Params::BITS, false);
         d_ws.ensure((size_t)sh.nsums() * sizeof(Xyzz<F>));
         // the packed bases are written on the main stream BEFORE the sort records `ready` there: the lane stream waits on
         // that event only, so everything the accumulation reads must precede it on the main stream

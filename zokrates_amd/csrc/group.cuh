@@ -30,9 +30,15 @@ void msm_table_levels(zkhip_ctx* ctx, void* d_table, u64 count, int c, int W) {
     stream_sync(ctx->stream);
 }
 
+// what msm_geom.h needs of a point type
+template <class F, class FS>
+static constexpr MsmPoint msm_point() {
+    return {MsmTuning<F>::IS_EXT, MsmTuning<F>::SLICE_WPE, MsmTuning<F>::FUSED_WPE, sizeof(Xyzz<F>), sizeof(Xyzz<FS>), msm_accum_lds_bytes<F>()};
+}
 // `nt` MSMs over ONE sorted list (tables[t] -> d_window_sums + t * sum_stride): one slicing, one accumulation launch, one
 // fold — A, B1 and L of a proof share the sort of the assignment, and as one launch their residency is what the grid says
 // (three separate accumulations pack five waves per SIMD and leave no room for a 128-register fold wave).
+// Every size and launch shape is msm_run_geom's (msm_geom.h).
 template <class FS>
 void msm_run_tables(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void* const* d_tables, int nt, const MsmShape& sh, Xyzz<FS>* d_window_sums,
                     u32 sum_stride, Event ev_begin, Event ev_end, Event accum_after, Xyzz<FS>* h_window_sums) {
@@ -42,75 +48,52 @@ void msm_run_tables(zkhip_ctx* ctx, MsmLane& lane, const MsmSort& so, const void
     for (int t = 0; t < nt; ++t) tables.p[t] = d_tables[t];
     Stream s = ctx->serial ? ctx->stream : lane_stream(lane);
     stream_wait_event(s, so.ready);
-    // one slice of the sorted list per work-item the machine holds (never finer than MSM_MIN_SLICE entries)
-    // (the slices may outnumber the work-items the kernel's registers let the machine hold: SLICE_WPE >= ACCUM_WPE)
-    const int single = MsmTuning<F>::IS_EXT ? (ctx->msm_g2_waves ? ctx->msm_g2_waves : MsmTuning<F>::SLICE_WPE)
-                                            : (ctx->msm_g1_waves ? ctx->msm_g1_waves : MsmTuning<F>::SLICE_WPE);
-    const int wpe = ctx->msm_waves ? ctx->msm_waves : (nt > 1 ? std::max(1, (ctx->msm_fused_waves ? ctx->msm_fused_waves : MsmTuning<F>::FUSED_WPE)) : single);
-    const u64 machine = ctx->msm_lanes ? (u64)ctx->msm_lanes : (u64)ctx->cus * 4 * 64 * wpe / (nt > 1 && !ctx->msm_waves ? nt : 1);
-    const u32 nlanes = (u32)std::max<u64>(1, std::min<u64>(machine, (sh.n * (u64)sh.W + ctx->msm_min_slice - 1) / ctx->msm_min_slice));
-    const MsmCut cut{nlanes, ctx->msm_min_slice, (u32)std::min<u64>(sh.n * (u64)sh.levels, 0x7fffffffu)};
-    const u64 partial_stride = (u64)sh.nkeys + nlanes;
-    lane.heavy.ensure(((size_t)sh.nkeys + 1) * 4);            // [0] = count, [1..] = keys
-    lane.lane_key.ensure((size_t)nlanes * 4);
-    lane.partial.ensure((size_t)nt * partial_stride * sizeof(Xyzz<F>));
-    lane.bucket.ensure((size_t)nt * sh.nkeys * sizeof(Xyzz<F>));
-    lane.rows.ensure((size_t)nt * sh.sets * sh.H * sizeof(Xyzz<F>));
-    lane.cols.ensure((size_t)nt * sh.sets * sh.Lw * sizeof(Xyzz<F>));
+    const MsmRunGeom g = msm_run_geom(sh, nt, msm_point<F, FS>(), ctx->msm);
+    lane.heavy.ensure(g.heavy_bytes);
+    lane.lane_key.ensure(g.lane_key_bytes);
+    lane.partial.ensure(g.partial_bytes);
+    lane.bucket.ensure(g.bucket_bytes);
+    lane.rows.ensure(g.rows_bytes);
+    lane.cols.ensure(g.cols_bytes);
     lds_opt_in(ctx, (const void*)k_msm_fold_rows<F>);
     lds_opt_in(ctx, (const void*)k_msm_fold_cols<F>);
     lds_opt_in(ctx, (const void*)k_msm_fold_final<F, FS>);
     lds_opt_in(ctx, (const void*)k_msm_fold_final_scan<F, FS>);
-    const unsigned T = 256;
-    ZK_LAUNCH(k_msm_lane_keys, dim3(blocks_for(nlanes, T)), dim3(T), 0, s, ptr<u32>(so.off), sh.nkeys, cut, ptr<u32>(lane.lane_key), ptr<u32>(lane.heavy));
-    ZK_LAUNCH(k_msm_find_heavy, dim3(blocks_for(sh.nkeys, T)), dim3(T), 0, s, ptr<u32>(so.off), sh.nkeys, cut, ptr<u32>(lane.heavy) + 1,
-              ptr<u32>(lane.heavy));
+    MSM_LAUNCH(k_msm_lane_keys, g.lane_keys, s, ptr<u32>(so.off), sh.nkeys, g.cut, ptr<u32>(lane.lane_key), ptr<u32>(lane.heavy));
+    MSM_LAUNCH(k_msm_find_heavy, g.find_heavy, s, ptr<u32>(so.off), sh.nkeys, g.cut, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy));
     if (accum_after && !ctx->serial) stream_wait_event(s, accum_after);   // (the slicing above only needs the sort)
     if (ev_begin) event_record(ev_begin, s);
-    const size_t acc_lds = msm_accum_lds_bytes<F>();
-    if (ctx->skip_inf_mode == 1 || (ctx->skip_inf_mode == 0 && sh.skip_inf)) {
-        if (acc_lds > 64 * 1024) lds_opt_in(ctx, (const void*)k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, true>);
-        ZK_LAUNCH((k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, true>), dim3(blocks_for(nlanes, T), nt), dim3(T), acc_lds, s, tables, ptr<u32>(so.off), ptr<u32>(so.sorted),
-                  ptr<u32>(lane.lane_key), ptr<Xyzz<F>>(lane.partial), partial_stride, sh.nkeys, cut);
+    if (g.skip_inf) {
+        if (g.accum.lds > 64 * 1024) lds_opt_in(ctx, (const void*)k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, true>);
+        MSM_LAUNCH((k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, true>), g.accum, s, tables, ptr<u32>(so.off), ptr<u32>(so.sorted), ptr<u32>(lane.lane_key),
+                   ptr<Xyzz<F>>(lane.partial), g.partial_stride, sh.nkeys, g.cut);
     } else {
-        if (acc_lds > 64 * 1024) lds_opt_in(ctx, (const void*)k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, false>);
-        ZK_LAUNCH((k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, false>), dim3(blocks_for(nlanes, T), nt), dim3(T), acc_lds, s, tables, ptr<u32>(so.off), ptr<u32>(so.sorted),
-                  ptr<u32>(lane.lane_key), ptr<Xyzz<F>>(lane.partial), partial_stride, sh.nkeys, cut);
+        if (g.accum.lds > 64 * 1024) lds_opt_in(ctx, (const void*)k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, false>);
+        MSM_LAUNCH((k_msm_accum<F, MsmTuning<F>::ACCUM_WPE, false>), g.accum, s, tables, ptr<u32>(so.off), ptr<u32>(so.sorted), ptr<u32>(lane.lane_key),
+                   ptr<Xyzz<F>>(lane.partial), g.partial_stride, sh.nkeys, g.cut);
     }
     if (ev_end) event_record(ev_end, s);
     // (the fold chain stays on the stream of its accumulation)
-    if (ctx->heavy_runs) {
+    if (g.heavy_reduce) {
         lds_opt_in(ctx, (const void*)k_msm_heavy_reduce<F>);
-        const unsigned TH = MSM_HEAVY_THREADS;
-        ZK_LAUNCH((k_msm_heavy_reduce<F>), dim3(MSM_HEAVY_CHUNKS, nt), dim3(TH), (size_t)TH * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.partial), partial_stride,
-                  ptr<u32>(so.off), sh.nkeys, cut, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy));
+        MSM_LAUNCH((k_msm_heavy_reduce<F>), g.heavy, s, ptr<Xyzz<F>>(lane.partial), g.partial_stride, ptr<u32>(so.off), sh.nkeys, g.cut, ptr<u32>(lane.heavy) + 1,
+                   ptr<u32>(lane.heavy));
     }
-    FoldDigits digs{};
-    ZK_LAUNCH((k_msm_fold_rows<F>), dim3(sh.H, sh.sets, nt), dim3(sh.Lw), (size_t)sh.Lw * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.partial), partial_stride,
-              ptr<u32>(so.off), sh.nkeys, cut, sh.K, sh.Lw, ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy), ctx->heavy_runs ? 1u : 0u, ptr<Xyzz<F>>(lane.bucket),
-              ptr<Xyzz<F>>(lane.rows));
-    // column sums of the K = H x Lw buckets of a set; work-item (lo, hg) adds RG / HG rows serially
-    const u32 RG = sh.H;
-    const u32 HG = std::max<u32>(1, std::min<u32>((u32)ctx->fold_hg, RG)), CW = std::min<u32>(sh.Lw, 256 / HG), NG = sh.H / RG;
-    ZK_LAUNCH((k_msm_fold_cols<F>), dim3(sh.Lw / CW, sh.sets * NG, nt), dim3(CW, HG), (size_t)CW * HG * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.bucket), (u64)sh.K,
-              (u64)sh.nkeys, sh.Lw, sh.H, RG, ptr<Xyzz<F>>(lane.cols));
-    digs.d[0] = FoldDigit{lane.cols.p, sh.Lw, 1, 0};
-    digs.d[1] = FoldDigit{lane.rows.p, sh.H, 0, (u32)ilog2_floor(sh.Lw)};
-    // the scan form of the last fold step: one workgroup of <= 256 work-items per digit; the double-and-add form (two digits
-    // in one workgroup of Lw work-items) is the fallback.  Either leaves one sum per digit and bucket set.
-    u32 longest = 0;
-    for (u32 d = 0; d < sh.ndig; ++d) longest = std::max(longest, digs.d[d].len);
-    const unsigned TS = std::max<u32>(64, longest);
-    if (ctx->fold_scan && TS <= 256) {
-        ZK_LAUNCH((k_msm_fold_final_scan<F, FS>), dim3(sh.sets, nt, sh.ndig), dim3(TS), TS * sizeof(Xyzz<F>), s, digs, d_window_sums, sum_stride);
+    MSM_LAUNCH((k_msm_fold_rows<F>), g.fold_rows, s, ptr<Xyzz<F>>(lane.partial), g.partial_stride, ptr<u32>(so.off), sh.nkeys, g.cut, sh.K, sh.Lw,
+               ptr<u32>(lane.heavy) + 1, ptr<u32>(lane.heavy), g.heavy_reduce ? 1u : 0u, ptr<Xyzz<F>>(lane.bucket), ptr<Xyzz<F>>(lane.rows));
+    // column sums of the K = H x Lw buckets of a set; work-item (lo, hg) adds H / HG rows serially
+    MSM_LAUNCH((k_msm_fold_cols<F>), g.fold_cols, s, ptr<Xyzz<F>>(lane.bucket), (u64)sh.K, (u64)sh.nkeys, sh.Lw, sh.H, sh.H, ptr<Xyzz<F>>(lane.cols));
+    // the last fold step, scan form (one workgroup per digit) or double-and-add: either leaves one sum per digit and bucket set
+    if (g.final_scan) {
+        FoldDigits digs{};
+        digs.d[0] = FoldDigit{lane.cols.p, sh.Lw, 1, 0};
+        digs.d[1] = FoldDigit{lane.rows.p, sh.H, 0, (u32)ilog2_floor(sh.Lw)};
+        MSM_LAUNCH((k_msm_fold_final_scan<F, FS>), g.fold_final, s, digs, d_window_sums, sum_stride);
     } else {
-        const unsigned TF = std::max<u32>(64, sh.Lw);
-        ZK_LAUNCH((k_msm_fold_final<F, FS>), dim3(sh.sets, nt), dim3(TF), TF * sizeof(Xyzz<F>), s, ptr<Xyzz<F>>(lane.rows), ptr<Xyzz<F>>(lane.cols), sh.Lw,
-                  sh.H, d_window_sums, sum_stride);
+        MSM_LAUNCH((k_msm_fold_final<F, FS>), g.fold_final, s, ptr<Xyzz<F>>(lane.rows), ptr<Xyzz<F>>(lane.cols), sh.Lw, sh.H, d_window_sums, sum_stride);
     }
     if (h_window_sums)          // the lane's own copy-out (pinned host memory of the proof slot: truly asynchronous)
-        for (int t = 0; t < nt; ++t)
-            dev_d2h_pinned(h_window_sums + (size_t)t * sum_stride, d_window_sums + (size_t)t * sum_stride, (size_t)sh.nsums() * sizeof(Xyzz<FS>), s);
+        for (int t = 0; t < nt; ++t) dev_d2h_pinned(h_window_sums + (size_t)t * sum_stride, d_window_sums + (size_t)t * sum_stride, g.sums_bytes, s);
     event_record(lane.done, s);
 }
 // number of points at infinity among the first `count` entries (level 0) of a packed table; synchronises ctx->stream

@@ -22,6 +22,7 @@
 #pragma once
 #include "devrt.h"
 #include "ec.cuh"
+#include "msm_geom.h"   // the launch constants (MSM_COARSE_BITS, SCAN_*, MSM_HEAVY_*, ZK_SORT_THREADS, ...) and MsmCut: the host's arithmetic needs them too
 
 namespace zk {
 
@@ -100,7 +101,6 @@ template <> struct MsmTuning<Fu2<Bls377Fq>> : MsmTuning<Fu2<Bls381Fq>> {};
 // dynamic LDS of one accumulation workgroup (256 work-items): the coordinates of the running sum that live there, word-major
 template <class F> constexpr size_t msm_accum_lds_bytes() { return (size_t)((MsmTuning<F>::ZZ_IN_LDS ? 2 : 0) + (MsmTuning<F>::XY_IN_LDS ? 2 : 0)) * (sizeof(F) / 4) * 256 * 4; }
 // the base tables of the MSMs one launch serves (A, B1 and L of a proof share the sort of the assignment)
-static constexpr int MSM_MAX_TABLES = 3;
 struct MsmTables {
     const void* p[MSM_MAX_TABLES];
 };
@@ -155,11 +155,6 @@ __global__ void k_points_to_packed(const Aff<FS>* __restrict__ in, AffPacked<U>*
 }
 
 static constexpr u32 MSM_NO_DIGIT = 0xffffffffu;
-// work-items of a sort workgroup (one workgroup per CU: its histogram takes up to 128 KiB of LDS); 1024 measured the same as
-// 512 (profiles/r3e_sort_workgroup_ab.txt)
-#ifndef ZK_SORT_THREADS
-#define ZK_SORT_THREADS 512
-#endif
 static constexpr u32 MSM_HEAVY = 16;  // a bucket spread over more slices than this is reduced by a whole workgroup (a value repeated
                                       // across a witness — the constant in every first S-box of a Poseidon chain, the ones of a
                                       // boolean-heavy assignment — would otherwise be summed serially by one work-item of the fold)
@@ -325,8 +320,7 @@ static __global__ void __launch_bounds__(ZK_SORT_THREADS) k_msm_place(const u32*
 //   k_msm_part_fine     a workgroup = one tile of one region: 256 counters, one global atomic per touched bucket, entries placed
 //                       into runs of ~8 per (tile, bucket) inside a 0.25 MB region of `sorted` that the L2 keeps whole.
 // Same result as k_msm_place up to the order of the entries inside a bucket, which no consumer depends on.
-static constexpr u32 MSM_COARSE_BITS = 8;                 // keys per coarse bin = 256 (a window narrower than 9 bits takes k_msm_place)
-static constexpr u32 MSM_FINE_TILE = 2048;                // pairs per workgroup of the fine pass (8 per work-item)
+// (MSM_COARSE_BITS = 8: keys per coarse bin = 256; MSM_FINE_TILE = 2048 pairs per workgroup of the fine pass, 8 per work-item: msm_geom.h)
 static __global__ void __launch_bounds__(256) k_msm_part_coarse(const u32* __restrict__ dig, u64 n, int c, int W, u64 chunk, u32 sets, u64 idx_stride,
                                                               const u32* __restrict__ off, u32* __restrict__ ccur, unsigned long long* __restrict__ pairs,
                                                               const u32* __restrict__ keep) {
@@ -371,7 +365,6 @@ static __global__ void __launch_bounds__(256) k_msm_part_coarse(const u32* __res
     }
 }
 // tile_off[r] = tiles of the coarse regions before r (tile_off[nbins] = all of them); one workgroup, nbins <= a few thousand
-static constexpr int MSM_TILE_SCAN_THREADS = 256;
 static __global__ void k_msm_tile_offsets(const u32* __restrict__ off, u32 nbins, u32* __restrict__ tile_off) {
     ZK_PRIO_HIGH();
     __shared__ u32 sh[MSM_TILE_SCAN_THREADS];
@@ -445,8 +438,7 @@ static __global__ void __launch_bounds__(256) k_msm_part_fine(const unsigned lon
 // one launch where round 5 ran three (k_scan_local / _chunks / _add below: kept for more counters than one workgroup takes) and
 // the two-level placement a fourth.  Tiles of 4096 counters: a work-item loads four consecutive ones (coalesced 16-byte loads), the
 // wavefront scans its 64 sums with lane shuffles, the 16 wavefronts' totals meet in LDS, a running carry links the tiles.
-static constexpr u32 SCAN_ONE_THREADS = 256, SCAN_ONE_PER = 16, SCAN_ONE_MAX = 1u << 17;
-// (256 work-items: one wavefront per SIMD and 20 registers — a workgroup that finds a place beside accumulation kernels; a first
+// (SCAN_ONE_THREADS = 256 work-items of SCAN_ONE_PER = 16 counters a round, at most SCAN_ONE_MAX = 2^17 counters: msm_geom.h.  256: one wavefront per SIMD and 20 registers — a workgroup that finds a place beside accumulation kernels; a first
 // version with 1024 work-items needed a whole CU to itself and waited 2.5 ms for one in a lone proof's trace)
 static __device__ __forceinline__ u32 wave_inclusive_scan(u32 v) {
     const u32 lane = threadIdx.x & 63u;
@@ -543,10 +535,7 @@ static __global__ void __launch_bounds__(256) k_scan_one(const u32* __restrict__
     if (t == 0) tile_off[nbins] = tcarry;
 }
 // ---- 2a. exclusive scan of the counters: one workgroup per chunk of SCAN_CHUNK counters ----
-static constexpr int SCAN_THREADS = 256;
-static constexpr int SCAN_PER_THREAD = 16;
-static constexpr int SCAN_CHUNK = SCAN_THREADS * SCAN_PER_THREAD;
-
+// (SCAN_THREADS = 256 work-items of SCAN_PER_THREAD = 16 counters each: msm_geom.h)
 static __global__ void k_scan_local(const u32* __restrict__ cnt, u32* __restrict__ off, u32* __restrict__ chunk_sum, u64 total) {
     ZK_PRIO_HIGH();
     __shared__ u32 sh[SCAN_THREADS];
@@ -607,7 +596,7 @@ static __global__ void k_scan_add(u32* __restrict__ off, const u32* __restrict__
 // The list (length total = off[nkeys], known only on the device) is cut into nlanes slices of P = max(ceil(total / nlanes),
 // min_slice) entries: with nlanes = the number of work-items the machine holds, every work-item of the accumulation
 // kernel does the same number of additions in ONE round of workgroups, whatever the scalars look like.
-struct MsmCut { u32 nlanes, min_slice; u32 table_len; };   // table_len: entries of a base table (levels x points), for the checked build
+// (MsmCut {nlanes, min_slice, table_len}: msm_geom.h)
 static __device__ __forceinline__ u32 msm_slice_len(const u32* __restrict__ off, u32 nkeys, MsmCut cut) {
     const u32 total = off[nkeys];
     const u32 P = (total + cut.nlanes - 1) / cut.nlanes;
@@ -902,13 +891,11 @@ __device__ __forceinline__ Xyzz<F> xyzz_mul_small(const Xyzz<F>& p, u32 k) {
 //     G2 in a trace of zokrates_amd/sha256_circuit.py), so k_msm_heavy_reduce goes first: the partials of a heavy bucket are cut
 //     into MSM_HEAVY_CHUNKS runs, workgroup c sums run c of every heavy bucket into the run's first slot, and the row's
 //     workgroup below only adds the run heads.  With an empty list the kernel returns at once.
-static constexpr u32 MSM_HEAVY_CHUNKS = 64;
-// work-items per workgroup of k_msm_heavy_reduce.  The kernel is launched whether or not a heavy bucket exists (the list is on the
+// MSM_HEAVY_THREADS = 64 (msm_geom.h, with MSM_HEAVY_CHUNKS = 64) work-items per workgroup of k_msm_heavy_reduce.  The kernel is launched whether or not a heavy bucket exists (the list is on the
 // device) and must find a place before it can return: one wave and 9 / 18 KB of LDS (G1 / G2) instead of four and 36 / 73 at 256 is a
 // place found sooner beside the accumulations, and a run of a heavy bucket is 8 serial additions + 6 tree levels instead of 2 + 8.
 // Lone dense proofs: median 9.61 against 9.78 ms over three processes of 40 each, the stdlib SHA-256 circuit (which HAS heavy
 // buckets) and the others level (profiles/r7s_*, r7q_*)
-static constexpr unsigned MSM_HEAVY_THREADS = 64;
 struct HeavyRun {
     u32 g0, g1, len;     // the bucket's lanes [g0, g1], lanes per run
 };

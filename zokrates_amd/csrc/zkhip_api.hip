@@ -329,9 +329,9 @@ int32_t zkhip_ctx_create(int32_t device, zkhip_ctx** out) {
 
         ctx->ws = ctx->stream;
         ctx->serial = getenv("ZKHIP_SERIAL") != nullptr;
-        ctx->msm_c_env = env_int("ZKHIP_MSM_C", 2, MSM_MAX_C, 0);
-        ctx->msm_sets = env_int("ZKHIP_MSM_SETS", 1, 64, 0);
-        ctx->msm_waves = env_int("ZKHIP_MSM_WAVES", 1, 8, 0);
+        ctx->msm.msm_c_env = env_int("ZKHIP_MSM_C", 2, MSM_MAX_C, 0);
+        ctx->msm.msm_sets = env_int("ZKHIP_MSM_SETS", 1, 64, 0);
+        ctx->msm.msm_waves = env_int("ZKHIP_MSM_WAVES", 1, 8, 0);
         ctx->ntt_single_max = env_int("ZKHIP_NTT_SINGLE_MAX_LOG", 0, NTT_MAX_SUBLOG, 10);
         ctx->ntt_max_sublog = env_int("ZKHIP_NTT_MAX_SUBLOG", 2, NTT_MAX_SUBLOG, NTT_MAX_SUBLOG);
         ctx->ntt_cols = env_int("ZKHIP_NTT_COLS", 1, 8, 2);
@@ -341,12 +341,12 @@ int32_t zkhip_ctx_create(int32_t device, zkhip_ctx** out) {
         ctx->g2_head_start = env_int("ZKHIP_G2_HEAD_START", 0, 2, 1);
         ctx->split_min_log = env_int("ZKHIP_SPLIT_MIN_LOG", 0, 40, 18);
         ctx->fuse_z = env_int("ZKHIP_FUSE_Z", 0, 1, 1) != 0;
-        ctx->heavy_runs = env_int("ZKHIP_MSM_HEAVY_RUNS", 0, 1, 1) != 0;
-        { const int hg = env_int("ZKHIP_FOLD_HG", 1, 256, 32); ctx->fold_hg = 1 << ilog2_floor((u64)hg); }
-        ctx->msm_fused_waves = env_int("ZKHIP_MSM_FUSED_WAVES", 1, 8, 0);
-        ctx->msm_g1_waves = env_int("ZKHIP_MSM_G1_WAVES", 1, 16, 0);
-        ctx->msm_g2_waves = env_int("ZKHIP_MSM_G2_WAVES", 1, 16, 0);
-        ctx->sort_wgs = (u32)env_int("ZKHIP_SORT_WGS", 16, 4096, 256);
+        ctx->msm.heavy_runs = env_int("ZKHIP_MSM_HEAVY_RUNS", 0, 1, 1) != 0;
+        { const int hg = env_int("ZKHIP_FOLD_HG", 1, 256, 32); ctx->msm.fold_hg = 1 << ilog2_floor((u64)hg); }
+        ctx->msm.msm_fused_waves = env_int("ZKHIP_MSM_FUSED_WAVES", 1, 8, 0);
+        ctx->msm.msm_g1_waves = env_int("ZKHIP_MSM_G1_WAVES", 1, 16, 0);
+        ctx->msm.msm_g2_waves = env_int("ZKHIP_MSM_G2_WAVES", 1, 16, 0);
+        ctx->msm.sort_wgs = (u32)env_int("ZKHIP_SORT_WGS", 16, 4096, 256);
         ctx->ntt_fuse_first = env_int("ZKHIP_NTT_FUSE_FIRST", 0, 1, 1);
         if (const char* e = getenv("ZKHIP_PIPES")) ctx->pipe_plan = (e[0] == '-' || e[0] == '0') ? "" : (e[0] == '1' && !e[1]) ? ZK_PIPE_PLAN_RESIDENT : e;
         // every (slot, lane) has a stream of its own: with one stream per lane shared by the slots, the accumulation of
@@ -366,7 +366,7 @@ int32_t zkhip_ctx_create(int32_t device, zkhip_ctx** out) {
         snprintf(buf, sizeof(buf), "zkhip on %s (%s), %d CUs, %.0f GiB", prop.name, prop.gcnArchName, prop.multiProcessorCount,
                  prop.totalGlobalMem / 1073741824.0);
         ctx->desc = buf;
-        ctx->cus = std::max(1, prop.multiProcessorCount);
+        ctx->msm.cus = std::max(1, prop.multiProcessorCount);
         lap("device properties");
 #endif
         *out = ctx.release();
@@ -436,15 +436,15 @@ int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value) {
     return guarded(ctx, [&] {
         auto in = [&](int lo, int hi) { require(value >= lo && value <= hi, ZKHIP_ERR_BAD_ARG, "tunable value out of range"); };
         switch (which) {
-            case ZKHIP_TUNE_MSM_C: if (value) in(2, MSM_MAX_C); ctx->msm_c_env = value; break;
-            case ZKHIP_TUNE_MSM_SETS: in(0, 64); ctx->msm_sets = value; break;
-            case ZKHIP_TUNE_SKIP_INF: in(0, 2); ctx->skip_inf_mode = value; break;
+            case ZKHIP_TUNE_MSM_C: if (value) in(2, MSM_MAX_C); ctx->msm.msm_c_env = value; break;
+            case ZKHIP_TUNE_MSM_SETS: in(0, 64); ctx->msm.msm_sets = value; break;
+            case ZKHIP_TUNE_SKIP_INF: in(0, 2); ctx->msm.skip_inf_mode = value; break;
             case ZKHIP_TUNE_B_SORT: in(0, 2); ctx->b_sort_mode = value; break;
-            case ZKHIP_TUNE_HEAVY_RUNS: in(0, 1); ctx->heavy_runs = value != 0; break;
-            case ZKHIP_TUNE_MSM_WAVES: in(0, 8); ctx->msm_waves = value; break;
-            case ZKHIP_TUNE_MSM_LANES: in(0, 1 << 24); ctx->msm_lanes = (u32)value; break;
-            case ZKHIP_TUNE_MSM_MIN_SLICE: in(1, 1 << 20); ctx->msm_min_slice = (u32)value; break;
-            case ZKHIP_TUNE_FOLD_SCAN: in(0, 1); ctx->fold_scan = value != 0; break;
+            case ZKHIP_TUNE_HEAVY_RUNS: in(0, 1); ctx->msm.heavy_runs = value != 0; break;
+            case ZKHIP_TUNE_MSM_WAVES: in(0, 8); ctx->msm.msm_waves = value; break;
+            case ZKHIP_TUNE_MSM_LANES: in(0, 1 << 24); ctx->msm.msm_lanes = (u32)value; break;
+            case ZKHIP_TUNE_MSM_MIN_SLICE: in(1, 1 << 20); ctx->msm.msm_min_slice = (u32)value; break;
+            case ZKHIP_TUNE_FOLD_SCAN: in(0, 1); ctx->msm.fold_scan = value != 0; break;
             case ZKHIP_TUNE_SERIAL: in(0, 1); dev_sync_all(); ctx->serial = value != 0; break;
             case ZKHIP_TUNE_NTT_SINGLE_MAX_LOG: in(0, NTT_MAX_SUBLOG); dev_sync_all(); ctx->ntt_single_max = value; ctx->plans.clear(); break;
             case ZKHIP_TUNE_NTT_MAX_SUBLOG: in(2, NTT_MAX_SUBLOG); dev_sync_all(); ctx->ntt_max_sublog = value; ctx->plans.clear(); break;
@@ -456,9 +456,9 @@ int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value) {
                 require(!ctx->pipes_made, ZKHIP_ERR_BAD_ARG, "the streams of this context exist already: the plan is chosen before its first proof");
                 if (!getenv("ZKHIP_PIPES")) ctx->pipe_plan = value ? ZK_PIPE_PLAN_RESIDENT : "";
                 break;
-            case ZKHIP_TUNE_FOLD_HG: in(1, 256); ctx->fold_hg = 1 << ilog2_floor((u64)value); break;
+            case ZKHIP_TUNE_FOLD_HG: in(1, 256); ctx->msm.fold_hg = 1 << ilog2_floor((u64)value); break;
             case ZKHIP_TUNE_FUSE_Z: in(0, 1); ctx->fuse_z = value != 0; break;
-            case ZKHIP_TUNE_MSM_FUSED_WAVES: in(0, 8); ctx->msm_fused_waves = value; break;
+            case ZKHIP_TUNE_MSM_FUSED_WAVES: in(0, 8); ctx->msm.msm_fused_waves = value; break;
             case ZKHIP_TUNE_STREAM_JITTER: in(0, 5000); dev_sync_all(); jitter_state().max_us.store(value); break;
             case ZKHIP_TUNE_NTT_COLS:
                 in(1, 8);
