@@ -201,6 +201,10 @@ int32_t zkhip_ctx_clock_probe(zkhip_ctx* ctx, uint32_t duration_us, double* ghz_
 #define ZKHIP_TUNE_NTT_MAX_SUBLOG 16 /* log2 of the longest sub-transform of an NTT pass (2..11; default 11): domains above 2^(2 x this)
                                       * take three passes instead of two — a test hook to reach the three-pass path (domains above
                                       * 2^22) with small domains.  Keys loaded before a change must be reloaded (their h order)        */
+#define ZKHIP_TUNE_EXEC_CHUNK 29       /* instances per chunk of zkhip_compute_witness (1 .. 65535 x 64); 0 (default): as many whole waves as fit half of the
+                                         device memory that is free (or held by the context's buffers of an earlier call), 32 GiB and 65536 instances at most, at
+                                         the bytes a chunk keeps per instance: (zkhip_xplan_dims [7]) of value store, the arguments, and the file and the inputs
+                                         where they are asked for.  A test hook as well: it puts the chunk seams wherever a tiny program needs them */
 int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value);
 
 /* ---- proving key ----
@@ -345,6 +349,71 @@ int32_t zkhip_wplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r
 void zkhip_wplan_free(zkhip_wplan* plan);
 int32_t zkhip_assignment_upload_witness(zkhip_ctx* ctx, const zkhip_wplan* plan, const uint8_t* witness, size_t len,
                                         uint8_t* inputs_out, uint64_t inputs_cap, uint64_t* n_inputs, zkhip_assignment** out);
+
+/* ---- witnesses computed on the device ----
+ * A host that holds a program and its ARGUMENTS runs `zokrates compute-witness` per proof: the reference's interpreter
+ * (/root/reference/zokrates_interpreter/src/lib.rs:30-138) is one thread that walks the statements over a BTreeMap, and its `witness`
+ * file is what the calls above then read.  A program is a straight-line list and no control flow depends on a value, so a BATCH of
+ * instances executes the same statement at the same time: one work-item per instance, the program compiled once into an instruction
+ * stream (csrc/xplan.h), the values in device memory instance-minor (csrc/wexec.cuh).  Opt-in: a prove call, upload or queue that
+ * never asks for a plan makes the launches and bytes it made before.  A lone instance runs on one lane and is slow; the route pays in
+ * batches (DESIGN.md section 3 has the measurement).
+ *
+ * The plan.  zkhip_xplan_create walks the statements section of the same `out` bytes `prog` was parsed from a second time, with the
+ * combinations RAW (no duplicates merged, no zero coefficients dropped), and compiles them in one pass with the set of variables
+ * defined so far — ~one and the arguments at the start; a repeated parameter keeps its last value:
+ *   Constraint   `lin` of exactly one raw term with coefficient 1 whose variable is not yet defined: a DEFINE, var = left * right;
+ *                otherwise a CHECK, left * right == lin (LinComb::is_assignee, zokrates_ast/src/ir/expression.rs:218-222).  A
+ *                combination is the sum over its raw terms, the empty one is 0.  Spans and error annotations are skipped.
+ *   Directive    the inputs are evaluated as QuadCombs, the outputs stored (they overwrite a defined variable) and defined.  Solvers:
+ *                ConditionEq, Bits(n), Div, Xor, Or, ShaAndXorAndXorAnd, ShaCh, EuclideanDiv, with the input and output counts of
+ *                Solver::get_signature (zokrates_ast/src/common/solvers.rs:52-69).  Bits is `to_bits_be` cut to the modulus' bit
+ *                length, without the interpreter's out-of-range trial (Interpreter::default()); Div by zero is 1; EuclideanDiv by zero
+ *                is quotient 0, remainder n.
+ *   Log          skipped.
+ * Refused with ZKHIP_ERR_BAD_ARG and a message that names the statement number: a statement that reads a variable nothing has
+ * defined yet (the variable in the reader's spelling: _k, ~out_k — the reference would panic there); a solver's wrong input or output
+ * count; any other solver — Zir, Ref, Sha256Round, SnarkVerifyBls12377, an unknown name — "... keeps the host interpreter", the
+ * solver named.  Refused as well: an `r1cs` of another curve, n, l or w than `prog`; `out` bytes of another curve, constraint count,
+ * variable order (hence l, w) or argument list than `prog` — the plan checks that it walked the program `prog` was parsed from.  Bytes
+ * that are no program are ZKHIP_ERR_PARSE.  The plan keeps the instruction stream, a pool of coefficients in the kernel's form, the
+ * slot of every variable (column j of the R1CS is slot j; a variable the system has no column for — a directive output no constraint
+ * mentions — sits at or above m = l + w), the ascending signed ids of every variable the interpreter's Witness would hold (the
+ * order of the reference's `witness` file: ~out_1, ~out_0, ~one, _0, ...) and the public-input columns.  Tied to its context (a call
+ * with another context's plan is refused); of `r1cs` it keeps what it needs — l, w, the columns — and reads nothing again, so the plan
+ * outlives it, and the assignments it delivers fit every system of the same program.  Freed and made again at will; it enqueues copies, so it is refused while a split proof or a queue is pending.
+ *   zkhip_xplan_dims: out[0] arguments, [1] statements executed, [2] defines, [3] checks, [4] directives, [5] entries of a witness
+ *   file, [6] variables without a column, [7] device bytes of value store per instance
+ *
+ * zkhip_compute_witness runs `count` instances.  args: count x arguments x 32 B canonical LE.  Each of assignments_out (count
+ * handles), witness_out (count x witness_cap_each BYTES), inputs_out (count x inputs_cap_each ELEMENTS of 32 B), first_statement and
+ * first_row may be NULL; status (count) may not.  Per instance: status[i] = ZKHIP_OK or ZKHIP_ERR_UNSATISFIED; an ordinary
+ * zkhip_assignment — m canonical integers in ark order, column 0 = 1, in a buffer of m + 2, exactly what zkhip_assignment_upload
+ * leaves, so every *_resident call, zkhip_queue_submit(z_resident) and zkhip_r1cs_check work unchanged (the caller frees it); the
+ * reference's `witness` bytes (u64 count, then (i64 id, 32-byte LE value) by ascending id: the first 8 + 40 x dims[5] bytes of the
+ * instance's share, the rest is not touched); public_inputs_values (public arguments in argument order, then ~out_0 ..).  A failed
+ * instance gets a NULL handle, a zero-filled file and zero-filled inputs, first_statement[i] = the lowest failing item of the
+ * statements section (logs and directives are counted) and first_row[i] = the R1CS row of that constraint, which is what
+ * zkhip_r1cs_check names; an instance that ran through has UINT64_MAX in both.
+ * Returns ZKHIP_OK if every instance ran through; ZKHIP_ERR_UNSATISFIED if any did not — the others are delivered, as checked proving
+ * delivers them, and zkhip_last_error names the first failing instance, its statement and its row.  An argument at or above r:
+ * ZKHIP_ERR_PARSE before anything is enqueued, the message names the instance and the argument.  A cap that is too small, a plan of
+ * another context or a NULL: ZKHIP_ERR_BAD_ARG.  count == 0 is ZKHIP_OK and touches nothing.  The call works through `count` in
+ * chunks (ZKHIP_TUNE_EXEC_CHUNK); the context keeps the buffers of its largest chunk — by default up to half of the free device memory,
+ * 32 GiB at most — until zkhip_ctx_free, so a context that shares its device with large keys names a chunk.  The assignments are
+ * NOT part of that budget: (m + 2) x 32 B per delivered instance, all of a call's at once (190 GB for 4 096 instances of a program of
+ * 1.45 M columns), are the caller's to fit — ask for fewer instances per call, or free each handle after its proof
+ * (ZKHIP_ERR_DEVICE / _NOMEM otherwise: no handle is delivered).
+ * Call discipline as zkhip_pairing_products: a stream and buffers of its own, no proof slot touched — allowed while a proof queue is
+ * open (a service computes the next batch between submits and hands the handles to zkhip_queue_submit), refused while a split proof
+ * is pending.  Nothing consults the environment. */
+typedef struct zkhip_xplan zkhip_xplan;
+int32_t zkhip_xplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r1cs* r1cs, const uint8_t* out_bytes, size_t len, zkhip_xplan** out);
+void zkhip_xplan_free(zkhip_xplan* plan);
+int32_t zkhip_xplan_dims(const zkhip_xplan* plan, uint64_t out[8]);
+int32_t zkhip_compute_witness(zkhip_ctx* ctx, const zkhip_xplan* plan, uint32_t count, const uint8_t* args, zkhip_assignment** assignments_out,
+                              uint8_t* witness_out, uint64_t witness_cap_each, uint8_t* inputs_out, uint64_t inputs_cap_each, int32_t* status,
+                              uint64_t* first_statement, uint64_t* first_row);
 
 /* Steady-state variant for proofs/sec: `count` assignments (each m x 32 B, contiguous), `count`
  * (r, s) pairs (64 B each) and `count` proof slots (8*sz(Fq)+3 B each).  Same results as `count`

@@ -21,6 +21,7 @@
 // integration/zokrates_hip (source only); this layer is what is compiled, tested and shipped here (tools: zkhip-cli).
 #pragma once
 #include <array>
+#include <cstring>
 #include <cstdint>
 #include <map>
 #include <stdexcept>
@@ -192,6 +193,50 @@ class System {
     mutable std::string plan_why_;
 };
 
+// A program's statements compiled for the device (zkhip.h "witnesses computed on the device": zkhip_xplan_create), for
+// Hip::compute_witness.  Made from the System and the bytes of the `out` file its Program was parsed from; the System must outlive it.
+class ExecPlan {
+  public:
+    ExecPlan() = default;
+    ~ExecPlan();
+    ExecPlan(ExecPlan&& o) noexcept : plan_(o.plan_), system_(o.system_) { memcpy(dims_, o.dims_, sizeof dims_); o.plan_ = nullptr; }
+    ExecPlan& operator=(ExecPlan&& o) noexcept;
+    ExecPlan(const ExecPlan&) = delete;
+    ExecPlan& operator=(const ExecPlan&) = delete;
+    zkhip_xplan* get() const { return plan_; }
+    const System& system() const { return *system_; }
+    uint64_t arguments() const { return dims_[0]; }
+    uint64_t statements() const { return dims_[1]; }
+    uint64_t witness_bytes() const { return 8 + 40 * dims_[5]; }      // the length of the program's `witness` file
+    uint64_t store_bytes_per_instance() const { return dims_[7]; }
+    explicit operator bool() const { return plan_ != nullptr; }
+
+  private:
+    friend class Hip;
+    zkhip_xplan* plan_ = nullptr;
+    const System* system_ = nullptr;
+    uint64_t dims_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+// One instance of Hip::compute_witness: the reference's `witness` bytes (if asked for), public_inputs_values, and the assignment
+// resident on the device for Hip::prove — or, for an instance that failed a check, the statement of the `out` file and the R1CS row.
+struct ComputedWitness {
+    bool satisfied = false;
+    uint64_t first_statement = 0, first_row = 0;      // (of a failed instance)
+    std::vector<uint8_t> file, inputs;                // inputs: 32-byte LE values
+    zkhip_assignment* z = nullptr;
+    ComputedWitness() = default;
+    ~ComputedWitness() { if (z) zkhip_assignment_free(z); }
+    ComputedWitness(ComputedWitness&& o) noexcept : satisfied(o.satisfied), first_statement(o.first_statement), first_row(o.first_row), file(std::move(o.file)),
+                                                   inputs(std::move(o.inputs)), z(o.z) { o.z = nullptr; }
+    ComputedWitness& operator=(ComputedWitness&& o) noexcept {
+        if (this != &o) { if (z) zkhip_assignment_free(z); satisfied = o.satisfied; first_statement = o.first_statement; first_row = o.first_row;
+                          file = std::move(o.file); inputs = std::move(o.inputs); z = o.z; o.z = nullptr; }
+        return *this;
+    }
+    ComputedWitness(const ComputedWitness&) = delete;
+    ComputedWitness& operator=(const ComputedWitness&) = delete;
+};
+
 // NonUniversalBackend::setup's result (zokrates_proof_systems/src/lib.rs:59-65,113-118): the verification key as the text of
 // `verification.key` (scheme/groth16.rs:18-25, scheme/gm17.rs:19-27) and the proving key in ark's serialize_unchecked bytes
 struct SetupKeypair {
@@ -311,6 +356,16 @@ class Hip {
     // variables the program lacks are ignored).  Off by default; returns the previous setting.
     bool set_device_witness(bool on) { const bool was = device_witness_; device_witness_ = on; return was; }
     bool last_witness_on_device() const { return last_on_device_; }
+    // Witnesses computed on the device (zkhip.h "witnesses computed on the device"): what `zokrates compute-witness` does on one host
+    // thread, for a BATCH of argument lists in one launch.  load_exec_plan compiles the statements of `program_bytes` (the `out` file
+    // the System's Program was parsed from) and throws Error(ZKHIP_ERR_BAD_ARG, "... keeps the host interpreter") for a program the
+    // device does not run (asm blocks, the bellman SHA round, the in-circuit verifier).  compute_witness takes count x arguments x 32
+    // bytes (canonical LE) and returns one ComputedWitness per instance; an instance that fails a check comes back with satisfied =
+    // false and the others are delivered.  A lone instance runs on one lane: the route pays in batches.  prove() over a
+    // ComputedWitness proves from its resident assignment: the same Proof as prove() over its `file`.
+    ExecPlan load_exec_plan(const System& system, const uint8_t* program_bytes, size_t program_len);
+    std::vector<ComputedWitness> compute_witness(const ExecPlan& plan, const uint8_t* args, uint32_t count, bool want_files = true);
+    Proof prove(Scheme scheme, const System& system, const ComputedWitness& witness, const Key& key, StdRng& rng, Timings* timings = nullptr);
     // a long-lived prover fed one witness at a time: a proof queue over a resident system and key (see Queue above)
     Queue open_queue(Scheme scheme, const System& system, const Key& key);
     std::string describe() const;

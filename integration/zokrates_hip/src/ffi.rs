@@ -10,6 +10,7 @@ use std::os::raw::c_char;
 #[repr(C)] pub struct zkhip_assignment { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_queue { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_wplan { _p: [u8; 0] }
+#[repr(C)] pub struct zkhip_xplan { _p: [u8; 0] }
 #[repr(C)] pub struct zkhip_vk { _p: [u8; 0] }
 /// zkhip_queue_submit*: as many proofs in flight as the queue holds; collect one first
 pub const ZKHIP_ERR_BUSY: i32 = -6;
@@ -65,6 +66,15 @@ extern "C" {
     pub fn zkhip_assignment_upload_witness(ctx: *mut zkhip_ctx, plan: *const zkhip_wplan, witness: *const u8, len: usize,
         inputs_out: *mut u8, inputs_cap: u64, n_inputs: *mut u64, out: *mut *mut zkhip_assignment) -> i32;
     pub fn zkhip_assignment_free(z: *mut zkhip_assignment);
+    // witnesses computed on the device: a program's statements compiled once (the plan), then `count` argument lists executed in one
+    // launch into resident assignments, the reference's `witness` bytes and the public inputs
+    pub fn zkhip_xplan_create(ctx: *mut zkhip_ctx, prog: *const zkhip_prog, r1cs: *const zkhip_r1cs, out_bytes: *const u8, len: usize,
+        out: *mut *mut zkhip_xplan) -> i32;
+    pub fn zkhip_xplan_free(plan: *mut zkhip_xplan);
+    pub fn zkhip_xplan_dims(plan: *const zkhip_xplan, out: *mut u64) -> i32;
+    pub fn zkhip_compute_witness(ctx: *mut zkhip_ctx, plan: *const zkhip_xplan, count: u32, args: *const u8,
+        assignments_out: *mut *mut zkhip_assignment, witness_out: *mut u8, witness_cap_each: u64, inputs_out: *mut u8,
+        inputs_cap_each: u64, status: *mut i32, first_statement: *mut u64, first_row: *mut u64) -> i32;
     pub fn zkhip_prove_g16_resident(ctx: *mut zkhip_ctx, pk: *const zkhip_pk, cs: *const zkhip_r1cs, z: *mut zkhip_assignment,
         r: *const u8, s: *const u8, proof_out: *mut u8, timings: *mut zkhip_timings) -> i32;
     // key cache: the resident form of a loaded key as one image

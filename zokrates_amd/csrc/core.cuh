@@ -29,6 +29,8 @@
 #include "zpack.cuh"
 #include "wingest.cuh"
 #include "wplan.h"
+#include "wexec.cuh"
+#include "xplan.h"
 
 namespace zk {
 
@@ -240,6 +242,10 @@ struct zkhip_ctx {
     Stream verify_stream = 0; // the pairing checks (pairing.cuh): a stream and buffers of their own, so that they may run while a proof queue is open
     bool verify_made = false;
     DBuf vfy[11];
+    Stream exec_stream = 0;   // witnesses computed on the device (wexec.cuh): a stream and buffers of their own, as the pairing checks have
+    bool exec_made = false;
+    DBuf xstore, xargs, xverdict, xptrs, xfile, xinputs;   // the value store of a chunk, its arguments, verdict words, z pointers, files and inputs; kept between calls
+    int exec_chunk = 0;       // instances per chunk of zkhip_compute_witness (ZKHIP_TUNE_EXEC_CHUNK; 0: from the store's bytes per instance, exec_chunk_default)
     DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed, zkhip_queue_submit_packed); kept between calls
     std::vector<std::unique_ptr<NttPlanBase>> plans;
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
@@ -576,6 +582,32 @@ struct zkhip_wplan {
     std::shared_ptr<const WPlanTables> host;
     DBuf pos, neg;
 };
+
+// zkhip_xplan: the statements of one program compiled for k_exec_program (xplan.h), resident: the instruction stream, the
+// coefficients, the entries of a witness file and the public-input slots on the device, and the host's copy.  (What it has of the
+// constraint system it was made from — l, w, the columns — is in the host's copy: nothing of the system is read again.)
+struct zkhip_xplan {
+    zkhip_ctx* ctx = nullptr;
+    std::shared_ptr<const XPlanHost> host;
+    DBuf code, pool, file_ids, file_slots, input_cols;
+};
+static inline Stream ctx_exec_stream(zkhip_ctx* ctx) {
+    if (!ctx->exec_made) { ctx->exec_stream = stream_create(); ctx->exec_made = true; }
+    return ctx->exec_stream;
+}
+// Instances per chunk when the caller names none.  `bytes_per_instance`: everything the call keeps per instance of a chunk — the value
+// store (slots x 32 B: 32 MiB for a program of 2^20 variables), the arguments, and the file and the inputs where they are asked for.  The
+// kernel wants as many waves as the device has room for: half of the device memory that is free or already held by this context's
+// exec buffers (so that a second call finds the chunk of the first), 32 GiB at most, in whole waves (one wave at least, 65536
+// instances at most).  The other half is left to the assignments the call delivers, which are the caller's to budget.
+static inline u64 exec_chunk_default(const zkhip_ctx* ctx, u64 bytes_per_instance) {
+    size_t free_b = 0, total_b = 0;
+    dev_mem_info(&free_b, &total_b);
+    const u64 held = ctx->xstore.cap + ctx->xargs.cap + ctx->xverdict.cap + ctx->xptrs.cap + ctx->xfile.cap + ctx->xinputs.cap;
+    const u64 budget = std::min<u64>(((u64)free_b + held) / 2, (u64)32 << 30);
+    const u64 fit = budget / std::max<u64>(bytes_per_instance, 32);
+    return std::min<u64>(std::max<u64>(fit / WX_BLOCK * WX_BLOCK, WX_BLOCK), 65536);
+}
 
 namespace zk {
 
@@ -2233,6 +2265,86 @@ struct Prover {
         require_verdict(verdict[0], verdict[2], wz.plan->host.get());
     }
 
+    // ---- witnesses computed on the device (wexec.cuh): `count` instances of the plan's program, a chunk at a time, on the context's
+    // exec stream and in its exec buffers — no proof slot, no other stream.  Per chunk: the arguments in, k_exec_program, the verdict
+    // words back (the host makes a resident assignment for every instance that ran through), then the gathers and the copies out.
+    // made[i]: the assignment of instance i, or null.  Returns the number of instances that failed a check.
+    static u64 compute_witness(zkhip_ctx* ctx, const zkhip_xplan* plan, u32 count, const uint8_t* args, std::vector<std::unique_ptr<zkhip_assignment>>* made,
+                               uint8_t* witness_out, u64 witness_cap_each, uint8_t* inputs_out, u64 inputs_cap_each, int32_t* status, u64* first_statement,
+                               u64* first_row) {
+        const XPlanHost& h = *plan->host;
+        Stream s = ctx_exec_stream(ctx);
+        const u64 m = h.l + h.w, n_in = h.input_cols.size(), entries = h.file_ids.size(), file_bytes = h.file_bytes();
+        const u64 per_instance = h.store_bytes_per_instance() + h.n_args * 32 + 4 + sizeof(void*) + (witness_out ? file_bytes : 0) + (inputs_out ? n_in * 32 : 0);
+        const u64 chunk = std::min<u64>(ctx->exec_chunk > 0 ? (u64)ctx->exec_chunk : exec_chunk_default(ctx, per_instance), count);
+        ctx->xstore.ensure(h.slots * chunk * sizeof(Fr));
+        ctx->xargs.ensure(std::max<u64>(h.n_args, 1) * chunk * 32);
+        ctx->xverdict.ensure(chunk * 4);
+        if (made) ctx->xptrs.ensure(chunk * sizeof(void*));
+        if (witness_out) ctx->xfile.ensure(chunk * file_bytes);
+        if (inputs_out) ctx->xinputs.ensure(std::max<u64>(n_in, 1) * chunk * 32);
+        std::vector<u32> verdict(chunk);
+        std::vector<void*> ptrs(chunk);
+        std::vector<uint8_t> tmp;
+        u64 n_failed = 0;
+        for (u64 c0 = 0; c0 < count; c0 += chunk) {
+            const u32 c = (u32)std::min<u64>(chunk, count - c0);
+            const dim3 waves(blocks_for(c, WX_BLOCK));
+            if (h.n_args) dev_h2d(ctx->xargs.p, args + c0 * h.n_args * 32, (size_t)c * h.n_args * 32, s);
+            ZK_LAUNCH((k_exec_program<Fr>), waves, dim3(WX_BLOCK), 0, s, ptr<u32>(plan->code), ptr<u32>(plan->pool), ptr<uint8_t>(ctx->xargs), (u32)h.n_args, c, chunk,
+                      ptr<Fr>(ctx->xstore), ptr<u32>(ctx->xverdict));
+            dev_d2h(verdict.data(), ctx->xverdict.p, (size_t)c * 4, s);
+            stream_sync(s);
+            for (u32 i = 0; i < c; ++i) {
+                const bool ok = verdict[i] == WX_RAN_THROUGH;
+                n_failed += !ok;
+                status[c0 + i] = ok ? ZKHIP_OK : ZKHIP_ERR_UNSATISFIED;
+                const u64 st = ok ? ~(u64)0 : verdict[i];
+                if (first_statement) first_statement[c0 + i] = st;
+                if (first_row) first_row[c0 + i] = ok || st >= h.row_of.size() || h.row_of[st] == XPLAN_NO_ROW ? ~(u64)0 : h.row_of[st];
+                ptrs[i] = nullptr;
+                if (made && ok) {
+                    std::unique_ptr<zkhip_assignment> a(new zkhip_assignment());
+                    a->curve = h.curve; a->ctx = ctx; a->m = m;
+                    a->scalars.ensure((m + 2) * 32);
+                    ptrs[i] = a->scalars.p;
+                    (*made)[c0 + i] = std::move(a);
+                }
+            }
+            if (made) {
+                dev_h2d(ctx->xptrs.p, ptrs.data(), (size_t)c * sizeof(void*), s);
+                ZK_LAUNCH((k_exec_gather<Fr>), dim3((unsigned)(m + 2), waves.x), dim3(WX_BLOCK), 0, s, ptr<Fr>(ctx->xstore), chunk, c, (const u32*)nullptr, m,
+                          ptr<u32>(ctx->xverdict), (Fr* const*)ctx->xptrs.p, (Fr*)nullptr, (u64)0, 1, 2u);
+            }
+            if (witness_out) {
+                ZK_LAUNCH((k_exec_witness_file<Fr>), dim3((unsigned)entries, waves.x), dim3(WX_BLOCK), 0, s, ptr<Fr>(ctx->xstore), chunk, c,
+                          (const long long*)plan->file_ids.p, ptr<u32>(plan->file_slots), entries, ptr<u32>(ctx->xverdict), ptr<uint8_t>(ctx->xfile), file_bytes);
+                if (witness_cap_each == file_bytes) {
+                    dev_d2h(witness_out + c0 * file_bytes, ctx->xfile.p, (size_t)c * file_bytes, s);
+                } else {
+                    tmp.resize((size_t)c * file_bytes);
+                    dev_d2h(tmp.data(), ctx->xfile.p, tmp.size(), s);
+                    stream_sync(s);
+                    for (u32 i = 0; i < c; ++i) memcpy(witness_out + (c0 + i) * witness_cap_each, tmp.data() + (size_t)i * file_bytes, file_bytes);
+                }
+            }
+            if (inputs_out && n_in) {
+                ZK_LAUNCH((k_exec_gather<Fr>), dim3((unsigned)n_in, waves.x), dim3(WX_BLOCK), 0, s, ptr<Fr>(ctx->xstore), chunk, c, ptr<u32>(plan->input_cols), n_in,
+                          ptr<u32>(ctx->xverdict), (Fr* const*)nullptr, ptr<Fr>(ctx->xinputs), n_in, 0, 0u);
+                if (inputs_cap_each == n_in) {
+                    dev_d2h(inputs_out + c0 * n_in * 32, ctx->xinputs.p, (size_t)c * n_in * 32, s);
+                } else {
+                    tmp.resize((size_t)c * n_in * 32);
+                    dev_d2h(tmp.data(), ctx->xinputs.p, tmp.size(), s);
+                    stream_sync(s);
+                    for (u32 i = 0; i < c; ++i) memcpy(inputs_out + (c0 + i) * inputs_cap_each * 32, tmp.data() + (size_t)i * n_in * 32, n_in * 32);
+                }
+            }
+            stream_sync(s);      // (the next chunk writes the same store; the assignments are complete when the call returns)
+        }
+        return n_failed;
+    }
+
     // generic MSM primitive (bases in ark encoding)
     template <class F, int NC>
     static void msm_api(zkhip_ctx* ctx, u64 n, const uint8_t* bases, const uint8_t* scalars, uint8_t* out) {
@@ -2456,6 +2568,8 @@ struct CurveOps {
     void (*assignment_upload)(zkhip_ctx*, zkhip_assignment*, const uint8_t*);
     void (*assignment_upload_packed)(zkhip_ctx*, zkhip_assignment*, const uint8_t*, size_t, u64, u64, u64);
     void (*assignment_upload_witness)(zkhip_ctx*, zkhip_assignment*, const WitnessZ&, uint8_t* head);
+    u64 (*compute_witness)(zkhip_ctx*, const zkhip_xplan*, u32, const uint8_t*, std::vector<std::unique_ptr<zkhip_assignment>>*, uint8_t*, u64, uint8_t*, u64,
+                           int32_t*, u64*, u64*);
     void (*r1cs_check)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, const void*, u64 out[2]);
     void (*ntt)(zkhip_ctx*, u32, int, uint8_t*);
     void (*witness_map)(zkhip_ctx*, const zkhip_r1cs*, const uint8_t*, uint8_t*);
@@ -2548,6 +2662,7 @@ static CurveOps make_curve_ops() {
     o.assignment_upload = &Prover<C>::assignment_upload;
     o.assignment_upload_packed = &Prover<C>::assignment_upload_packed;
     o.assignment_upload_witness = &Prover<C>::assignment_upload_witness;
+    o.compute_witness = &Prover<C>::compute_witness;
     o.r1cs_check = &Prover<C>::r1cs_check;
     o.ntt = &Transforms<C>::ntt_api;
     o.witness_map = &Prover<C>::witness_map_api;

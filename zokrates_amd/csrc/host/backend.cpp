@@ -448,6 +448,61 @@ Proof Hip::prove(Scheme scheme, const System& system, const uint8_t* witness, si
     return proof_from_raw(scheme, curve, raw, w.inputs.data(), w.n_inputs);
 }
 
+// ------------------------------------------------------------------ witnesses computed on the device
+ExecPlan::~ExecPlan() { if (plan_) zkhip_xplan_free(plan_); }
+ExecPlan& ExecPlan::operator=(ExecPlan&& o) noexcept {
+    if (this != &o) {
+        if (plan_) zkhip_xplan_free(plan_);
+        plan_ = o.plan_; system_ = o.system_; memcpy(dims_, o.dims_, sizeof dims_);
+        o.plan_ = nullptr;
+    }
+    return *this;
+}
+ExecPlan Hip::load_exec_plan(const System& system, const uint8_t* program_bytes, size_t program_len) {
+    ExecPlan p;
+    check(zkhip_xplan_create(ctx_, system.program().get(), system.get(), program_bytes, program_len, &p.plan_));
+    p.system_ = &system;
+    check(zkhip_xplan_dims(p.plan_, p.dims_));
+    return p;
+}
+std::vector<ComputedWitness> Hip::compute_witness(const ExecPlan& plan, const uint8_t* args, uint32_t count, bool want_files) {
+    std::vector<ComputedWitness> out(count);
+    if (!count) return out;
+    const uint64_t fb = plan.witness_bytes(), ni = plan.system().program().public_inputs();
+    std::vector<zkhip_assignment*> handles(count, nullptr);
+    std::vector<uint8_t> files(want_files ? (size_t)count * fb : 0), inputs((size_t)count * ni * 32 + 1);
+    std::vector<int32_t> status(count);
+    std::vector<uint64_t> st(count), row(count);
+    const int32_t rc = zkhip_compute_witness(ctx_, plan.get(), count, args, handles.data(), want_files ? files.data() : nullptr, fb, inputs.data(), ni, status.data(),
+                                             st.data(), row.data());
+    for (uint32_t i = 0; i < count; ++i) out[i].z = handles[i];      // (owned from here on, whatever the return code)
+    if (rc != ZKHIP_ERR_UNSATISFIED) check(rc);
+    for (uint32_t i = 0; i < count; ++i) {
+        out[i].satisfied = status[i] == ZKHIP_OK;
+        out[i].first_statement = st[i];
+        out[i].first_row = row[i];
+        if (!out[i].satisfied) continue;
+        if (want_files) out[i].file.assign(files.begin() + (size_t)i * fb, files.begin() + (size_t)(i + 1) * fb);
+        out[i].inputs.assign(inputs.begin() + (size_t)i * ni * 32, inputs.begin() + (size_t)(i + 1) * ni * 32);
+    }
+    return out;
+}
+Proof Hip::prove(Scheme scheme, const System& system, const ComputedWitness& witness, const Key& key, StdRng& rng, Timings* tm) {
+    if (!witness.satisfied || !witness.z) throw Error(ZKHIP_ERR_UNSATISFIED, "this instance did not satisfy its program: there is no assignment to prove from");
+    const int32_t curve = system.program().curve();
+    const size_t fq = curve == ZKHIP_CURVE_BN128 ? 32 : 48;
+    last_packed_ = false;
+    last_on_device_ = true;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> raw(8 * fq + 3);
+    uint8_t rnd[96];
+    draw_rnd(scheme, curve, rng, rnd);
+    check(scheme == Scheme::GM17 ? zkhip_prove_gm17_resident(ctx_, key.get(), system.get(), witness.z, rnd, raw.data(), nullptr)
+                                 : zkhip_prove_g16_resident(ctx_, key.get(), system.get(), witness.z, rnd, rnd + 32, raw.data(), nullptr));
+    if (tm) { tm->witness_to_assignment = 0; tm->r1cs_upload = 0; tm->prove = ms_since(t0); }
+    return proof_from_raw(scheme, curve, raw, witness.inputs.data(), witness.inputs.size() / 32);
+}
+
 // ------------------------------------------------------------------ the proof queue (zkhip.h "proof queue")
 Queue Hip::open_queue(Scheme scheme, const System& system, const Key& key) {
     Queue q;

@@ -2,6 +2,8 @@
 //
 //   zkhip-cli generate-proof -i out -w witness -p proving.key -j proof.json [-s g16|gm17] [--entropy TEXT]
 //                            [--key-cache DIR] [--device N] [--timings] [--verify [--device-verify]] [--check] [--compact-witness] [--device-witness]
+//   zkhip-cli generate-proof -i out --arguments v1 v2 ... -p proving.key -j proof.json      (the witness computed on the device)
+//   zkhip-cli compute-witness -i out -a v1 v2 ... -o witness [--verbose] [--device N]
 //
 // Mirrors /root/reference/zokrates_cli/src/ops/generate_proof.rs:95-202: the compiled program (`out`), the witness and the
 // proving key are read from files, the proof is written as JSON, one proof per process; `--entropy` seeds the RNG as
@@ -71,12 +73,111 @@ std::pair<int, int> cpu_and_node() {
 int usage() {
     fprintf(stderr, "usage: zkhip-cli generate-proof -i <out> -w <witness> -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] "
                     "[--key-cache DIR] [--device N] [--timings] [--verify [--device-verify]] [--check] [--compact-witness] [--device-witness] [--full-tables]\n"
+                    "       zkhip-cli generate-proof -i <out> --arguments v1 v2 ... -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
+                    "       zkhip-cli compute-witness -i <out> [-a v1 v2 ...] [-o <witness>] [--verbose] [--device N]\n"
                     "       zkhip-cli setup -i <out> -p <proving.key> -v <verification.key> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
                     "       zkhip-cli verify [-v <verification.key>] [-j <proof.json>] [--device] [--timings [--repeat N]]\n"
                     "       zkhip-cli print-proof [-j <proof.json>] [-f remix|json]\n");
     return 2;
 }
 }  // namespace
+
+namespace {
+// a decimal field element as 32 little-endian bytes, as the reference's `-a` takes them (T::try_from_dec_str,
+// zokrates_cli/src/ops/compute_witness.rs:132-139); whether it is below r is the library's to say
+std::array<uint8_t, 32> from_decimal(const std::string& s) {
+    std::array<uint8_t, 32> v{};
+    if (s.empty()) throw Error(ZKHIP_ERR_PARSE, "Could not parse argument: " + s);
+    for (char ch : s) {
+        if (ch < '0' || ch > '9') throw Error(ZKHIP_ERR_PARSE, "Could not parse argument: " + s);
+        unsigned carry = (unsigned)(ch - '0');
+        for (int i = 0; i < 32; ++i) { const unsigned t = v[i] * 10u + carry; v[i] = (uint8_t)t; carry = t >> 8; }
+        if (carry) throw Error(ZKHIP_ERR_PARSE, "Could not parse argument: " + s);
+    }
+    return v;
+}
+std::string to_decimal(const uint8_t* le) {
+    uint8_t v[32];
+    memcpy(v, le, 32);
+    std::string out;
+    for (;;) {
+        unsigned rem = 0;
+        bool any = false;
+        for (int i = 31; i >= 0; --i) { const unsigned t = rem * 256u + v[i]; v[i] = (uint8_t)(t / 10u); rem = t % 10u; any = any || v[i]; }
+        out.push_back((char)('0' + rem));
+        if (!any) break;
+    }
+    return std::string(out.rbegin(), out.rend());
+}
+// the values after -a / --arguments, up to the next option
+std::vector<uint8_t> take_arguments(int argc, char** argv, int& i) {
+    std::vector<uint8_t> out;
+    while (i + 1 < argc && argv[i + 1][0] != '-') {
+        const std::array<uint8_t, 32> v = from_decimal(argv[++i]);
+        out.insert(out.end(), v.begin(), v.end());
+    }
+    return out;
+}
+// one instance through the device: the plan of the program, the arguments in, the witness out; an Error names what failed
+ComputedWitness compute_one(Hip& hip, const System& system, const Mapped& prog_bytes, const std::vector<uint8_t>& args) {
+    const ExecPlan plan = hip.load_exec_plan(system, prog_bytes.data, prog_bytes.size);
+    if (args.size() != plan.arguments() * 32)
+        throw Error(ZKHIP_ERR_BAD_ARG, "Execution failed: Program takes " + std::to_string(plan.arguments()) + " inputs but was passed " + std::to_string(args.size() / 32) + " values");
+    std::vector<ComputedWitness> w = hip.compute_witness(plan, args.data(), 1);
+    if (!w[0].satisfied)
+        throw Error(ZKHIP_ERR_UNSATISFIED, "Execution failed: statement " + std::to_string(w[0].first_statement) + " of the program (constraint " + std::to_string(w[0].first_row) +
+                                               ") is not satisfied; its right-hand side is over " + system.program().row_variables(2, w[0].first_row));
+    return std::move(w[0]);
+}
+}  // namespace
+
+// zkhip-cli compute-witness -i out -a v1 v2 ... -o witness [--verbose] [--device N]
+// (/root/reference/zokrates_cli/src/ops/compute_witness.rs:98-233 with raw arguments: "Computing witness...", with --verbose the return
+// values as the JSON of a tuple of field elements, the `witness` file, "Witness file written to '..'".  --abi, --stdin, --json and
+// --circom-witness are not built.)  The witness is computed on the device (Hip::compute_witness): one instance, one lane.
+int cmd_compute_witness(int argc, char** argv) {
+    std::string input = "out", output = "witness";
+    std::vector<uint8_t> args;
+    bool verbose = false;
+    int device = 0;
+    try {
+        for (int i = 2; i < argc; ++i) {
+            const std::string a = argv[i];
+            auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(2); } return argv[++i]; };
+            if (a == "-i" || a == "--input") input = val();
+            else if (a == "-o" || a == "--output") output = val();
+            else if (a == "-a" || a == "--arguments") args = take_arguments(argc, argv, i);
+            else if (a == "--verbose") verbose = true;
+            else if (a == "--device") device = atoi(val().c_str());
+            else return usage();
+        }
+        printf("Computing witness...\n");
+        const Mapped prog_bytes(input);
+        const Program program(prog_bytes.data, prog_bytes.size);
+        Hip hip(device);
+        const System system = hip.load_system(program);
+        const ComputedWitness w = compute_one(hip, system, prog_bytes, args);
+        if (verbose) {
+            // witness.return_values(): ~out_0 .. ~out_{R-1}, the tail of the public inputs; R is the header's return count
+            uint32_t returns = 0;
+            memcpy(&returns, prog_bytes.data + 16, 4);
+            const size_t n = w.inputs.size() / 32;
+            std::string list;
+            for (size_t k = n - std::min<size_t>(returns, n); k < n; ++k) list += (list.empty() ? "\"" : ",\"") + to_decimal(&w.inputs[32 * k]) + "\"";
+            printf("\nWitness: \n[%s]\n\n", list.c_str());
+        }
+        std::ofstream o(output, std::ios::binary);
+        if (!o) throw Error(ZKHIP_ERR_BAD_ARG, "Could not create " + output);
+        o.write((const char*)w.file.data(), (std::streamsize)w.file.size());
+        o.close();
+        if (!o) throw Error(ZKHIP_ERR_BAD_ARG, "Could not save witness");
+        printf("Witness file written to '%s'\n", output.c_str());
+        return 0;
+    } catch (const std::exception& e) {
+        fprintf(stderr, "zkhip-cli: %s\n", e.what());
+        return 1;
+    }
+}
 
 // zkhip-cli setup -i out -p proving.key -v verification.key [-s g16|gm17] [--entropy TEXT] [--device N]
 // (/root/reference/zokrates_cli/src/ops/setup.rs: program in, proving.key + verification.key out)
@@ -219,16 +320,23 @@ int cmd_pairing_check(int argc, char** argv) {
 int main(int argc, char** argv) {
     if (argc >= 2 && strcmp(argv[1], "setup") == 0) return cmd_setup(argc, argv);
     if (argc >= 2 && strcmp(argv[1], "verify") == 0) return cmd_verify(argc, argv);
+    if (argc >= 2 && strcmp(argv[1], "compute-witness") == 0) return cmd_compute_witness(argc, argv);
     if (argc >= 2 && strcmp(argv[1], "print-proof") == 0) return cmd_print_proof(argc, argv);
     if (argc >= 2 && strcmp(argv[1], "pairing-check") == 0) return cmd_pairing_check(argc, argv);
     if (argc < 2 || strcmp(argv[1], "generate-proof") != 0) return usage();
     std::string input = "out", witness_path = "witness", pk_path = "proving.key", proof_path = "proof.json", scheme_s = "g16", entropy, cache_dir;
     bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false, device_witness = false, device_verify = false;
     int device = 0;
+    bool from_arguments = false;      // --arguments in place of -w: the witness computed on the device, the proof from its resident assignment
+    std::vector<uint8_t> arguments;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(2); } return argv[++i]; };
         if (a == "-i" || a == "--input") input = val();
+        else if (a == "--arguments") {
+            try { arguments = take_arguments(argc, argv, i); } catch (const Error& e) { fprintf(stderr, "zkhip-cli: %s\n", e.what()); return 1; }
+            from_arguments = true;
+        }
         else if (a == "--verify") self_check = true;
         else if (a == "--device-verify") device_verify = true;   // with --verify: that check on the GPU (Hip::verify_batch) instead of the host CPU
         else if (a == "--check") check_first = true;                 // the witness against the constraints, on the device, before proving
@@ -259,7 +367,7 @@ int main(int argc, char** argv) {
             try {
                 auto t0 = std::chrono::steady_clock::now();
                 const Mapped prog_bytes(input);
-                witness = Mapped(witness_path);
+                if (!from_arguments) witness = Mapped(witness_path);
                 ms_read = ms_since(t0);
                 t0 = std::chrono::steady_clock::now();
                 program.reset(new Program(prog_bytes.data, prog_bytes.size));
@@ -355,7 +463,7 @@ int main(int argc, char** argv) {
         // fails is refused with the number of its first failing constraint, the statement number of the `out` file
         System system;
         double ms_check = 0;
-        if (check_first) {
+        if (check_first && !from_arguments) {      // (a witness computed on the device has passed the program's own checks there)
             t0 = std::chrono::steady_clock::now();
             system = hip.load_system(*program);
             tm.r1cs_upload = ms_since(t0);
@@ -369,9 +477,25 @@ int main(int argc, char** argv) {
             printf("checked: the witness satisfies all %llu constraints (%.3f ms)\n", (unsigned long long)program->constraints(), ms_check);
         }
         const double upload_ms = tm.r1cs_upload;
-        const Proof proof = check_first ? hip.prove(scheme, system, witness.data, witness.size, key, rng, &tm)
-                                        : hip.prove(scheme, *program, witness.data, witness.size, key, rng, &tm);
-        if (check_first) tm.r1cs_upload = upload_ms;
+        Proof proof;
+        if (from_arguments) {
+            // the statements run on the device (one instance: one lane), the proof from the assignment they leave there
+            t0 = std::chrono::steady_clock::now();
+            system = hip.load_system(*program);
+            const double ms_system = ms_since(t0);
+            t0 = std::chrono::steady_clock::now();
+            const Mapped prog_bytes(input);
+            const ComputedWitness w = compute_one(hip, system, prog_bytes, arguments);
+            const double ms_exec = ms_since(t0);
+            proof = hip.prove(scheme, system, w, key, rng, &tm);
+            tm.r1cs_upload = ms_system;
+            tm.witness_to_assignment = ms_exec;
+            printf("witness computed on the device from %zu arguments (%.3f ms)\n", arguments.size() / 32, ms_exec);
+        } else {
+            proof = check_first ? hip.prove(scheme, system, witness.data, witness.size, key, rng, &tm)
+                                : hip.prove(scheme, *program, witness.data, witness.size, key, rng, &tm);
+            if (check_first) tm.r1cs_upload = upload_ms;
+        }
         t0 = std::chrono::steady_clock::now();
         {
             std::ofstream o(proof_path);

@@ -405,6 +405,7 @@ void zkhip_ctx_free(zkhip_ctx* ctx) {
     if (ctx->out_made) stream_destroy(ctx->out_stream);
     if (ctx->ntt_made) stream_destroy(ctx->ntt_stream);
     if (ctx->verify_made) stream_destroy(ctx->verify_stream);
+    if (ctx->exec_made) stream_destroy(ctx->exec_stream);
     stream_destroy(ctx->stream);
     delete ctx;
 }
@@ -464,6 +465,7 @@ int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value) {
                 in(1, 8);
                 require((value & (value - 1)) == 0, ZKHIP_ERR_BAD_ARG, "NTT_COLS must be 1, 2, 4 or 8 (the cols pass covers N2 / cols workgroups exactly)");
                 dev_sync_all(); ctx->ntt_cols = value; ctx->plans.clear(); break;
+            case ZKHIP_TUNE_EXEC_CHUNK: in(0, 65535 * (int)WX_BLOCK); ctx->exec_chunk = value; break;      // (the gathers' grids hold the waves of a chunk along y)
             default: throw ApiError{ZKHIP_ERR_BAD_ARG, "unknown tunable"};
         }
     });
@@ -725,6 +727,86 @@ int32_t zkhip_assignment_upload_witness(zkhip_ctx* ctx, const zkhip_wplan* plan,
         if (n_inputs) *n_inputs = t.input_cols.size();
         *out = a.release();
     });
+}
+
+// ---- witnesses computed on the device: the plan (the program's statements compiled for k_exec_program, resident), and the call
+static bool scalar_canonical(int curve, const uint8_t* b) {
+    if (curve == ZKHIP_CURVE_BN128) return canon_lt_mod(fe_from_bytes_canon<Fe<Bn254Fr>>(b));
+    if (curve == ZKHIP_CURVE_BLS12_381) return canon_lt_mod(fe_from_bytes_canon<Fe<Bls381Fr>>(b));
+    return canon_lt_mod(fe_from_bytes_canon<Fe<Bls377Fr>>(b));
+}
+int32_t zkhip_xplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r1cs* r1cs, const uint8_t* out_bytes, size_t len, zkhip_xplan** out) {
+    if (!ctx) return ZKHIP_ERR_BAD_ARG;
+    return guarded(ctx, [&] {      // (the gate: it enqueues the copies of its tables, as zkhip_wplan_create does)
+        require(prog && r1cs && out_bytes && out, ZKHIP_ERR_BAD_ARG, "null argument");
+        *out = nullptr;
+        require(r1cs->ctx == ctx, ZKHIP_ERR_BAD_ARG, "constraint system belongs to another context");
+        std::shared_ptr<XPlanHost> host(new XPlanHost());
+        try {
+            xplan_build(*prog, r1cs->curve, r1cs->l, r1cs->w, r1cs->n, out_bytes, len, *host);
+        } catch (const IngestError& e) {
+            throw ApiError{e.code, e.msg};
+        }
+        std::unique_ptr<zkhip_xplan> plan(new zkhip_xplan());
+        plan->ctx = ctx;
+        auto up = [&](DBuf& d, const void* src, size_t bytes) {
+            d.ensure(std::max<size_t>(bytes, 16));
+            if (bytes) dev_h2d(d.p, src, bytes, ctx->stream);
+        };
+        up(plan->code, host->code.data(), host->code.size() * 4);
+        up(plan->pool, host->pool.data(), host->pool.size() * 4);
+        up(plan->file_ids, host->file_ids.data(), host->file_ids.size() * 8);
+        up(plan->file_slots, host->file_slots.data(), host->file_slots.size() * 4);
+        up(plan->input_cols, host->input_cols.data(), host->input_cols.size() * 4);
+        stream_sync(ctx->stream);
+        plan->host = host;
+        *out = plan.release();
+    });
+}
+void zkhip_xplan_free(zkhip_xplan* plan) { delete plan; }
+int32_t zkhip_xplan_dims(const zkhip_xplan* plan, uint64_t out[8]) {
+    if (!plan || !out) return ZKHIP_ERR_BAD_ARG;
+    plan->host->dims(out);
+    return ZKHIP_OK;
+}
+// (on its own stream and in its own buffers, as the pairing checks: allowed while a proof queue is open, refused while a split proof
+// is pending — guarded_verify is that gate)
+int32_t zkhip_compute_witness(zkhip_ctx* ctx, const zkhip_xplan* plan, uint32_t count, const uint8_t* args, zkhip_assignment** assignments_out,
+                              uint8_t* witness_out, uint64_t witness_cap_each, uint8_t* inputs_out, uint64_t inputs_cap_each, int32_t* status,
+                              uint64_t* first_statement, uint64_t* first_row) {
+    bool unsatisfied = false;
+    const int32_t rc = guarded_verify(ctx, [&] {
+        require(plan != nullptr, ZKHIP_ERR_BAD_ARG, "null argument");
+        require(plan->ctx == ctx, ZKHIP_ERR_BAD_ARG, "the execution plan belongs to another context");
+        if (count == 0) return;
+        const XPlanHost& h = *plan->host;
+        require(status && (args || h.n_args == 0), ZKHIP_ERR_BAD_ARG, "null argument");
+        require(!witness_out || witness_cap_each >= h.file_bytes(), ZKHIP_ERR_BAD_ARG,
+                ("witness buffer too small: a file of this program has " + std::to_string(h.file_bytes()) + " bytes (8 + 40 x zkhip_xplan_dims [5])").c_str());
+        require(!inputs_out || inputs_cap_each >= h.input_cols.size(), ZKHIP_ERR_BAD_ARG, "inputs buffer too small");
+        // every argument below r, before anything is enqueued
+        const CurveOps* ops = ops_for(h.curve);
+        for (uint64_t i = 0; i < count; ++i)
+            for (uint64_t k = 0; k < h.n_args; ++k)
+                if (!scalar_canonical(h.curve, args + (i * h.n_args + k) * 32))
+                    throw ApiError{ZKHIP_ERR_PARSE, "instance " + std::to_string(i) + ", argument " + std::to_string(k) + ": not a canonical field element (at or above r)"};
+        std::vector<std::unique_ptr<zkhip_assignment>> made(assignments_out ? count : 0);
+        if (assignments_out) for (uint32_t i = 0; i < count; ++i) assignments_out[i] = nullptr;
+        std::vector<uint64_t> own_st(first_statement ? 0 : count), own_row(first_row ? 0 : count);      // (the message names both, asked for or not)
+        if (!first_statement) first_statement = own_st.data();
+        if (!first_row) first_row = own_row.data();
+        const uint64_t bad = ops->compute_witness(ctx, plan, count, args, assignments_out ? &made : nullptr, witness_out, witness_cap_each, inputs_out, inputs_cap_each,
+                                                  status, first_statement, first_row);
+        if (assignments_out) for (uint32_t i = 0; i < count; ++i) assignments_out[i] = made[i].release();
+        if (bad) {
+            uint32_t i = 0;
+            while (status[i] == ZKHIP_OK) ++i;
+            ctx->err = "instance " + std::to_string(i) + " does not satisfy the program: statement " + std::to_string(first_statement[i]) + ", constraint (R1CS row) " +
+                       std::to_string(first_row[i]) + "; " + std::to_string(bad) + " of " + std::to_string(count) + " instances failed";
+            unsatisfied = true;
+        }
+    });
+    return rc == ZKHIP_OK && unsatisfied ? ZKHIP_ERR_UNSATISFIED : rc;
 }
 
 int32_t zkhip_prove_g16_resident(zkhip_ctx* ctx, const zkhip_pk* pk, const zkhip_r1cs* r1cs, zkhip_assignment* z, const uint8_t* r,

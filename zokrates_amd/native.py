@@ -81,6 +81,7 @@ class Library:
         "zkhip_wplan_create", "zkhip_wplan_free", "zkhip_assignment_upload_witness", "zkhip_queue_submit_witness", "zkhip_queue_collect_inputs",
         "zkhip_pairing_products", "zkhip_tower_op", "zkhip_vk_load_g16", "zkhip_vk_load_gm17", "zkhip_vk_free", "zkhip_vk_dims",
         "zkhip_verify_g16_batch", "zkhip_verify_gm17_batch",
+        "zkhip_xplan_create", "zkhip_xplan_free", "zkhip_xplan_dims", "zkhip_compute_witness",
     ]
 
     def __init__(self, path=None):
@@ -203,6 +204,10 @@ class Library:
         L.zkhip_assignment_upload_witness.restype = i32; L.zkhip_assignment_upload_witness.argtypes = [vp, vp, vp, sz, vp, u64, vp, pp]
         L.zkhip_queue_submit_witness.restype = i32; L.zkhip_queue_submit_witness.argtypes = [vp, vp, vp, sz, vp, vp]
         L.zkhip_queue_collect_inputs.restype = i32; L.zkhip_queue_collect_inputs.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+        L.zkhip_xplan_create.restype = i32; L.zkhip_xplan_create.argtypes = [vp, vp, vp, vp, sz, pp]
+        L.zkhip_xplan_free.restype = None; L.zkhip_xplan_free.argtypes = [vp]
+        L.zkhip_xplan_dims.restype = i32; L.zkhip_xplan_dims.argtypes = [vp, vp]
+        L.zkhip_compute_witness.restype = i32; L.zkhip_compute_witness.argtypes = [vp, vp, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp]
         self.L = L
 
     def init(self, hw_queues):
@@ -273,7 +278,7 @@ class Context:
         self._check(self.lib.L.zkhip_describe(self.h, buf, 256))
         return buf.value.decode()
 
-    TUNABLES = {"msm_c": 1, "msm_waves": 2, "msm_lanes": 3, "msm_min_slice": 4, "fold_scan": 5, "serial": 6, "ntt_single_max_log": 7, "ntt_cols": 8, "slots": 9, "z_gate": 10, "fuse_z": 11, "msm_fused_waves": 12, "stream_jitter": 13, "ntt_max_sublog": 16, "msm_sets": 17, "skip_inf": 18, "b_sort": 19, "heavy_runs": 20, "fold_hg": 25, "ntt_fuse_first": 26, "pipe_plan": 28}
+    TUNABLES = {"msm_c": 1, "msm_waves": 2, "msm_lanes": 3, "msm_min_slice": 4, "fold_scan": 5, "serial": 6, "ntt_single_max_log": 7, "ntt_cols": 8, "slots": 9, "z_gate": 10, "fuse_z": 11, "msm_fused_waves": 12, "stream_jitter": 13, "ntt_max_sublog": 16, "msm_sets": 17, "skip_inf": 18, "b_sort": 19, "heavy_runs": 20, "fold_hg": 25, "ntt_fuse_first": 26, "pipe_plan": 28, "exec_chunk": 29}
 
     def clock_probe(self, duration_us=2000):
         """`zkhip_ctx_clock_probe`: the shader clock (GHz) the device runs at over the next `duration_us` microseconds — one wavefront
@@ -300,6 +305,50 @@ class Context:
         self._check(self.lib.L.zkhip_assignment_upload_witness(self.h, plan.h, _ptr(wit), wit.size, _ptr(inputs) if want_inputs else None, cap,
                                                                C.byref(n_in), C.byref(a.h)))
         return (a, inputs[:32 * n_in.value].copy()) if want_inputs else a
+
+    def compute_witness(self, plan, args, want_files=False, want_inputs=False, want_assignments=True):
+        """`zkhip_compute_witness`: the program of `plan` (`Program.exec_plan`) run on the device for a batch.  `args`: count x
+        arguments canonical integers (a list of lists of ints, or uint8[count * arguments * 32]).  Returns a `WitnessBatch`: per
+        instance `status` (0 or -5), `first_statement`, `first_row` (None where it ran through), the resident `assignments` (None for a
+        failed instance), and on request `files` (the reference's `witness` bytes) and `inputs` (public_inputs_values, bytes).  `code`
+        is the call's return value (0, or -5 if any instance failed: the others are delivered) and `message` its text."""
+        n_args = plan.n_args
+        if isinstance(args, np.ndarray) or isinstance(args, (bytes, bytearray)):
+            a = _u8(args)
+            count = a.size // (32 * n_args) if n_args else 0
+        else:
+            count = len(args)
+            a = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for row in args for v in row), dtype=np.uint8)
+        if n_args and a.size != count * n_args * 32:
+            raise ValueError(f"arguments have {a.size} bytes, expected {count} x {n_args} x 32")
+        handles = (C.c_void_p * max(count, 1))()
+        fb, ni = plan.file_bytes, plan.n_inputs
+        files = np.zeros(max(count * fb, 1), dtype=np.uint8)
+        inputs = np.zeros(max(count * ni * 32, 1), dtype=np.uint8)
+        status = np.zeros(max(count, 1), dtype=np.int32)
+        st, row = np.zeros(max(count, 1), dtype=np.uint64), np.zeros(max(count, 1), dtype=np.uint64)
+        rc = self.lib.L.zkhip_compute_witness(self.h, plan.h, count, _ptr(a) if a.size else None, handles if want_assignments else None,
+                                              _ptr(files) if want_files else None, fb, _ptr(inputs) if want_inputs else None, ni, _ptr(status), _ptr(st), _ptr(row))
+        if rc not in (0, -5):
+            self._check(rc)
+        out = WitnessBatch()
+        out.code = rc
+        out.message = self.lib.L.zkhip_last_error(self.h).decode() if rc else ""
+        out.status = [int(x) for x in status[:count]]
+        none = (1 << 64) - 1
+        out.first_statement = [None if int(x) == none else int(x) for x in st[:count]]
+        out.first_row = [None if int(x) == none else int(x) for x in row[:count]]
+        out.assignments = []
+        for i in range(count):
+            if want_assignments and handles[i]:
+                z = Assignment.__new__(Assignment)
+                z.ctx, z.h = self, C.c_void_p(handles[i])
+                out.assignments.append(z)
+            else:
+                out.assignments.append(None)
+        out.files = [files[i * fb:(i + 1) * fb].tobytes() for i in range(count)] if want_files else None
+        out.inputs = [inputs[i * ni * 32:(i + 1) * ni * 32].tobytes() for i in range(count)] if want_inputs else None
+        return out
 
     def close(self):
         if self.h:
@@ -1010,6 +1059,12 @@ class Program:
         parameter, an output without a column): such callers keep `assignment`."""
         return WitnessPlan(ctx, self, cs)
 
+    def exec_plan(self, ctx, cs, data):
+        """`zkhip_xplan_create`: this program's statements compiled for the device, for `Context.compute_witness`.  `data`: the same
+        `out` bytes the program was parsed from.  Raises ZkhipError (BAD_ARG) for a program that keeps the host interpreter (a solver
+        the device does not run, a read before definition)."""
+        return ExecPlan(ctx, self, cs, data)
+
     def assignment(self, witness_bytes):
         """(z uint8[m*32] in ark order, inputs uint8[k*32] = public_inputs_values) from a ZoKrates `witness` file."""
         wit = _u8(witness_bytes)
@@ -1039,6 +1094,45 @@ class Program:
     def close(self):
         if self.h:
             self.lib.L.zkhip_prog_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WitnessBatch:
+    """What `Context.compute_witness` returns."""
+
+    def close(self):
+        for z in self.assignments:
+            if z is not None:
+                z.close()
+
+
+class ExecPlan:
+    """`zkhip_xplan`: the statements of one program compiled for the device, on one context (`Program.exec_plan`)."""
+
+    DIMS = ("n_args", "n_statements", "n_defines", "n_checks", "n_directives", "n_entries", "n_extra", "store_bytes")
+
+    def __init__(self, ctx, prog, cs, data):
+        self.ctx = ctx
+        data = _u8(data)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.L.zkhip_xplan_create(ctx.h, prog.h, cs.h, _ptr(data), data.size, C.byref(self.h)))
+        d = np.zeros(8, dtype=np.uint64)
+        ctx.lib.L.zkhip_xplan_dims(self.h, _ptr(d))
+        self.dims = tuple(int(x) for x in d)
+        for k, v in zip(self.DIMS, self.dims):
+            setattr(self, k, v)
+        self.n_inputs = prog.n_public_args + prog.return_count
+        self.file_bytes = 8 + 40 * self.n_entries
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.L.zkhip_xplan_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
