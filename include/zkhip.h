@@ -205,6 +205,12 @@ int32_t zkhip_ctx_clock_probe(zkhip_ctx* ctx, uint32_t duration_us, double* ghz_
                                          device memory that is free (or held by the context's buffers of an earlier call), 32 GiB and 65536 instances at most, at
                                          the bytes a chunk keeps per instance: (zkhip_xplan_dims [7]) of value store, the arguments, and the file and the inputs
                                          where they are asked for.  A test hook as well: it puts the chunk seams wherever a tiny program needs them */
+#define ZKHIP_TUNE_ALLOC_FILL 30       /* TESTS ONLY, process-wide (every context of the process, like _STREAM_JITTER), never read from the environment.  A 32-bit
+                                         word; while it is non-zero every device and pinned-host block the library allocates is filled with it, to its last byte,
+                                         before the allocation returns (one fill and one synchronisation per allocation).  0 (default): off, allocations are
+                                         handed out as the runtime gives them.  Fresh memory that reads as zero looks like points at infinity, zero scalars and
+                                         empty buckets; under a fill a kernel that reads a slot nobody wrote gives other bytes (tests/test_workspace_reuse.py).
+                                         Blocks allocated before the call keep what they hold */
 int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value);
 
 /* ---- proving key ----

@@ -71,6 +71,20 @@ inline void host_parallel_for(uint64_t n, Fn&& fn, unsigned max_threads = 8) {
     th.join();
 }
 
+// TESTS ONLY (ZKHIP_TUNE_ALLOC_FILL, process-wide, 0 = off, never read from the environment): while the word is non-zero, dev_alloc and
+// host_alloc_pinned fill the whole block they hand out with it before they return.  Fresh memory tends to read as zero, and zero is
+// the neutral element of nearly everything here (a point at infinity, the scalar 0, an empty bucket): a kernel that reads a slot
+// nobody wrote then gives the right answer by luck.  Under a fill it does not (tests/test_workspace_reuse.py).
+inline std::atomic<uint32_t>& alloc_fill_word() {
+    static std::atomic<uint32_t> w{0};
+    return w;
+}
+inline void host_fill_words(void* p, size_t bytes, uint32_t w) {
+    uint32_t* q = (uint32_t*)p;
+    for (size_t i = 0; i < bytes / 4; ++i) q[i] = w;
+    for (size_t i = bytes / 4 * 4; i < bytes; ++i) ((unsigned char*)p)[i] = (unsigned char)(w >> (8 * (i & 3)));
+}
+
 #ifndef ZK_EMU
 #define ZK_HIP_CHECK(expr)                                                                        \
     do {                                                                                          \
@@ -112,9 +126,14 @@ inline void* dev_alloc(size_t bytes) {
     std::lock_guard<std::mutex> lock(t.mu);
     const size_t offset = (size_t)(t.counter++ % slots) * step;
     void* base = nullptr;
-    ZK_HIP_CHECK(hipMalloc(&base, (std::max<size_t>(bytes, 1) + offset + page - 1) / page * page));
+    const size_t blk = (std::max<size_t>(bytes, 1) + offset + page - 1) / page * page;
+    ZK_HIP_CHECK(hipMalloc(&base, blk));
     void* p = (char*)base + offset;
     t.base_of[p] = base;
+    if (const uint32_t w = alloc_fill_word().load(std::memory_order_relaxed)) {   // (tests only: the block's pages from p to their end)
+        ZK_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)p, (int)w, (blk - offset) / 4, nullptr));
+        ZK_HIP_CHECK(hipStreamSynchronize(nullptr));
+    }
     return p;
 }
 inline void dev_free(void* p) {
@@ -129,6 +148,7 @@ inline void dev_free(void* p) {
 inline void* host_alloc_pinned(size_t bytes) {
     void* p = nullptr;
     ZK_HIP_CHECK(hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault));
+    if (const uint32_t w = alloc_fill_word().load(std::memory_order_relaxed)) host_fill_words(p, bytes ? bytes : 16, w);
     return p;
 }
 inline void host_free_pinned(void* p) {
@@ -515,7 +535,13 @@ typedef double* Event;
 inline int dev_count() { return 1; }
 inline void dev_set(int) {}
 inline void dev_pci_bus_id(int, char* out, size_t cap) { snprintf(out, cap, "0000:00:00.0"); }   // (the emulator's one "device")
-inline void* dev_alloc(size_t bytes) { return aligned_alloc(256, ((bytes ? bytes : 16) + 255) / 256 * 256); }
+inline void* dev_alloc(size_t bytes) {
+    const size_t blk = ((bytes ? bytes : 16) + 255) / 256 * 256;
+    void* p = aligned_alloc(256, blk);
+    if (const uint32_t w = alloc_fill_word().load(std::memory_order_relaxed))
+        if (p) host_fill_words(p, blk, w);
+    return p;
+}
 inline void dev_free(void* p) { free(p); }
 inline void* host_alloc_pinned(size_t bytes) { return dev_alloc(bytes); }
 inline void host_free_pinned(void* p) { free(p); }

@@ -466,6 +466,7 @@ int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value) {
                 require((value & (value - 1)) == 0, ZKHIP_ERR_BAD_ARG, "NTT_COLS must be 1, 2, 4 or 8 (the cols pass covers N2 / cols workgroups exactly)");
                 dev_sync_all(); ctx->ntt_cols = value; ctx->plans.clear(); break;
             case ZKHIP_TUNE_EXEC_CHUNK: in(0, 65535 * (int)WX_BLOCK); ctx->exec_chunk = value; break;      // (the gathers' grids hold the waves of a chunk along y)
+            case ZKHIP_TUNE_ALLOC_FILL: dev_sync_all(); alloc_fill_word().store((uint32_t)value); break;   // (tests only, process-wide: devrt.h)
             default: throw ApiError{ZKHIP_ERR_BAD_ARG, "unknown tunable"};
         }
     });
