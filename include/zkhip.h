@@ -25,7 +25,7 @@
  *    them the proof is PENDING in its context, and the context accepts zkhip_prove_g16_split_end, zkhip_prove_g16_split_abort and
  *    the calls that neither enqueue device work nor change a handle (zkhip_last_error, zkhip_describe, zkhip_pk_dims,
  *    zkhip_pk_is_bound, zkhip_pk_export_size, zkhip_partial_size, zkhip_combine_*, zkhip_ctx_set_checked(ctx, -1),
- *    zkhip_ctx_unsatisfied, zkhip_setup_*_size, the zkhip_prog_* family).  Every other call on that context or on one of its keys —
+ *    zkhip_ctx_unsatisfied, zkhip_setup_*_size, the zkhip_prog_* family, zkhip_xplan_levels, zkhip_exec_last).  Every other call on that context or on one of its keys —
  *    the prove calls, zkhip_r1cs_check, a second begin, zkhip_pk_bind_r1cs / _shard / zkhip_pk_unbind, zkhip_ctx_tune,
  *    zkhip_ctx_set_checked(ctx, 0 / 1), key loads, imports and exports, setups, uploads (zkhip_assignment_upload, _upload_packed,
  *    _upload_witness), zkhip_wplan_create (it enqueues the copies of its tables) and the primitives (they work in the
@@ -205,6 +205,12 @@ int32_t zkhip_ctx_clock_probe(zkhip_ctx* ctx, uint32_t duration_us, double* ghz_
                                          device memory that is free (or held by the context's buffers of an earlier call), 32 GiB and 65536 instances at most, at
                                          the bytes a chunk keeps per instance: (zkhip_xplan_dims [7]) of value store, the arguments, and the file and the inputs
                                          where they are asked for.  A test hook as well: it puts the chunk seams wherever a tiny program needs them */
+#define ZKHIP_TUNE_EXEC_WIDE 31        /* 0 (default): zkhip_compute_witness runs one work-item per instance, as before.  1: it takes the level-scheduled route —
+                                         one work-item per (instruction of a level, instance): the route for a lone instance or a few.  Read at each call;
+                                         changes no result */
+#define ZKHIP_TUNE_EXEC_WIDE_MIN 32    /* the width (instructions) at and above which a level of the schedule gets a launch of its own on the level-scheduled
+                                         route; narrower neighbours share one launch of one workgroup per instance.  0 = the default (1024: the measured sweep was flat); otherwise
+                                         1 .. 2^20.  A test hook as well, like _EXEC_CHUNK: it puts the segment seams where a tiny program needs them */
 #define ZKHIP_TUNE_ALLOC_FILL 30       /* TESTS ONLY, process-wide (every context of the process, like _STREAM_JITTER), never read from the environment.  A 32-bit
                                          word; while it is non-zero every device and pinned-host block the library allocates is filled with it, to its last byte,
                                          before the allocation returns (one fill and one synchronisation per allocation).  0 (default): off, allocations are
@@ -412,11 +418,32 @@ int32_t zkhip_assignment_upload_witness(zkhip_ctx* ctx, const zkhip_wplan* plan,
  * (ZKHIP_ERR_DEVICE / _NOMEM otherwise: no handle is delivered).
  * Call discipline as zkhip_pairing_products: a stream and buffers of its own, no proof slot touched — allowed while a proof queue is
  * open (a service computes the next batch between submits and hands the handles to zkhip_queue_submit), refused while a split proof
- * is pending.  Nothing consults the environment. */
+ * is pending.  Nothing consults the environment.
+ *
+ * A lone witness across the device (ZKHIP_TUNE_EXEC_WIDE = 1; off by default).  The same call, plan, stream, store, verdicts, gather
+ * and file kernels and the same bytes out; one work-item per (instruction of a level, instance) instead of one per instance.  The plan
+ * knows which slots every instruction reads and writes, so it also holds the program's dependency LEVELS, computed once on the
+ * host when the plan is made: an instruction sits at the lowest level above the last write of every slot it reads and above the last
+ * write and every reader of the slots it writes (a directive's output that overwrites a defined variable, the second binding of a
+ * repeated parameter: strictly after every reader of the old value); the instructions of one level run in no order.  The call cuts the
+ * levels, in ascending order, into launches: a level of ZKHIP_TUNE_EXEC_WIDE_MIN instructions or more is one launch over the whole
+ * device, every maximal run of narrower levels one launch of one workgroup per instance with a workgroup barrier between levels.  The
+ * stream orders the launches; no launch waits on another workgroup of itself.  The verdict of an instance is the minimum over its
+ * failing statements — still "the lowest failing statement".  A program gains what its depth allows: a deep, narrow one stays a chain.
+ * Measured: a lone witness of a synthetic program of 2^20 statements in 5 535 levels takes 1.94 s against 12.2 s
+ * on one lane; up to 1 024 instances the one-lane route did not win back.
+ *   zkhip_xplan_levels: out[0] levels, [1] instructions of the widest level, [2] instructions in all (the arguments' included),
+ *   [3] levels of fewer than 64 instructions.  Read-only, no device work.
+ *   zkhip_exec_last: the last zkhip_compute_witness of the context that reached the device: out[0] 0 none yet, 1 one work-item per
+ *   instance, 2 level-scheduled; [1] chunks; [2] program launches per chunk (1 on route 1; on route 2 the launches the levels were cut
+ *   into — one small launch before them writes ~one and the verdict words and is not counted); [3] the WIDE_MIN in force.  Read-only.
+ * NULL arguments of either are ZKHIP_ERR_BAD_ARG. */
 typedef struct zkhip_xplan zkhip_xplan;
 int32_t zkhip_xplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r1cs* r1cs, const uint8_t* out_bytes, size_t len, zkhip_xplan** out);
 void zkhip_xplan_free(zkhip_xplan* plan);
 int32_t zkhip_xplan_dims(const zkhip_xplan* plan, uint64_t out[8]);
+int32_t zkhip_xplan_levels(const zkhip_xplan* plan, uint64_t out[4]);
+int32_t zkhip_exec_last(const zkhip_ctx* ctx, uint64_t out[4]);
 int32_t zkhip_compute_witness(zkhip_ctx* ctx, const zkhip_xplan* plan, uint32_t count, const uint8_t* args, zkhip_assignment** assignments_out,
                               uint8_t* witness_out, uint64_t witness_cap_each, uint8_t* inputs_out, uint64_t inputs_cap_each, int32_t* status,
                               uint64_t* first_statement, uint64_t* first_row);

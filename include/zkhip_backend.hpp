@@ -365,6 +365,10 @@ class Hip {
     // ComputedWitness proves from its resident assignment: the same Proof as prove() over its `file`.
     ExecPlan load_exec_plan(const System& system, const uint8_t* program_bytes, size_t program_len);
     std::vector<ComputedWitness> compute_witness(const ExecPlan& plan, const uint8_t* args, uint32_t count, bool want_files = true);
+    // A lone witness across the device (ZKHIP_TUNE_EXEC_WIDE): compute_witness runs the program's dependency levels, one work-item per
+    // (instruction of a level, instance), instead of one per instance — the route for one request or a few.  The same results; off
+    // by default.  Throws under a pending split proof, like every tunable.
+    void set_exec_wide(bool on);
     Proof prove(Scheme scheme, const System& system, const ComputedWitness& witness, const Key& key, StdRng& rng, Timings* timings = nullptr);
     // a long-lived prover fed one witness at a time: a proof queue over a resident system and key (see Queue above)
     Queue open_queue(Scheme scheme, const System& system, const Key& key);

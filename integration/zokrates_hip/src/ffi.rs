@@ -72,6 +72,8 @@ extern "C" {
         out: *mut *mut zkhip_xplan) -> i32;
     pub fn zkhip_xplan_free(plan: *mut zkhip_xplan);
     pub fn zkhip_xplan_dims(plan: *const zkhip_xplan, out: *mut u64) -> i32;
+    pub fn zkhip_xplan_levels(plan: *const zkhip_xplan, out: *mut u64) -> i32;
+    pub fn zkhip_exec_last(ctx: *const zkhip_ctx, out: *mut u64) -> i32;
     pub fn zkhip_compute_witness(ctx: *mut zkhip_ctx, plan: *const zkhip_xplan, count: u32, args: *const u8,
         assignments_out: *mut *mut zkhip_assignment, witness_out: *mut u8, witness_cap_each: u64, inputs_out: *mut u8,
         inputs_cap_each: u64, status: *mut i32, first_statement: *mut u64, first_row: *mut u64) -> i32;

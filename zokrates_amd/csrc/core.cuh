@@ -246,6 +246,9 @@ struct zkhip_ctx {
     bool exec_made = false;
     DBuf xstore, xargs, xverdict, xptrs, xfile, xinputs;   // the value store of a chunk, its arguments, verdict words, z pointers, files and inputs; kept between calls
     int exec_chunk = 0;       // instances per chunk of zkhip_compute_witness (ZKHIP_TUNE_EXEC_CHUNK; 0: from the store's bytes per instance, exec_chunk_default)
+    bool exec_wide = false;   // ZKHIP_TUNE_EXEC_WIDE: zkhip_compute_witness takes the level-scheduled route (k_exec_level, k_exec_levels_run)
+    int exec_wide_min = 0;    // ZKHIP_TUNE_EXEC_WIDE_MIN: the width at which a level gets a launch of its own (0: EXEC_WIDE_MIN_DEFAULT)
+    u64 exec_last[4] = {0, 0, 0, 0};   // the last zkhip_compute_witness, as zkhip_exec_last reports it
     DBuf zpack;               // the packed bytes of the compact assignment being widened (zkhip_assignment_upload_packed, zkhip_queue_submit_packed); kept between calls
     std::vector<std::unique_ptr<NttPlanBase>> plans;
     // kernels whose dynamic-LDS limit has been raised for this context's device (the attribute is per device: a flag per
@@ -590,7 +593,14 @@ struct zkhip_xplan {
     zkhip_ctx* ctx = nullptr;
     std::shared_ptr<const XPlanHost> host;
     DBuf code, pool, file_ids, file_slots, input_cols;
+    DBuf sched, level_start;      // the level schedule (xplan.h: xplan_schedule), for the level-scheduled route
 };
+// The width at and above which a level of the schedule is a launch of k_exec_level of its own; narrower levels share a launch of
+// k_exec_levels_run with their neighbours.  The sweep over 64 .. 8192 at one instance was flat on the program measured (DESIGN §3 "A
+// lone witness across the device", profiles/device_exec_wide.json), so it fixes nothing: 1024 is four strides of the run kernel's
+// workgroup, inside the 256 .. 4096 that were defensible beforehand, and keeps a program of narrower levels at the fewest launches.
+static constexpr int EXEC_WIDE_MIN_DEFAULT = 1024;
+static constexpr int EXEC_WIDE_MIN_MAX = 1 << 20;
 static inline Stream ctx_exec_stream(zkhip_ctx* ctx) {
     if (!ctx->exec_made) { ctx->exec_stream = stream_create(); ctx->exec_made = true; }
     return ctx->exec_stream;
@@ -2266,7 +2276,8 @@ struct Prover {
     }
 
     // ---- witnesses computed on the device (wexec.cuh): `count` instances of the plan's program, a chunk at a time, on the context's
-    // exec stream and in its exec buffers — no proof slot, no other stream.  Per chunk: the arguments in, k_exec_program, the verdict
+    // exec stream and in its exec buffers — no proof slot, no other stream.  Per chunk: the arguments in, k_exec_program (or, with
+    // ZKHIP_TUNE_EXEC_WIDE, the plan's levels as launches of k_exec_level / k_exec_levels_run), the verdict
     // words back (the host makes a resident assignment for every instance that ran through), then the gathers and the copies out.
     // made[i]: the assignment of instance i, or null.  Returns the number of instances that failed a check.
     static u64 compute_witness(zkhip_ctx* ctx, const zkhip_xplan* plan, u32 count, const uint8_t* args, std::vector<std::unique_ptr<zkhip_assignment>>* made,
@@ -2287,12 +2298,50 @@ struct Prover {
         std::vector<void*> ptrs(chunk);
         std::vector<uint8_t> tmp;
         u64 n_failed = 0;
+        // the route (read at each call): one work-item per instance, or the plan's levels cut into launches at wide_min
+        const bool wide = ctx->exec_wide;
+        const u32 wide_min = (u32)(ctx->exec_wide_min > 0 ? ctx->exec_wide_min : EXEC_WIDE_MIN_DEFAULT);
+        const u32 n_levels = h.level_start.empty() ? 0 : (u32)h.level_start.size() - 1;
+        u64 launches = 1;
+        if (wide) {
+            launches = 0;
+            bool in_run = false;
+            for (u32 lv = 0; lv < n_levels; ++lv) {
+                const bool narrow = h.level_start[lv + 1] - h.level_start[lv] < wide_min;
+                launches += !narrow || !in_run;
+                in_run = narrow;
+            }
+        }
+        ctx->exec_last[0] = wide ? 2 : 1;
+        ctx->exec_last[1] = (count + chunk - 1) / chunk;
+        ctx->exec_last[2] = launches;
+        ctx->exec_last[3] = wide_min;
         for (u64 c0 = 0; c0 < count; c0 += chunk) {
             const u32 c = (u32)std::min<u64>(chunk, count - c0);
             const dim3 waves(blocks_for(c, WX_BLOCK));
             if (h.n_args) dev_h2d(ctx->xargs.p, args + c0 * h.n_args * 32, (size_t)c * h.n_args * 32, s);
-            ZK_LAUNCH((k_exec_program<Fr>), waves, dim3(WX_BLOCK), 0, s, ptr<u32>(plan->code), ptr<u32>(plan->pool), ptr<uint8_t>(ctx->xargs), (u32)h.n_args, c, chunk,
-                      ptr<Fr>(ctx->xstore), ptr<u32>(ctx->xverdict));
+            if (!wide) {
+                ZK_LAUNCH((k_exec_program<Fr>), waves, dim3(WX_BLOCK), 0, s, ptr<u32>(plan->code), ptr<u32>(plan->pool), ptr<uint8_t>(ctx->xargs), (u32)h.n_args, c, chunk,
+                          ptr<Fr>(ctx->xstore), ptr<u32>(ctx->xverdict));
+            } else {
+                // the levels in ascending order: a level of wide_min instructions or more is a launch of its own over the whole
+                // device, every maximal run of narrower ones a launch of one workgroup per instance; the stream orders the launches
+                ZK_LAUNCH((k_exec_begin<Fr>), waves, dim3(WX_BLOCK), 0, s, c, ptr<Fr>(ctx->xstore), ptr<u32>(ctx->xverdict));
+                for (u32 lv = 0; lv < n_levels;) {
+                    const u32 first = h.level_start[lv], width = h.level_start[lv + 1] - first;
+                    if (width >= wide_min) {
+                        ZK_LAUNCH((k_exec_level<Fr>), dim3(blocks_for(width, WX_BLOCK), std::min<u32>(c, 65535)), dim3(WX_BLOCK), 0, s, ptr<u32>(plan->code), ptr<u32>(plan->pool),
+                                  ptr<u32>(plan->sched), first, width, ptr<uint8_t>(ctx->xargs), (u32)h.n_args, c, chunk, ptr<Fr>(ctx->xstore), ptr<u32>(ctx->xverdict));
+                        ++lv;
+                        continue;
+                    }
+                    u32 end = lv + 1;
+                    while (end < n_levels && h.level_start[end + 1] - h.level_start[end] < wide_min) ++end;
+                    ZK_LAUNCH((k_exec_levels_run<Fr>), dim3(c), dim3(WX_RUN_BLOCK), 0, s, ptr<u32>(plan->code), ptr<u32>(plan->pool), ptr<u32>(plan->sched),
+                              ptr<u32>(plan->level_start), lv, end, ptr<uint8_t>(ctx->xargs), (u32)h.n_args, chunk, ptr<Fr>(ctx->xstore), ptr<u32>(ctx->xverdict));
+                    lv = end;
+                }
+            }
             dev_d2h(verdict.data(), ctx->xverdict.p, (size_t)c * 4, s);
             stream_sync(s);
             for (u32 i = 0; i < c; ++i) {

@@ -465,6 +465,7 @@ ExecPlan Hip::load_exec_plan(const System& system, const uint8_t* program_bytes,
     check(zkhip_xplan_dims(p.plan_, p.dims_));
     return p;
 }
+void Hip::set_exec_wide(bool on) { check(zkhip_ctx_tune(ctx_, ZKHIP_TUNE_EXEC_WIDE, on ? 1 : 0)); }
 std::vector<ComputedWitness> Hip::compute_witness(const ExecPlan& plan, const uint8_t* args, uint32_t count, bool want_files) {
     std::vector<ComputedWitness> out(count);
     if (!count) return out;

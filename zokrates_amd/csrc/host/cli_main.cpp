@@ -3,7 +3,7 @@
 //   zkhip-cli generate-proof -i out -w witness -p proving.key -j proof.json [-s g16|gm17] [--entropy TEXT]
 //                            [--key-cache DIR] [--device N] [--timings] [--verify [--device-verify]] [--check] [--compact-witness] [--device-witness]
 //   zkhip-cli generate-proof -i out --arguments v1 v2 ... -p proving.key -j proof.json      (the witness computed on the device)
-//   zkhip-cli compute-witness -i out -a v1 v2 ... -o witness [--verbose] [--device N]
+//   zkhip-cli compute-witness -i out -a v1 v2 ... -o witness [--verbose] [--wide] [--device N]
 //
 // Mirrors /root/reference/zokrates_cli/src/ops/generate_proof.rs:95-202: the compiled program (`out`), the witness and the
 // proving key are read from files, the proof is written as JSON, one proof per process; `--entropy` seeds the RNG as
@@ -73,8 +73,8 @@ std::pair<int, int> cpu_and_node() {
 int usage() {
     fprintf(stderr, "usage: zkhip-cli generate-proof -i <out> -w <witness> -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] "
                     "[--key-cache DIR] [--device N] [--timings] [--verify [--device-verify]] [--check] [--compact-witness] [--device-witness] [--full-tables]\n"
-                    "       zkhip-cli generate-proof -i <out> --arguments v1 v2 ... -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
-                    "       zkhip-cli compute-witness -i <out> [-a v1 v2 ...] [-o <witness>] [--verbose] [--device N]\n"
+                    "       zkhip-cli generate-proof -i <out> --arguments v1 v2 ... -p <proving.key> -j <proof.json> [-s g16|gm17] [--entropy TEXT] [--wide] [--device N]\n"
+                    "       zkhip-cli compute-witness -i <out> [-a v1 v2 ...] [-o <witness>] [--verbose] [--wide] [--device N]\n"
                     "       zkhip-cli setup -i <out> -p <proving.key> -v <verification.key> [-s g16|gm17] [--entropy TEXT] [--device N]\n"
                     "       zkhip-cli verify [-v <verification.key>] [-j <proof.json>] [--device] [--timings [--repeat N]]\n"
                     "       zkhip-cli print-proof [-j <proof.json>] [-f remix|json]\n");
@@ -131,14 +131,15 @@ ComputedWitness compute_one(Hip& hip, const System& system, const Mapped& prog_b
 }
 }  // namespace
 
-// zkhip-cli compute-witness -i out -a v1 v2 ... -o witness [--verbose] [--device N]
+// zkhip-cli compute-witness -i out -a v1 v2 ... -o witness [--verbose] [--wide] [--device N]
 // (/root/reference/zokrates_cli/src/ops/compute_witness.rs:98-233 with raw arguments: "Computing witness...", with --verbose the return
 // values as the JSON of a tuple of field elements, the `witness` file, "Witness file written to '..'".  --abi, --stdin, --json and
-// --circom-witness are not built.)  The witness is computed on the device (Hip::compute_witness): one instance, one lane.
+// --circom-witness are not built.)  The witness is computed on the device (Hip::compute_witness): one instance on one lane, or with --wide
+// across the device, level by level (Hip::set_exec_wide) — the same file.
 int cmd_compute_witness(int argc, char** argv) {
     std::string input = "out", output = "witness";
     std::vector<uint8_t> args;
-    bool verbose = false;
+    bool verbose = false, wide = false;
     int device = 0;
     try {
         for (int i = 2; i < argc; ++i) {
@@ -148,6 +149,7 @@ int cmd_compute_witness(int argc, char** argv) {
             else if (a == "-o" || a == "--output") output = val();
             else if (a == "-a" || a == "--arguments") args = take_arguments(argc, argv, i);
             else if (a == "--verbose") verbose = true;
+            else if (a == "--wide") wide = true;
             else if (a == "--device") device = atoi(val().c_str());
             else return usage();
         }
@@ -155,6 +157,7 @@ int cmd_compute_witness(int argc, char** argv) {
         const Mapped prog_bytes(input);
         const Program program(prog_bytes.data, prog_bytes.size);
         Hip hip(device);
+        hip.set_exec_wide(wide);
         const System system = hip.load_system(program);
         const ComputedWitness w = compute_one(hip, system, prog_bytes, args);
         if (verbose) {
@@ -325,7 +328,7 @@ int main(int argc, char** argv) {
     if (argc >= 2 && strcmp(argv[1], "pairing-check") == 0) return cmd_pairing_check(argc, argv);
     if (argc < 2 || strcmp(argv[1], "generate-proof") != 0) return usage();
     std::string input = "out", witness_path = "witness", pk_path = "proving.key", proof_path = "proof.json", scheme_s = "g16", entropy, cache_dir;
-    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false, device_witness = false, device_verify = false;
+    bool have_entropy = false, timings = false, self_check = false, resident_tables = false, check_first = false, compact = false, device_witness = false, device_verify = false, wide = false;
     int device = 0;
     bool from_arguments = false;      // --arguments in place of -w: the witness computed on the device, the proof from its resident assignment
     std::vector<uint8_t> arguments;
@@ -337,6 +340,7 @@ int main(int argc, char** argv) {
             try { arguments = take_arguments(argc, argv, i); } catch (const Error& e) { fprintf(stderr, "zkhip-cli: %s\n", e.what()); return 1; }
             from_arguments = true;
         }
+        else if (a == "--wide") wide = true;                         // with --arguments: the witness level by level across the device (the same proof.json)
         else if (a == "--verify") self_check = true;
         else if (a == "--device-verify") device_verify = true;   // with --verify: that check on the GPU (Hip::verify_batch) instead of the host CPU
         else if (a == "--check") check_first = true;                 // the witness against the constraints, on the device, before proving
@@ -479,7 +483,8 @@ int main(int argc, char** argv) {
         const double upload_ms = tm.r1cs_upload;
         Proof proof;
         if (from_arguments) {
-            // the statements run on the device (one instance: one lane), the proof from the assignment they leave there
+            // the statements run on the device (one instance: one lane, or --wide), the proof from the assignment they leave there
+            hip.set_exec_wide(wide);
             t0 = std::chrono::steady_clock::now();
             system = hip.load_system(*program);
             const double ms_system = ms_since(t0);

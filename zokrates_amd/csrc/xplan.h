@@ -13,7 +13,10 @@
 // zkhip_prog_parse read is walked a second time, with the combinations RAW — no duplicates merged, no zero coefficients dropped:
 // is_assignee looks at the raw LinComb, which the R1CS inside zkhip_prog no longer has.
 //
-// Pure host code over ingest.h's zkhip_prog and field.cuh (tests/host/exec_plan.cpp compiles it alone); the kernels are in wexec.cuh,
+// The plan also holds the stream's LEVEL SCHEDULE (xplan_schedule below): which instructions depend on which is a property of the
+// stream alone, computed here once, for the level-scheduled route of wexec.cuh (k_exec_level, k_exec_levels_run).
+//
+// Pure host code over ingest.h's zkhip_prog and field.cuh (tests/host/exec_plan.cpp and exec_levels.cpp compile it alone); the kernels are in wexec.cuh,
 // the resident plan and the entry points in core.cuh / zkhip_api.hip.
 #pragma once
 #include <algorithm>
@@ -61,13 +64,89 @@ struct XPlanHost {
     std::vector<uint32_t> file_slots;      // their slots
     std::vector<uint32_t> input_cols;      // public arguments in argument order, then ~out_0 .. ~out_{R-1} (as WPlanTables)
     std::vector<uint32_t> row_of;          // R1CS row of statement k (XPLAN_NO_ROW: not a constraint)
+    // the level schedule (xplan_schedule below): the word offset of every instruction by (level, opcode, offset), and where each
+    // level begins in it (levels + 1 entries; level L of the text is level_start[L - 1] .. level_start[L])
+    std::vector<uint32_t> sched;
+    std::vector<uint32_t> level_start;
     uint64_t store_bytes_per_instance() const { return slots * 32; }
     uint64_t file_bytes() const { return 8 + 40 * (uint64_t)file_ids.size(); }
     void dims(uint64_t out[8]) const {
         out[0] = n_args; out[1] = n_statements; out[2] = n_defines; out[3] = n_checks; out[4] = n_directives; out[5] = file_ids.size();
         out[6] = n_extra; out[7] = store_bytes_per_instance();
     }
+    void levels(uint64_t out[4]) const {
+        const uint64_t nl = level_start.empty() ? 0 : level_start.size() - 1;
+        out[0] = nl; out[1] = 0; out[2] = sched.size(); out[3] = 0;
+        for (uint64_t k = 0; k < nl; ++k) {
+            const uint64_t width = level_start[k + 1] - level_start[k];
+            out[1] = std::max(out[1], width);
+            out[3] += width < 64;
+        }
+    }
 };
+
+// ---- the level schedule: which instructions of a stream may run side by side
+// One instruction of the stream at word `pc`: read(slot) for every slot a combination names, THEN write(slot) for every slot it
+// stores (an instruction evaluates all its inputs before its first store).  Returns the offset of the next instruction; XOP_END and
+// a word that is no opcode return `pc` itself.
+template <class Read, class Write>
+inline uint32_t xplan_walk(const uint32_t* code, uint32_t pc, Read&& read, Write&& write) {
+    const uint32_t op = code[pc];
+    uint32_t at = pc + 1;
+    auto lcs = [&](int count) {
+        for (int k = 0; k < count; ++k) {
+            const uint32_t n = code[at++];
+            for (uint32_t t = 0; t < n; ++t, at += 2) read(code[at]);
+        }
+    };
+    switch (op) {
+        case XOP_ARG: write(code[at + 1]); return at + 2;
+        case XOP_DEFINE: { const uint32_t o = code[at++]; lcs(2); write(o); return at; }
+        case XOP_CHECK: ++at; lcs(3); return at;
+        case XOP_CONDEQ: { const uint32_t o0 = code[at], o1 = code[at + 1]; at += 2; lcs(2); write(o0); write(o1); return at; }
+        case XOP_BITS: { const uint32_t n = code[at++]; lcs(2); for (uint32_t k = 0; k < n; ++k) write(code[at + k]); return at + n; }
+        case XOP_DIV: case XOP_XOR: case XOP_OR: { const uint32_t o = code[at++]; lcs(4); write(o); return at; }
+        case XOP_SHA3: case XOP_SHACH: { const uint32_t o = code[at++]; lcs(6); write(o); return at; }
+        case XOP_EDIV: { const uint32_t o0 = code[at], o1 = code[at + 1]; at += 2; lcs(4); write(o0); write(o1); return at; }
+        default: return pc;
+    }
+}
+// Levels of a stream over `slots` slots.  Per slot W, the level of the last write (slot 0, ~one, counts as written at level 0, before
+// the first level runs) and R, the highest level that read the current value (0 after a write).  An instruction sits at the smallest
+// L >= 1 above W of every slot it reads (read after write) and above W and R of every slot it writes (write after write, write after
+// read: a directive's output may overwrite a defined variable, a repeated parameter writes twice — both land strictly after every
+// reader of the old value).  The instructions of one level run in no order.  `sched` is sorted by level, then opcode, then offset,
+// so that neighbouring work-items mostly run one arm of the kernel's switch.
+inline void xplan_schedule(const std::vector<uint32_t>& code, uint64_t slots, std::vector<uint32_t>& sched, std::vector<uint32_t>& level_start) {
+    std::vector<uint32_t> W(slots, 0), R(slots, 0), level_of;
+    sched.clear();
+    uint32_t top = 0;
+    for (uint32_t pc = 0;;) {
+        uint32_t L = 0;
+        const uint32_t next = xplan_walk(code.data(), pc, [&](uint32_t s) { L = std::max(L, W[s]); },
+                                         [&](uint32_t s) { L = std::max(L, std::max(W[s], R[s])); });
+        if (next == pc) break;
+        ++L;
+        xplan_walk(code.data(), pc, [&](uint32_t s) { R[s] = std::max(R[s], L); }, [&](uint32_t s) { W[s] = L; R[s] = 0; });
+        sched.push_back(pc);
+        level_of.push_back(L);
+        top = std::max(top, L);
+        pc = next;
+    }
+    std::vector<uint32_t> idx(sched.size());
+    for (uint32_t k = 0; k < idx.size(); ++k) idx[k] = k;
+    std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) {
+        if (level_of[a] != level_of[b]) return level_of[a] < level_of[b];
+        if (code[sched[a]] != code[sched[b]]) return code[sched[a]] < code[sched[b]];
+        return sched[a] < sched[b];
+    });
+    level_start.assign((size_t)top + 1, 0);
+    for (uint32_t L : level_of) ++level_start[L];      // [L] = width of level L; [0] = 0
+    for (uint32_t L = 1; L <= top; ++L) level_start[L] += level_start[L - 1];      // [L] = end of level L = start of level L + 1
+    std::vector<uint32_t> sorted(sched.size());
+    for (uint32_t k = 0; k < idx.size(); ++k) sorted[k] = sched[idx[k]];
+    sched.swap(sorted);
+}
 
 namespace xplan_detail {
 
@@ -488,6 +567,7 @@ void build(const zkhip_prog& prog, int curve, uint64_t l, uint64_t w, uint64_t n
         if (!c.slot_of(id, slot) || !c.defined[slot]) fail(ZKHIP_ERR_BAD_ARG, "output " + witness_var_name(id) + " is never computed by the program");
         out.input_cols.push_back(slot);
     }
+    xplan_schedule(out.code, out.slots, out.sched, out.level_start);
 }
 
 inline uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }

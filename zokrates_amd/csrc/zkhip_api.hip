@@ -466,6 +466,8 @@ int32_t zkhip_ctx_tune(zkhip_ctx* ctx, int32_t which, int32_t value) {
                 require((value & (value - 1)) == 0, ZKHIP_ERR_BAD_ARG, "NTT_COLS must be 1, 2, 4 or 8 (the cols pass covers N2 / cols workgroups exactly)");
                 dev_sync_all(); ctx->ntt_cols = value; ctx->plans.clear(); break;
             case ZKHIP_TUNE_EXEC_CHUNK: in(0, 65535 * (int)WX_BLOCK); ctx->exec_chunk = value; break;      // (the gathers' grids hold the waves of a chunk along y)
+            case ZKHIP_TUNE_EXEC_WIDE: in(0, 1); ctx->exec_wide = value != 0; break;      // (read at each zkhip_compute_witness; changes no result)
+            case ZKHIP_TUNE_EXEC_WIDE_MIN: in(0, EXEC_WIDE_MIN_MAX); ctx->exec_wide_min = value; break;
             case ZKHIP_TUNE_ALLOC_FILL: dev_sync_all(); alloc_fill_word().store((uint32_t)value); break;   // (tests only, process-wide: devrt.h)
             default: throw ApiError{ZKHIP_ERR_BAD_ARG, "unknown tunable"};
         }
@@ -759,6 +761,8 @@ int32_t zkhip_xplan_create(zkhip_ctx* ctx, const zkhip_prog* prog, const zkhip_r
         up(plan->file_ids, host->file_ids.data(), host->file_ids.size() * 8);
         up(plan->file_slots, host->file_slots.data(), host->file_slots.size() * 4);
         up(plan->input_cols, host->input_cols.data(), host->input_cols.size() * 4);
+        up(plan->sched, host->sched.data(), host->sched.size() * 4);
+        up(plan->level_start, host->level_start.data(), host->level_start.size() * 4);
         stream_sync(ctx->stream);
         plan->host = host;
         *out = plan.release();
@@ -768,6 +772,16 @@ void zkhip_xplan_free(zkhip_xplan* plan) { delete plan; }
 int32_t zkhip_xplan_dims(const zkhip_xplan* plan, uint64_t out[8]) {
     if (!plan || !out) return ZKHIP_ERR_BAD_ARG;
     plan->host->dims(out);
+    return ZKHIP_OK;
+}
+int32_t zkhip_xplan_levels(const zkhip_xplan* plan, uint64_t out[4]) {
+    if (!plan || !out) return ZKHIP_ERR_BAD_ARG;
+    plan->host->levels(out);
+    return ZKHIP_OK;
+}
+int32_t zkhip_exec_last(const zkhip_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return ZKHIP_ERR_BAD_ARG;
+    for (int k = 0; k < 4; ++k) out[k] = ctx->exec_last[k];
     return ZKHIP_OK;
 }
 // (on its own stream and in its own buffers, as the pairing checks: allowed while a proof queue is open, refused while a split proof

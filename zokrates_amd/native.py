@@ -81,7 +81,7 @@ class Library:
         "zkhip_wplan_create", "zkhip_wplan_free", "zkhip_assignment_upload_witness", "zkhip_queue_submit_witness", "zkhip_queue_collect_inputs",
         "zkhip_pairing_products", "zkhip_tower_op", "zkhip_vk_load_g16", "zkhip_vk_load_gm17", "zkhip_vk_free", "zkhip_vk_dims",
         "zkhip_verify_g16_batch", "zkhip_verify_gm17_batch",
-        "zkhip_xplan_create", "zkhip_xplan_free", "zkhip_xplan_dims", "zkhip_compute_witness",
+        "zkhip_xplan_create", "zkhip_xplan_free", "zkhip_xplan_dims", "zkhip_xplan_levels", "zkhip_exec_last", "zkhip_compute_witness",
     ]
 
     def __init__(self, path=None):
@@ -207,6 +207,8 @@ class Library:
         L.zkhip_xplan_create.restype = i32; L.zkhip_xplan_create.argtypes = [vp, vp, vp, vp, sz, pp]
         L.zkhip_xplan_free.restype = None; L.zkhip_xplan_free.argtypes = [vp]
         L.zkhip_xplan_dims.restype = i32; L.zkhip_xplan_dims.argtypes = [vp, vp]
+        L.zkhip_xplan_levels.restype = i32; L.zkhip_xplan_levels.argtypes = [vp, vp]
+        L.zkhip_exec_last.restype = i32; L.zkhip_exec_last.argtypes = [vp, vp]
         L.zkhip_compute_witness.restype = i32; L.zkhip_compute_witness.argtypes = [vp, vp, u32, vp, vp, vp, u64, vp, u64, vp, vp, vp]
         self.L = L
 
@@ -278,7 +280,7 @@ class Context:
         self._check(self.lib.L.zkhip_describe(self.h, buf, 256))
         return buf.value.decode()
 
-    TUNABLES = {"msm_c": 1, "msm_waves": 2, "msm_lanes": 3, "msm_min_slice": 4, "fold_scan": 5, "serial": 6, "ntt_single_max_log": 7, "ntt_cols": 8, "slots": 9, "z_gate": 10, "fuse_z": 11, "msm_fused_waves": 12, "stream_jitter": 13, "ntt_max_sublog": 16, "msm_sets": 17, "skip_inf": 18, "b_sort": 19, "heavy_runs": 20, "fold_hg": 25, "ntt_fuse_first": 26, "pipe_plan": 28, "exec_chunk": 29, "alloc_fill": 30}
+    TUNABLES = {"msm_c": 1, "msm_waves": 2, "msm_lanes": 3, "msm_min_slice": 4, "fold_scan": 5, "serial": 6, "ntt_single_max_log": 7, "ntt_cols": 8, "slots": 9, "z_gate": 10, "fuse_z": 11, "msm_fused_waves": 12, "stream_jitter": 13, "ntt_max_sublog": 16, "msm_sets": 17, "skip_inf": 18, "b_sort": 19, "heavy_runs": 20, "fold_hg": 25, "ntt_fuse_first": 26, "pipe_plan": 28, "exec_chunk": 29, "alloc_fill": 30, "exec_wide": 31, "exec_wide_min": 32}
 
     def clock_probe(self, duration_us=2000):
         """`zkhip_ctx_clock_probe`: the shader clock (GHz) the device runs at over the next `duration_us` microseconds — one wavefront
@@ -291,6 +293,13 @@ class Context:
     def tune(self, name, value):
         """`zkhip_ctx_tune`: development / measurement knobs (window width, slices, fold form, serial streams ...)."""
         self._check(self.lib.L.zkhip_ctx_tune(self.h, self.TUNABLES[name], int(value)))
+
+    def exec_last(self):
+        """`zkhip_exec_last`: (route, chunks, program launches per chunk, wide_min in force) of the last `compute_witness` — route 0
+        none yet, 1 one work-item per instance, 2 level-scheduled (`tune("exec_wide", 1)`)."""
+        d = np.zeros(4, dtype=np.uint64)
+        self._check(self.lib.L.zkhip_exec_last(self.h, _ptr(d)))
+        return tuple(int(x) for x in d)
 
     def upload_witness(self, plan, witness_bytes, want_inputs=True):
         """`zkhip_assignment_upload_witness`: a ZoKrates `witness` file ordered and checked on the device through `plan`
@@ -1129,6 +1138,12 @@ class ExecPlan:
             setattr(self, k, v)
         self.n_inputs = prog.n_public_args + prog.return_count
         self.file_bytes = 8 + 40 * self.n_entries
+
+    def levels(self):
+        """`zkhip_xplan_levels`: (levels, instructions of the widest level, instructions in all, levels of fewer than 64)."""
+        d = np.zeros(4, dtype=np.uint64)
+        self.ctx._check(self.ctx.lib.L.zkhip_xplan_levels(self.h, _ptr(d)))
+        return tuple(int(x) for x in d)
 
     def close(self):
         if self.h:
